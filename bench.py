@@ -1,10 +1,20 @@
 #!/usr/bin/env python3
 """Decode-throughput benchmark (BASELINE.json metric): Llama-2-7B fp16, batch 1, ctx 2048, TP = N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python bench.py --preset llama3-8b --ctx 4096 --batch 8      # BASELINE configs[4] (C4) at TP = N
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it builds the model, settles and warms up, times the K
+steps, writes the last step's outputs if --dump-outputs is given, and prints the result line (metric, value,
+unit, ms_per_step, config, step_ms, settle). Everything else below — roofline, greedy_64, prefill, cpu_baseline —
+takes runs of its own and is measured and reported only under --full.
+
+--dump-outputs DIR writes what the last timed step returned to a caller, as float32 / float64 .npy files:
+DIR/logits.npy ([batch, vocab], the vocab shards of all ranks joined) and DIR/next_token.npy ([batch], the
+greedy argmax of each sequence). Weights, KV rows, tokens and positions are seeded, so the same arguments give
+the same inputs in every run and two builds can be compared output for output.
 
 A step is one full decode step of the 32-layer model at position 2047 (KV rows 0..2046 resident in
 HBM), replayed from its captured hipGraph; the step is idempotent (it rewrites the same K/V row), so
@@ -13,7 +23,7 @@ architecture (no checkpoints are reachable); every input is resident in HBM befo
 Under TP each rank holds 1/N of the heads / FFN columns / vocab and the step all-reduces twice per
 layer over RCCL; value = tokens/s of the whole job (1 token per step across all ranks).
 
-Rank 0 prints one JSON line. `roofline` prices the DOMINANT kernel (the family with the largest share
+Rank 0 prints one JSON line. Under --full: `roofline` prices the DOMINANT kernel (the family with the largest share
 of the step's device time, e.g. the fused RMSNorm + gate/up GEMV + SwiGLU at C1): its algorithmic bytes
 per launch / its mean launch time, measured live with HIP events on the engine's own stream
 (sli_model_time_families); `roofline.families` lists every family the same way, and `roofline.traffic`
@@ -60,6 +70,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the last step's outputs (logits, next token) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what takes runs of its own: the per-family roofline, the greedy run, "
+                         "the prefill and the CPU baseline (the options below --settle-ms shape these)")
     ap.add_argument("--w-dtype", default="f16", choices=["f16", "i8", "f32"])
     ap.add_argument("--preset", default="llama2-7b")
     ap.add_argument("--ctx", type=int, default=CTX)
@@ -86,7 +101,10 @@ def parse():
         (p for p in (os.path.join(ROOT, "profiles", f) for f in ("r6_gemv_traffic.json", "r5_gemv_traffic.json", "r4_gemv_traffic.json",
                                                                    "r3_gemv_traffic.json"))
          if os.path.exists(p)), os.path.join(ROOT, "profiles", "r5_gemv_traffic.json")))
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def _time_steps(fwd, timing, n_layers, budget_s, min_steps=3, max_steps=50):
@@ -409,7 +427,70 @@ def main():
     st = model.state()
     if st["error"]:
         raise SystemExit(f"device error flag {st['error']}")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, B, dist if dist_on else None, rank, world)
     wbytes, kvbytes = model.step_bytes()
+    ms = 1e3 * elapsed / a.steps
+    value = B * a.steps / elapsed  # tokens/s of the whole job (B tokens per step, all ranks on the same tokens)
+    out = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "tokens/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(ms, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": a.w_dtype if a.w_dtype != "f16" else "fp16",
+        "data": "synthetic",
+        "config": {"workload": f"{a.preset} decode step, batch {B}, ctx {a.ctx}, tensor parallel {world}",
+                   "global_batch": B, "seq_len": a.ctx, "parallelism": f"tp{world}", "weights": a.w_dtype,
+                   "kv_cache": "fp16", "accumulate": "fp32",
+                   "step_bytes_per_gpu": round(wbytes + kvbytes),
+                   "hbm_roofline_tokens_per_s": round(B * HBM_PEAK_GBS * 1e9 / (wbytes + kvbytes), 1),
+                   "step_frac_of_hbm_peak": round((wbytes + kvbytes) / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)},
+        "exec": exec_mode,
+        "tp_allreduce": allreduce,
+        "qkv_attn_fused": model.fused_qkv_attn(),
+        "full": a.full,
+        "step_ms": step_stats(marks.durations_ms(), ms),
+        "settle": {**settle, "note": "untimed replays before the --warmup steps (--settle-ms)"},
+    }
+    if a.full:
+        full_report(out, a, model, cfg, barrier, rank, world, exec_mode, ms, wbytes, kvbytes)
+    model.close()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist_on:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, model, B, dist, rank, world):
+    """--dump-outputs: what the last timed step handed its caller — the logits of every sequence (each rank's
+    vocab shard, joined in vocab order on rank 0) and the greedy next token — as <path>/<name>.npy."""
+    import numpy as np
+    shard, lo = model.logits()
+    shards = [(lo, shard.reshape(B, -1))]
+    if dist is not None:
+        shards = [None] * world
+        dist.all_gather_object(shards, (lo, shard.reshape(B, -1)))
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    logits = np.concatenate([s for _, s in sorted(shards, key=lambda x: x[0])], axis=1)
+    np.save(os.path.join(path, "logits.npy"), logits.astype(np.float32))
+    np.save(os.path.join(path, "next_token.npy"),
+            np.array([model.state(b)["last_argmax"] for b in range(B)], np.float64))
+    progress(f"outputs written to {path}: logits {logits.shape}, next_token ({B},)")
+
+
+def full_report(out, a, model, cfg, barrier, rank, world, exec_mode, ms, wbytes, kvbytes):
+    """--full: the measurements beside the headline that take runs of their own (per-family probes and the roofline,
+    the greedy run, the prefill, the CPU baseline), added to the result line `out`."""
+    B = a.batch
     progress("timed; per-family probes")
     fam = model.time_families(a.gemv_iters)
     sfl = model.time_stream(a.gemv_iters)  # the measured streaming-read floor of the same launches
@@ -453,30 +534,7 @@ def main():
         except (OSError, ValueError, KeyError):
             traffic = None
 
-    ms = 1e3 * elapsed / a.steps
-    value = B * a.steps / elapsed  # tokens/s of the whole job (B tokens per step, all ranks on the same tokens)
-    out = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "tokens/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(ms, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": a.w_dtype if a.w_dtype != "f16" else "fp16",
-        "data": "synthetic",
-        "config": {"workload": f"{a.preset} decode step, batch {B}, ctx {a.ctx}, tensor parallel {world}",
-                   "global_batch": B, "seq_len": a.ctx, "parallelism": f"tp{world}", "weights": a.w_dtype,
-                   "kv_cache": "fp16", "accumulate": "fp32",
-                   "step_bytes_per_gpu": round(wbytes + kvbytes),
-                   "hbm_roofline_tokens_per_s": round(B * HBM_PEAK_GBS * 1e9 / (wbytes + kvbytes), 1),
-                   "step_frac_of_hbm_peak": round((wbytes + kvbytes) / (ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 4)},
-        "exec": exec_mode,
-        "tp_allreduce": allreduce,
-        "qkv_attn_fused": model.fused_qkv_attn(),
+    out.update({
         "roofline": {"bound": "hbm", "kernel": f"{dom}: {FAMILY_KERNELS[B > 1][dom]}",
                      "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
@@ -503,9 +561,7 @@ def main():
                                                   "frac": round(g["bytes_per_launch"] / (g["avg_us"] * 1e-6) / 1e9
                                                                 / HBM_PEAK_GBS, 4)}},
         "greedy_64": greedy,
-        "step_ms": step_stats(marks.durations_ms(), ms),
-        "settle": {**settle, "note": "untimed replays before the --warmup steps (--settle-ms)"},
-    }
+    })
     out["greedy_64"]["timed_mean_over_greedy"] = round(ms / greedy["ms_per_step"], 4)
     if exec_mode.startswith("persist"):
         out["roofline"]["families_note"] = ("the launch graph's kernels by family (sli_model_time_families), probed beside "
@@ -582,12 +638,6 @@ def main():
                           "vs_token_by_token_s": round((n - 1) * ms * 1e-3, 4)}
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_seconds, a.preset, a.ctx)
-    model.close()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def _comm_fatal(e: BaseException) -> bool:

@@ -37,6 +37,17 @@ def build(force: bool = False) -> str | None:
     return LIB_PATH
 
 
+def build_level2() -> str | None:
+    """Build _ref/level2/dropin_llama_refops (oracle/Makefile `level2`: the reference's op sources compiled in place
+    against this repo's include/, linked with libsli.so, which must exist) where the reference sources exist, so the
+    GPU tests that run it find it in a fresh tree as well."""
+    exe = os.path.join(_HERE, "_ref", "level2", "dropin_llama_refops")
+    if not source_present():
+        return exe if os.path.exists(exe) else None
+    subprocess.run(["make", "-s", "-C", _HERE, "level2", f"REF={REF_ROOT}"], check=True)
+    return exe
+
+
 def available() -> bool:
     return os.path.exists(LIB_PATH) or source_present()
 

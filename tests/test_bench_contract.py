@@ -1,5 +1,5 @@
 """The bench line contract (the task's bench.py section) on the committed round-6 bench lines (profiles/r6*_bench_c*.json,
-written by `python bench.py` on an MI355X): every required key, the roofline and cpu_baseline objects, the units and
+written by `python bench.py --full` on an MI355X): every required key, the roofline and cpu_baseline objects, the units and
 the arithmetic that ties them together (value x ms_per_step = global batch; frac = achieved / peak; achieved = the
 dominant family's algorithmic bytes / its launch time), and the step_ms block (SURVEY §5's p50 / p99: one HIP event
 between consecutive graph replays of the timed window; its mean against the host clock, its p50 against the mean, the
