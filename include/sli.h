@@ -36,7 +36,10 @@ typedef enum {
                            (default 120 s): a peer or the communicator is wedged; the communicator was aborted */
 } sli_status;
 
-typedef enum { SLI_DT_F32 = 0, SLI_DT_F16 = 1, SLI_DT_I8 = 2 } sli_dtype;
+/* SLI_DT_MXFP4: OCP microscaling FP4 weights (e2m1 elements, one e8m0 scale per 32 consecutive columns; the layout
+ * and the quantisation rule are with sli_quant_mxfp4 below). A weight dtype of the model level and of the
+ * sli_*_mxfp4 entry points only. */
+typedef enum { SLI_DT_F32 = 0, SLI_DT_F16 = 1, SLI_DT_I8 = 2, SLI_DT_MXFP4 = 3 } sli_dtype;
 
 typedef void* sli_stream_t;
 
@@ -65,6 +68,29 @@ int sli_stream_sync(sli_stream_t stream);
  * [rows][cols] in w_dtype; w_row_scale[rows] multiplies each row for SLI_DT_I8 (NULL otherwise). */
 int sli_matmul(const float* x, const void* w, int w_dtype, const float* w_row_scale, float* y, int32_t rows,
                int32_t cols, float scale, sli_stream_t stream);
+
+/* MXFP4 weights. A [rows][cols] tensor needs cols % 32 == 0 and is two arrays in plain OCP layout:
+ *   data   uint8 [rows][cols / 2]: element 2i in bits 3:0 of byte i, element 2i + 1 in bits 7:4; a 4-bit code is the
+ *          sign in bit 3 and the magnitude {0, .5, 1, 1.5, 2, 3, 4, 6}[bits 2:0];
+ *   scales uint8 [rows][cols / 32], e8m0: the block's elements are multiplied by 2^(byte - 127).
+ * Quantisation of a block of 32 finite values w (deterministic): amax = max|w|; amax == 0 gives scale byte 127 and
+ * codes 0; otherwise e = clamp(floor(log2(amax)) - 2, -127, 127), scale byte e + 127 (255 is never produced), and
+ * each |w| * 2^-e (exact) is rounded to the nearest magnitude of the grid, ties to the even code, saturating at 6:
+ * <= .25 -> 0, (.25, .75) -> .5, [.75, 1.25] -> 1, (1.25, 1.75) -> 1.5, [1.75, 2.5] -> 2, (2.5, 3.5) -> 3,
+ * [3.5, 5] -> 4, > 5 -> 6; the sign bit is w's (a zero may carry either sign). NaN and Inf inputs are out of
+ * contract: the result for a block that holds one is unspecified.
+ *
+ * sli_mxfp4_bytes: the sizes of the two arrays (host only, no device needed); SLI_ERR_SHAPE if cols % 32 != 0.
+ * sli_quant_mxfp4: device fp32 [rows][cols] -> data, scales (device; data 16-byte aligned).
+ * sli_dequant_mxfp4: the inverse, fp32 [rows][cols] (exact: every element times scale is an fp32 value).
+ * sli_matmul_mxfp4: y[r] = scale * sum_c x[c] * W[r][c], x and y fp32, fp32 accumulation, on the GEMV of sli_matmul
+ * (x and data 16-byte aligned, cols below 16320). sli_matmul itself rejects SLI_DT_MXFP4 (its row scales are float). */
+int sli_mxfp4_bytes(int32_t rows, int32_t cols, size_t* data_bytes, size_t* scale_bytes);
+int sli_quant_mxfp4(const float* src, void* data, void* scales, int32_t rows, int32_t cols, sli_stream_t stream);
+int sli_dequant_mxfp4(const void* data, const void* scales, float* dst, int32_t rows, int32_t cols,
+                      sli_stream_t stream);
+int sli_matmul_mxfp4(const float* x, const void* data, const void* scales, float* y, int32_t rows, int32_t cols,
+                     float scale, sli_stream_t stream);
 
 /* Batched projection for B sequences decoding in lockstep (the reference is batch 1; this serves
  * SURVEY.md §8 config C4): y[b][r] = sum_c x[b][c] * W[r][c] for b < batch <= 8, on MFMA
@@ -125,7 +151,10 @@ int sli_argmax(const float* logits, int32_t n, int32_t* out_dev, sli_stream_t st
 typedef struct {
     int32_t vocab, dim, n_heads, n_kv_heads, head_dim, ffn, n_layers, max_len;
     float eps, theta;
-    int32_t w_dtype;  /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_I8 (per-row symmetric) */
+    int32_t w_dtype;  /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_I8 (per-row symmetric) / SLI_DT_MXFP4 (fp32 weights handed to
+                         the model are quantised by the rule at sli_quant_mxfp4; batch 1 only, the launch graph only,
+                         no GEMM prefill; dim, the local ffn width and the local q width multiples of 32, else
+                         SLI_ERR_SHAPE) */
     int32_t kv_dtype; /* SLI_DT_F32 / SLI_DT_F16 */
     int32_t act_mode; /* 0: reference sigmoid(gate)*up (swiglu_kernel.cpp:12-13); 1: SiLU(gate)*up */
     int32_t tp_rank, tp_size;
@@ -256,7 +285,7 @@ int sli_model_predict_batch(sli_model* m, const int32_t* prompts, const int32_t*
 int sli_model_get_kv(sli_model* m, int32_t layer, int32_t which, int32_t upto, float* host);
 int sli_model_get_kv_seq(sli_model* m, int32_t seq, int32_t layer, int32_t which, int32_t upto, float* host);
 /* Read back this rank's shard of a weight (sli_tp_plan window, n = n_rows * n_cols) as fp32 (int8 is
- * dequantised with its row scales). */
+ * dequantised with its row scales, MXFP4 with its block scales). */
 int sli_model_get_weight(sli_model* m, int32_t kind, int32_t index, float* host, int64_t n);
 int sli_model_stream(sli_model* m, sli_stream_t* out);
 /* Algorithmic HBM bytes of one step on this rank (weights, KV at the current position) — SURVEY.md §8(d). */

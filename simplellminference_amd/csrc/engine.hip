@@ -40,6 +40,8 @@
 namespace sli {
 
 struct LayerW {
+    // *_s: int8 row scales (float per row); mxfp4: the e8m0 block scales, uint8 [rows][cols / 32], behind the
+    // same pointers (mx_scales)
     void* qkv = nullptr;   // [(hq + 2 hkv) hd][D]
     float* qkv_s = nullptr;
     void* wo = nullptr;    // [D][hq hd]   (column slice of wo, re-laid contiguous)
@@ -66,7 +68,8 @@ struct sli_model {
     // local (this rank's) geometry
     int D = 0, L = 0, T = 0, V = 0, hd = 0, hq = 0, hkv = 0, Il = 0;
     int v_lo = 0, v_n = 0;
-    size_t wbytes = 4, kvbytes = 4;
+    double wbytes = 4;  // bytes per weight element (mxfp4: 0.5; its block scales are counted apart)
+    size_t kvbytes = 4;
     // device buffers
     void* emb = nullptr;
     float* emb_s = nullptr;
@@ -222,11 +225,36 @@ __global__ void __launch_bounds__(256) place_kernel(T* dst, float* dst_scale, in
     }
 }
 
+// The same window quantised to MXFP4 (mxfp4.h: the rule of sli.h), one thread per block of 32 columns. A block is
+// 32 consecutive columns of the full row, so a column window that starts and ends on multiples of 32 shares the
+// unsharded quantisation.
+template <class Src>
+__global__ void __launch_bounds__(256) place_mx_kernel(uint8_t* dst, uint8_t* dst_scale, int nrows, int ncols,
+                                                       int row_lo, int col_lo, int full_cols, Src src) {
+    const int bpr = ncols / kMxBlock;
+    const size_t nblk = (size_t)nrows * bpr;
+    for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < nblk; b += (size_t)gridDim.x * blockDim.x) {
+        const int r = (int)(b / bpr), cb = (int)(b - (size_t)r * bpr);
+        const uint64_t base = (uint64_t)(row_lo + r) * (uint64_t)full_cols + (uint64_t)(col_lo + cb * kMxBlock);
+        mx_quant_block([&](int i) { return src(base + i); }, dst, dst_scale, b);
+    }
+}
+
+static const uint8_t* mx_scales(const float* s) { return reinterpret_cast<const uint8_t*>(s); }
+
 template <class Src>
 static int place(sli_model* m, void* dst, float* dst_scale, int nrows, int ncols, int row_lo, int col_lo, int full_cols,
                  const Src& src) {
     const int blocks = std::min(nrows, 4096);
     hipStream_t s = m->stream;
+    if (m->c.w_dtype == SLI_DT_MXFP4) {
+        SLI_CHECK(ncols % kMxBlock == 0 && col_lo % kMxBlock == 0, SLI_ERR_SHAPE, "mxfp4: window not on 32-column blocks");
+        const size_t nblk = (size_t)nrows * (ncols / kMxBlock);
+        hipLaunchKernelGGL((place_mx_kernel<Src>), dim3((unsigned)std::min<size_t>(4096, (nblk + 255) / 256)), dim3(256), 0,
+                           s, (uint8_t*)dst, (uint8_t*)dst_scale, nrows, ncols, row_lo, col_lo, full_cols, src);
+        SLI_HIP(hipGetLastError());
+        return SLI_OK;
+    }
     switch (m->c.w_dtype) {
         case SLI_DT_F32:
             hipLaunchKernelGGL((place_kernel<float, Src>), dim3(blocks), dim3(256), 0, s, (float*)dst, dst_scale, nrows,
@@ -251,7 +279,13 @@ static int place_f32(sli_model* m, float* dst, int n, const Src& src) {
     return SLI_OK;
 }
 
-static char* wptr(void* base, size_t elem_bytes, size_t elems) { return (char*)base + elem_bytes * elems; }
+static char* wptr(void* base, double elem_bytes, size_t elems) { return (char*)base + (size_t)(elem_bytes * (double)elems); }
+// the scales of row `row` of a matrix with `cols` columns: a float per row (int8), a byte per 32 columns (mxfp4)
+static float* sptr(const sli_model* m, float* sbase, size_t row, int cols) {
+    if (!sbase) return nullptr;
+    if (m->c.w_dtype == SLI_DT_MXFP4) return (float*)((uint8_t*)sbase + row * (size_t)(cols / kMxBlock));
+    return sbase + row;
+}
 
 // Place one full reference tensor (kind, index) from `src` into this rank's shard (sli_tp_plan).
 template <class Src>
@@ -278,7 +312,7 @@ static int place_tensor(sli_model* m, int kind, int index, const Src& src) {
         default: return fail(SLI_ERR_ARG, "unknown tensor kind");
     }
     void* dst = wptr(base, m->wbytes, (size_t)w.dst_row_off * w.n_cols);
-    return place(m, dst, sbase ? sbase + w.dst_row_off : nullptr, w.n_rows, w.n_cols, w.row_lo, w.col_lo,
+    return place(m, dst, sptr(m, sbase, (size_t)w.dst_row_off, w.n_cols), w.n_rows, w.n_cols, w.row_lo, w.col_lo,
                  w.full_cols, src);
 }
 
@@ -593,19 +627,29 @@ static int tpl_launch(sli_model* m) {
 template <typename WT, typename KT>
 struct StepRecorder {
     static constexpr bool NT = true;  // streamed-once weights: non-temporal loads
+    // mxfp4: a matrix's *_s pointer holds its block scales, which go to the GEMV's loads (GemvIn::wscale), and
+    // the epilogues get no row scales
+    static constexpr bool MX = is_mx<WT>::value;
+    static const float* rs(const float* s) { return MX ? nullptr : s; }
+    static GemvIn gin(const float* x, const float* norm_w, float eps, int cols, const float* wscale) {
+        GemvIn in{x, norm_w, eps, cols};
+        if (MX) in.wscale = mx_scales(wscale);
+        return in;
+    }
     static int gemv_qkv(sli_model* m, int l) {
         const LayerW& w = m->layers[l];
-        GemvIn in{m->x, m->norms + (size_t)(2 * l) * m->D, m->c.eps, m->D};
+        const GemvIn in = gin(m->x, m->norms + (size_t)(2 * l) * m->D, m->c.eps, m->D, w.qkv_s);
         KT* kc = (KT*)m->kc + (size_t)l * m->hkv * m->T * m->hd;
         KT* vc = (KT*)m->vc + (size_t)l * m->hkv * m->T * m->hd;
-        EpiQKV<KT> e{m->q, kc, vc, w.qkv_s, &m->st->pos, m->sin_t, m->cos_t, m->hq, m->hkv, m->hd, m->T};
+        EpiQKV<KT> e{m->q, kc, vc, rs(w.qkv_s), &m->st->pos, m->sin_t, m->cos_t, m->hq, m->hkv, m->hd, m->T};
         SLI_HIP((launch_gemv_u<WT, 2, 4, NT>((const WT*)w.qkv, in, e, (m->hq + 2 * m->hkv) * (m->hd / 2), m->stream)));
         return SLI_OK;
     }
     // q/k/v + attention as one launch (qkv_attn.h) where the shape qualifies: *done = 1; 0: run the separate launches
     static int gemv_qkv_attn(sli_model* m, int l, int* done, bool dry = false) {
         *done = 0;
-        if constexpr (std::is_same<KT, __half>::value && !std::is_same<WT, float>::value) {
+        // (mxfp4 weights keep the separate launches: the shared launch's register budget was tuned for fp16 / int8)
+        if constexpr (std::is_same<KT, __half>::value && !std::is_same<WT, float>::value && !MX) {
             if (!m->qa_count || !qkv_attn_on(m)) return SLI_OK;
             const LayerW& w = m->layers[l];
             GemvIn in{m->x, m->norms + (size_t)(2 * l) * m->D, m->c.eps, m->D};
@@ -638,21 +682,22 @@ struct StepRecorder {
         if (m->wo_ks > 1) return gemv_wo_ks(m, l);
         const bool tp = m->partial;
         if (!m->wo_merge) {  // the attention merged its splits into attn: a plain input
-            GemvIn in{m->attn, nullptr, 0.0f, m->hq * m->hd};
+            const GemvIn in = gin(m->attn, nullptr, 0.0f, m->hq * m->hd, w.wo_s);
             if (fused_ar(m)) {
-                SLI_HIP((launch_gemv_u<WT, 1, 2, NT>((const WT*)w.wo, in, push_epi(m, w.wo_s, 0), m->D, m->stream)));
+                SLI_HIP((launch_gemv_u<WT, 1, 2, NT>((const WT*)w.wo, in, push_epi(m, rs(w.wo_s), 0), m->D, m->stream)));
                 return SLI_OK;
             }
-            EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, w.wo_s, 1.0f, m->D};
+            EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(w.wo_s), 1.0f, m->D};
             SLI_HIP((launch_gemv_u<WT, 1, 2, NT>((const WT*)w.wo, in, e, m->D, m->stream)));
             return SLI_OK;
         }
-        GemvIn in{m->attn, nullptr, 0.0f, m->hq * m->hd};
-        EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, w.wo_s, 1.0f, m->D};
+        const GemvIn in = gin(m->attn, nullptr, 0.0f, m->hq * m->hd, w.wo_s);
+        EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(w.wo_s), 1.0f, m->D};
         const AttnMergeIn am{m->part, &m->st->pos, attn_max_splits(m), attn_wg_positions(m->c.kv_dtype, m->hd), m->hd};
-        constexpr int UW = 2;  // int8 too (tools/gemv_lab i8: R1U2 7.5 us vs R1U1 7.95 on the 4096x4096 shape)
+        // int8 too (tools/gemv_lab i8: R1U2 7.5 us vs R1U1 7.95 on the 4096x4096 shape); mxfp4: kMxWoU
+        constexpr int UW = MX ? kMxWoU : 2;
         if (fused_ar(m)) {
-            const EpiPush<1> ep = push_epi(m, w.wo_s, 0);
+            const EpiPush<1> ep = push_epi(m, rs(w.wo_s), 0);
             if (am.max_splits > 8)
                 SLI_HIP((launch_gemv_merge<WT, 1, UW, NT, EpiPush<1>, 16>((const WT*)w.wo, in, ep, am, m->D, m->stream)));
             else
@@ -671,8 +716,10 @@ struct StepRecorder {
     static int gemv_wo_ks(sli_model* m, int l) {
         const LayerW& w = m->layers[l];
         const int ks = m->wo_ks;
-        GemvIn in{m->attn, nullptr, 0.0f, m->hq * m->hd / ks};
-        const EpiKPart e{m->wo_part, w.wo_s, m->D, ks};
+        // (mxfp4: row d * ks + k of the [D * ks][QD / ks] view owns blocks [k QD / (32 ks), (k + 1) QD / (32 ks)) of
+        // row d's scales: the same bytes, as for the data)
+        const GemvIn in = gin(m->attn, nullptr, 0.0f, m->hq * m->hd / ks, w.wo_s);
+        const EpiKPart e{m->wo_part, rs(w.wo_s), m->D, ks};
         AttnMergeIn am{m->part, &m->st->pos, attn_max_splits(m), attn_wg_positions(m->c.kv_dtype, m->hd), m->hd};
         am.ksplit = ks;
         am.kunits = m->D;
@@ -681,7 +728,7 @@ struct StepRecorder {
         // wave's rows at C1: wo 9.42 -> 8.97 us, +0.4 % tok/s; 3 is slower, 9.66), int8 2 (4 measured no faster)
         // (profiles/r4_wo_nb_ab.txt)
         constexpr bool I8 = std::is_same<WT, int8_t>::value;
-        constexpr int UK = I8 ? 1 : 2, NBK = I8 ? 2 : 4;
+        constexpr int UK = MX ? kMxWoU : I8 ? 1 : 2, NBK = MX ? kMxWoNB : I8 ? 2 : 4;
         if (am.max_splits > 8)
             SLI_HIP((launch_gemv_merge_ks<WT, 1, UK, NT, EpiKPart, 16, NBK>((const WT*)w.wo, in, e, am, grid, m->stream)));
         else
@@ -694,10 +741,10 @@ struct StepRecorder {
     }
     static int gemv_gu(sli_model* m, int l) {
         const LayerW& w = m->layers[l];
-        GemvIn in{m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->c.eps, m->D};
-        EpiSwiGLU e{m->act, w.gu_s, m->Il, m->c.act_mode};
+        const GemvIn in = gin(m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->c.eps, m->D, w.gu_s);
+        EpiSwiGLU e{m->act, rs(w.gu_s), m->Il, m->c.act_mode};
         if (m->wo_ks > 1) {  // stage x1 = x + the K-split wo's partials (XStageSum)
-            constexpr int UG = std::is_same<WT, int8_t>::value ? 2 : 4;  // launch_gemv_u's unsplit U
+            constexpr int UG = gemv_uw<WT, 4>();  // launch_gemv_u's unsplit U
             if (m->wo_ks == 2)
                 SLI_HIP((launch_gemv_sum<WT, 2, UG, NT, EpiSwiGLU, 2>((const WT*)w.gu, in, e, m->wo_part, m->Il, m->stream)));
             else
@@ -710,9 +757,9 @@ struct StepRecorder {
     static int gemv_down(sli_model* m, int l) {
         const LayerW& w = m->layers[l];
         const bool tp = m->partial;
-        GemvIn in{m->act, nullptr, 0.0f, m->Il};
+        const GemvIn in = gin(m->act, nullptr, 0.0f, m->Il, w.down_s);
         if (fused_ar(m)) {
-            const EpiPush<1> ep = push_epi(m, w.down_s, 1);
+            const EpiPush<1> ep = push_epi(m, rs(w.down_s), 1);
             if constexpr (std::is_same<WT, int8_t>::value)
                 SLI_HIP((launch_gemv<WT, 1, 4, NT>((const WT*)w.down, in, ep, m->D, m->stream)));
             else
@@ -721,7 +768,7 @@ struct StepRecorder {
         }
         if (m->wo_ks == 2) return gemv_down_sum<2>(m, w, in);
         if (m->wo_ks == 4) return gemv_down_sum<4>(m, w, in);
-        EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, w.down_s, 1.0f, m->D};
+        EpiStore<1> e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(w.down_s), 1.0f, m->D};
         if constexpr (std::is_same<WT, int8_t>::value)  // tools/gemv_lab i8: R1U4 11.66 us vs R1U3 11.74
             SLI_HIP((launch_gemv<WT, 1, 4, NT>((const WT*)w.down, in, e, m->D, m->stream)));
         else
@@ -731,7 +778,7 @@ struct StepRecorder {
     // down + residual x1 = x + the K-split wo's partials (EpiStoreSum: XStageSum's order), written to x
     template <int NP>
     static int gemv_down_sum(sli_model* m, const LayerW& w, const GemvIn& in) {
-        const EpiStoreSum<1, NP> e{m->x, m->x, m->wo_part, w.down_s, m->D};
+        const EpiStoreSum<1, NP> e{m->x, m->x, m->wo_part, rs(w.down_s), m->D};
         if constexpr (std::is_same<WT, int8_t>::value)
             SLI_HIP((launch_gemv<WT, 1, 4, NT>((const WT*)w.down, in, e, m->D, m->stream)));
         else
@@ -745,9 +792,10 @@ struct StepRecorder {
         return cs == 1 ? gemv_balanced_blocks(units) : gemv_blocks(units, cs);  // launch_gemv's grid
     }
     static int gemv_lm(sli_model* m) {
-        GemvIn in{m->x, m->norms + (size_t)(2 * m->L) * m->D, m->c.eps, m->D};
-        EpiLogits<2> e{m->logits, m->keys, m->emb_s ? m->emb_s + m->v_lo : nullptr, m->v_n, m->v_lo, 0ull};
-        const WT* w = (const WT*)m->emb + (size_t)m->v_lo * m->D;
+        const float* es = sptr(m, m->emb_s, (size_t)m->v_lo, m->D);  // this rank's rows of the table's scales
+        const GemvIn in = gin(m->x, m->norms + (size_t)(2 * m->L) * m->D, m->c.eps, m->D, es);
+        EpiLogits<2> e{m->logits, m->keys, rs(es), m->v_n, m->v_lo, 0ull};
+        const WT* w = (const WT*)((const char*)m->emb + (size_t)m->v_lo * wt_row_bytes<WT>((size_t)m->D));
         SLI_HIP((launch_gemv_u<WT, 2, 4, NT>(w, in, e, (m->v_n + 1) / 2, m->stream)));
         return SLI_OK;
     }
@@ -904,10 +952,14 @@ struct StepRecorder {
         const bool batched = m->B > 1;
         if (p == 0) {
             if (batched) {
-                const int eb = std::min(64, (m->D + 255) / 256);
-                hipLaunchKernelGGL(embedding_batch_kernel<WT>, dim3(eb, m->B), dim3(256), 0, s, m->st,
-                                   (const WT*)m->emb, m->emb_s, m->x, m->V, m->D);
-                SLI_HIP(hipGetLastError());
+                if constexpr (MX) {
+                    return fail(SLI_ERR_ARG, "batch > 1 needs fp16 weights");
+                } else {
+                    const int eb = std::min(64, (m->D + 255) / 256);
+                    hipLaunchKernelGGL(embedding_batch_kernel<WT>, dim3(eb, m->B), dim3(256), 0, s, m->st,
+                                       (const WT*)m->emb, m->emb_s, m->x, m->V, m->D);
+                    SLI_HIP(hipGetLastError());
+                }
             } else {
                 SLI_TRY(embedding_launch(0, &m->st->token, m->emb, m->c.w_dtype, m->emb_s, m->x, m->V, m->D, s));
             }
@@ -1034,7 +1086,7 @@ struct StepRecorder {
     template <class Epi, class Cfg>
     static int pg_cfg(sli_model* m, const void* W, int N, int K, const __half* hi, const __half* lo, const Epi& e,
                       int M) {
-        if constexpr (std::is_same<WT, float>::value) {
+        if constexpr (std::is_same<WT, float>::value || MX) {
             return fail(SLI_ERR_ARG, "prefill needs fp16 or int8 weights");
         } else {
             const PgIn<WT> in{(const WT*)W, hi, lo, N, K, M};
@@ -1092,10 +1144,12 @@ struct StepRecorder {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
-        if (p == 0) {
-            hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
-                               m->emb_s, f.x, D);
-            SLI_HIP(hipGetLastError());
+        if constexpr (!MX) {  // (mxfp4 has no GEMM prefill: pf_supported; pg_cfg fails below)
+            if (p == 0) {
+                hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
+                                   m->emb_s, f.x, D);
+                SLI_HIP(hipGetLastError());
+            }
         }
         const int l = p / 2;
         const LayerW& w = m->layers[l];
@@ -1229,6 +1283,8 @@ struct StepRecorder {
         if (wd == SLI_DT_F32 && kd == SLI_DT_F16) return StepRecorder<float, __half>::FN(__VA_ARGS__);  \
         if (wd == SLI_DT_F32 && kd == SLI_DT_F32) return StepRecorder<float, float>::FN(__VA_ARGS__);   \
         if (wd == SLI_DT_I8 && kd == SLI_DT_F16) return StepRecorder<int8_t, __half>::FN(__VA_ARGS__);  \
+        if (wd == SLI_DT_MXFP4 && kd == SLI_DT_F16) return StepRecorder<mxfp4, __half>::FN(__VA_ARGS__); \
+        if (wd == SLI_DT_MXFP4) return StepRecorder<mxfp4, float>::FN(__VA_ARGS__);                     \
         return StepRecorder<int8_t, float>::FN(__VA_ARGS__);                                            \
     })()
 
@@ -1445,7 +1501,7 @@ static int wo_ksplit(const sli_model* m) {
     if (ks == 1 || m->B != 1 || m->partial || m->group || m->D > 4 * sli::kGemvThreads || m->hq % ks) return 1;
     if (!m->wo_merge) return 1;  // the split pays off in the merge staging it shrinks
     const int cols = m->hq * m->hd / ks;
-    const int epv = 16 / (int)m->wbytes;  // weight elements per 16-byte vector
+    const int epv = (int)(16.0 / m->wbytes);  // weight elements per 16-byte vector
     if (cols % epv || cols % 4 || sli::gemv_ksplit_grid(m->D, ks) == 0) return 1;
     return ks;
 }
@@ -1499,19 +1555,27 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     SLI_CHECK(c.n_kv_heads % c.tp_size == 0 && c.ffn % c.tp_size == 0, SLI_ERR_SHAPE,
               "kv heads and ffn must divide by tp_size");
     SLI_CHECK((c.ffn / c.tp_size) % 2 == 0, SLI_ERR_SHAPE, "local ffn must be even");
-    SLI_CHECK(c.w_dtype >= SLI_DT_F32 && c.w_dtype <= SLI_DT_I8, SLI_ERR_ARG, "bad w_dtype");
+    SLI_CHECK(c.w_dtype >= SLI_DT_F32 && c.w_dtype <= SLI_DT_MXFP4, SLI_ERR_ARG, "bad w_dtype");
     SLI_CHECK(c.kv_dtype == SLI_DT_F32 || c.kv_dtype == SLI_DT_F16, SLI_ERR_ARG, "bad kv_dtype");
     SLI_CHECK(c.tp_size == 1 || comm_id || group || std::getenv("SLI_DEBUG_NOCOMM"), SLI_ERR_ARG,
               "tensor parallel needs a comm id");
-    const size_t wb = c.w_dtype == SLI_DT_F32 ? 4 : c.w_dtype == SLI_DT_F16 ? 2 : 1;
-    SLI_CHECK(((size_t)c.dim * wb) % 16 == 0 && ((size_t)(c.ffn / c.tp_size) * wb) % 16 == 0 &&
-                  ((size_t)(c.dim / c.tp_size) * wb) % 16 == 0,
+    const bool mx = c.w_dtype == SLI_DT_MXFP4;
+    // MXFP4 quantises blocks of 32 consecutive columns of the unsharded row: every local column window (the whole
+    // row of q/k/v, gate/up and the table; this rank's columns of wo and down; the K-split wo's column blocks, which
+    // wo_ksplit only takes on vector boundaries) must start and end on a multiple of 32
+    if (mx)
+        SLI_CHECK(c.dim % kMxBlock == 0 && (c.ffn / c.tp_size) % kMxBlock == 0 &&
+                      ((c.n_heads / c.tp_size) * c.head_dim) % kMxBlock == 0,
+                  SLI_ERR_SHAPE, "mxfp4: dim, the local ffn width and the local q width must be multiples of 32");
+    const double wb = c.w_dtype == SLI_DT_F32 ? 4 : c.w_dtype == SLI_DT_F16 ? 2 : c.w_dtype == SLI_DT_I8 ? 1 : 0.5;
+    auto rowb = [&](int cols) { return (size_t)((double)cols * wb); };
+    SLI_CHECK(rowb(c.dim) % 16 == 0 && rowb(c.ffn / c.tp_size) % 16 == 0 && rowb(c.dim / c.tp_size) % 16 == 0,
               SLI_ERR_SHAPE, "row bytes must be multiples of 16");
     SLI_CHECK(c.dim <= kGemvMaxCols && c.ffn / c.tp_size <= kGemvMaxCols, SLI_ERR_SHAPE, "row too long for LDS staging");
     const int B = c.batch > 0 ? c.batch : 1;
     SLI_CHECK(B <= kBgMaxBatch, SLI_ERR_SHAPE, "batch must be at most 8");
     if (B > 1) {
-        SLI_CHECK(c.w_dtype == SLI_DT_F16, SLI_ERR_ARG, "batch > 1 needs fp16 weights (MFMA projections)");
+        SLI_CHECK(c.w_dtype == SLI_DT_F16, SLI_ERR_ARG, "batch > 1 needs fp16 weights (MFMA projections)");  // mxfp4 too
         SLI_CHECK(c.dim % 32 == 0 && (c.ffn / c.tp_size) % 32 == 0 && ((c.n_heads / c.tp_size) * c.head_dim) % 32 == 0,
                   SLI_ERR_SHAPE, "batch > 1: projection inputs must be multiples of 32");
         SLI_CHECK(c.dim <= kBgMaxStageK, SLI_ERR_SHAPE, "batch > 1: dim must be at most 4096 (RMS staging)");
@@ -1554,15 +1618,24 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     auto A = [&](void** p, size_t bytes) {
         if (rc == SLI_OK) rc = model_alloc(m, p, bytes);
     };
-    A(&m->emb, (size_t)m->V * D * wb);
+    auto WB = [&](size_t rows, size_t cols) { return (size_t)((double)(rows * cols) * wb); };  // a matrix's bytes
+    auto SB = [&](size_t rows, size_t cols) { return rows * (cols / kMxBlock); };             // its mxfp4 scales
+    A(&m->emb, WB(m->V, D));
     if (i8) A((void**)&m->emb_s, sizeof(float) * m->V);
+    if (mx) A((void**)&m->emb_s, SB(m->V, D));
     A((void**)&m->norms, sizeof(float) * (size_t)(2 * m->L + 1) * D);
     m->layers.resize(m->L);
     for (auto& w : m->layers) {
-        A(&w.qkv, (size_t)qkv_rows * D * wb);
-        A(&w.wo, (size_t)D * m->hq * hd * wb);
-        A(&w.gu, (size_t)2 * m->Il * D * wb);
-        A(&w.down, (size_t)D * m->Il * wb);
+        A(&w.qkv, WB(qkv_rows, D));
+        A(&w.wo, WB(D, (size_t)m->hq * hd));
+        A(&w.gu, WB((size_t)2 * m->Il, D));
+        A(&w.down, WB(D, m->Il));
+        if (mx) {
+            A((void**)&w.qkv_s, SB(qkv_rows, D));
+            A((void**)&w.wo_s, SB(D, (size_t)m->hq * hd));
+            A((void**)&w.gu_s, SB((size_t)2 * m->Il, D));
+            A((void**)&w.down_s, SB(D, m->Il));
+        }
         if (i8) {
             A((void**)&w.qkv_s, sizeof(float) * qkv_rows);
             A((void**)&w.wo_s, sizeof(float) * D);
@@ -1813,7 +1886,7 @@ static int get_state(sli_model* m, int seq, int32_t* pos, int32_t* token, int32_
 // whose exchange it does have; an in-process group sums the chunk rows itself (record_group_prefill).
 static bool pf_supported(const sli_model* m) {
     if (m->partial && !m->collectives && !m->group) return false;
-    return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
+    return m->c.w_dtype != SLI_DT_F32 && m->c.w_dtype != SLI_DT_MXFP4 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
            m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
 }
 
@@ -2107,11 +2180,22 @@ int sli_model_get_weight(sli_model* m, int32_t kind, int32_t index, float* host,
             default: return fail(SLI_ERR_ARG, "unknown tensor kind");
         }
         src = wptr(const_cast<void*>(src), m->wbytes, (size_t)w.dst_row_off * w.n_cols);
-        if (scale) scale += w.dst_row_off;
+        scale = sptr(m, const_cast<float*>(scale), (size_t)w.dst_row_off, w.n_cols);
     }
     SLI_CHECK(n == rows * cols, SLI_ERR_SHAPE, "host buffer size must be the local shard's rows*cols");
-    std::vector<unsigned char> raw((size_t)(rows * cols) * m->wbytes);
+    std::vector<unsigned char> raw((size_t)((double)(rows * cols) * m->wbytes));
     SLI_HIP(hipMemcpy(raw.data(), src, raw.size(), hipMemcpyDeviceToHost));
+    if (m->c.w_dtype == SLI_DT_MXFP4) {  // table decode on the host (mxfp4.h layout)
+        std::vector<unsigned char> sb((size_t)rows * (cols / kMxBlock));
+        SLI_HIP(hipMemcpy(sb.data(), scale, sb.size(), hipMemcpyDeviceToHost));
+        static const float grid[8] = {0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f};
+        for (int64_t i = 0; i < rows * cols; ++i) {
+            const unsigned code = (i & 1) ? (raw[i >> 1] >> 4) : (raw[i >> 1] & 15u);
+            const float v = std::ldexp(grid[code & 7u], (int)sb[i / kMxBlock] - 127);
+            host[i] = (code & 8u) ? -v : v;
+        }
+        return SLI_OK;
+    }
     std::vector<float> sc;
     if (scale) {
         sc.resize(rows);
@@ -2144,7 +2228,8 @@ int sli_model_step_bytes(sli_model* m, double* weight_bytes, double* kv_bytes) {
     SLI_CHECK(m, SLI_ERR_ARG, "null model");
     std::vector<DevState> h;
     SLI_TRY(download_states(m, h));
-    const double wb = (double)m->wbytes, D = m->D, hd = m->hd;
+    // (mxfp4: cols / 2 data bytes + cols / 32 scale bytes per row)
+    const double wb = m->wbytes + (m->c.w_dtype == SLI_DT_MXFP4 ? 1.0 / kMxBlock : 0.0), D = m->D, hd = m->hd;
     const double per_layer = ((m->hq + 2.0 * m->hkv) * hd * D + D * m->hq * hd + 3.0 * m->Il * D) * wb;
     double w = m->L * per_layer + (double)m->v_n * D * wb;
     if (m->c.w_dtype == SLI_DT_I8) w += 4.0 * (m->L * ((m->hq + 2.0 * m->hkv) * hd + 2.0 * D + 2.0 * m->Il) + m->v_n);
@@ -2312,7 +2397,8 @@ int sli_model_time_families(sli_model* m, int32_t iters, double* us, double* byt
     SLI_TRY(download_states(m, h));
     double ctx = 0.0;
     for (const DevState& d : h) ctx += d.pos + 1.0;
-    const double wb = (double)m->wbytes, D = m->D, hd = m->hd, i8 = m->c.w_dtype == SLI_DT_I8 ? 4.0 : 0.0;
+    const double wb = m->wbytes + (m->c.w_dtype == SLI_DT_MXFP4 ? 1.0 / kMxBlock : 0.0), D = m->D, hd = m->hd,
+                 i8 = m->c.w_dtype == SLI_DT_I8 ? 4.0 : 0.0;
     const double qkv_rows = (m->hq + 2.0 * m->hkv) * hd;
     bytes[SLI_FAM_QKV] = qkv_rows * (D * wb + i8);
     bytes[SLI_FAM_ATTN] = 2.0 * ctx * m->hkv * hd * (double)m->kvbytes;
@@ -2381,7 +2467,8 @@ int sli_model_time_stream(sli_model* m, int32_t iters, double* us) {
     SLI_HIP(hipMalloc(&g.sink, 4096));
     SLI_HIP(hipEventCreate(&g.e0));
     SLI_HIP(hipEventCreate(&g.e1));
-    const long long wb = m->wbytes, D = m->D, hd = m->hd;
+    const long long D = m->D, hd = m->hd;
+    const double wb = m->wbytes;  // (mxfp4: the data bytes; the scales, 1/16 of them, are not part of this floor)
     const long long kvl = (long long)m->B * m->hkv * m->T * hd * m->kvbytes;  // one layer's K (or V)
     const int grid = device_cus();
     auto launch = [&](int f, int l) {
@@ -2389,16 +2476,19 @@ int sli_model_time_stream(sli_model* m, int32_t iters, double* us) {
         long long na = 0, nb = 0, nc = 0;
         const LayerW& w = m->layers[f == SLI_FAM_LM ? 0 : l];
         switch (f) {
-            case SLI_FAM_QKV: a = (const char*)w.qkv; na = (m->hq + 2LL * m->hkv) * hd * D * wb; break;
+            case SLI_FAM_QKV: a = (const char*)w.qkv; na = (long long)((m->hq + 2LL * m->hkv) * hd * D * wb); break;
             case SLI_FAM_ATTN:
                 a = (const char*)m->kc + l * kvl;
                 b = (const char*)m->vc + l * kvl;
                 na = nb = kvl;
                 break;
-            case SLI_FAM_WO: a = (const char*)w.wo; na = D * m->hq * hd * wb; break;
-            case SLI_FAM_GU: a = (const char*)w.gu; na = 2LL * m->Il * D * wb; break;
-            case SLI_FAM_DOWN: a = (const char*)w.down; na = D * m->Il * wb; break;
-            default: a = (const char*)m->emb + (long long)m->v_lo * D * wb; na = (long long)m->v_n * D * wb; break;
+            case SLI_FAM_WO: a = (const char*)w.wo; na = (long long)(D * m->hq * hd * wb); break;
+            case SLI_FAM_GU: a = (const char*)w.gu; na = (long long)(2LL * m->Il * D * wb); break;
+            case SLI_FAM_DOWN: a = (const char*)w.down; na = (long long)(D * m->Il * wb); break;
+            default:
+                a = (const char*)m->emb + (long long)((long long)m->v_lo * D * wb);
+                na = (long long)((long long)m->v_n * D * wb);
+                break;
         }
         hipLaunchKernelGGL(stream_read_kernel, dim3(grid), dim3(1024), 0, m->stream, a, na, b, nb, c, nc, g.sink);
     };

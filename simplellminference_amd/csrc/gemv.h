@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mxfp4.h"
 
 namespace sli {
 
@@ -28,6 +29,7 @@ struct GemvIn {
     int cw = 16;     // waves per workgroup that stream (gemv_wave_count); the others only shadow loads
     int blk0 = 0;    // workgroups in front of the GEMV's own in the grid (qkv_attn.h: the attention's); OFFS only
     int blk1 = 0;    // OFFS: the end of the GEMV's workgroups (0: the grid's end)
+    const uint8_t* wscale = nullptr;  // mxfp4 weights: block scales [rows][cols / 32] of the matrix W points at
 };
 
 constexpr int kGemvThreads = 1024;  // one persistent 16-wave workgroup per CU: x staged once per CU
@@ -43,7 +45,7 @@ constexpr int kGemvStageV4 = 4;  // float4 of x per thread: 1024 threads x 4 x 4
 // whole first weight chunk (measured: x staged 6-11 us into a 10-30 us launch), and no wave could
 // start consuming weights until every wave's first chunk had landed.
 // LDS layout of the staged x: float4 f of the input lives at slot xswz<G>(f), G = float4s per 16-byte
-// weight vector (fp32 1, fp16 2, int8 4). Lane l of a GEMV wave reads the G float4s of weight vector
+// weight vector (fp32 1, fp16 2, int8 4, mxfp4 8). Lane l of a GEMV wave reads the G float4s of weight vector
 // v = base + l; unswizzled, the 16 lanes of a ds_read_b128 group (MI355X_MICROARCH.md §LDS:
 // {0-3,12-15,20-27}, ...) hit only 16/G distinct 16-byte slots of the 256-byte bank row (fp16 2-way,
 // int8 4-way conflicts). XOR-ing the float4 index inside its vector with bits of v>>(4/G) spreads
@@ -288,9 +290,10 @@ __device__ __forceinline__ void gemv_stage_x(float* smem, const GemvIn& in) {
 
 // acc[r] += sum over the U vectors (64 lanes apart, starting at vector index v) of W[r] . x.
 // MASK: vectors at index >= nvec contribute nothing (their loads were clamped in range by the caller).
+// mxfp4: sc[j][r] is the block scale byte of vector w[j][r] (one block per vector), applied in the convert.
 template <typename WT, int R, int U, bool MASK = false>
-__device__ __forceinline__ void gemv_chunk(const u32x4 (&w)[U][R], const float* xs, int v, float* acc,
-                                           int nvec = 0) {
+__device__ __forceinline__ void gemv_chunk(const u32x4 (&w)[U][R], const unsigned (&sc)[U][R], const float* xs, int v,
+                                           float* acc, int nvec = 0) {
     constexpr int EPV = Vec16<WT>::N;
 #pragma unroll
     for (int j = 0; j < U; ++j) {
@@ -311,7 +314,10 @@ __device__ __forceinline__ void gemv_chunk(const u32x4 (&w)[U][R], const float* 
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             float wf[EPV];
-            Vec16<WT>::unpack(w[j][r], wf);
+            if constexpr (is_mx<WT>::value)
+                Vec16<WT>::unpack(w[j][r], sc[j][r], wf);
+            else
+                Vec16<WT>::unpack(w[j][r], wf);
 #pragma unroll
             for (int e = 0; e < EPV; ++e) acc[r] = fmaf(wf[e], xv[e], acc[r]);
         }
@@ -354,7 +360,7 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = kGemvThreads >> 6;  // compile-time: blockDim.x is a dispatch-packet load
     const int nvec = in.cols / EPV;
-    const size_t row_bytes = (size_t)in.cols * sizeof(WT);
+    const size_t row_bytes = wt_row_bytes<WT>((size_t)in.cols);
     const int nunits = epi.units();
     // OFFS: the GEMV is workgroups [in.blk0, gridDim.x) of a launch it shares (qkv_attn.h)
     const int bx = OFFS ? (int)blockIdx.x - in.blk0 : (int)blockIdx.x;
@@ -406,7 +412,8 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
 #define SLI_GEMV_DUP_LOADS 0
 #endif
     const Pos dummy = SLI_GEMV_DUP_LOADS ? last : Pos{0, 0, 0, 0};
-    auto load_step = [&](const Pos& q, u32x4 (&w)[U][R]) {
+    // mxfp4: the block scale (one byte per vector) is loaded with its vector, unconditional and clamped like it
+    auto load_step = [&](const Pos& q, u32x4 (&w)[U][R], unsigned (&sc)[U][R]) {
         const Pos& a = q.it > it_last ? dummy : q;
         int rows[R];
         epi.rows(min(a.u, nunits - 1), rows);
@@ -415,8 +422,10 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
         for (int j = 0; j < U; ++j) {
             const int vj = min(v + j * 64, nvec - 1);  // clamp, never branch around a load
 #pragma unroll
-            for (int r = 0; r < R; ++r)
+            for (int r = 0; r < R; ++r) {
                 w[j][r] = load16<NT>(reinterpret_cast<const char*>(W) + (size_t)rows[r] * row_bytes + (size_t)vj * 16);
+                if constexpr (is_mx<WT>::value) sc[j][r] = in.wscale[(size_t)rows[r] * (size_t)nvec + (size_t)vj];
+            }
         }
     };
     auto next = [&](Pos& q) {
@@ -432,13 +441,13 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     float acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.0f;
-    auto consume_step = [&](const Pos& q, const u32x4(&w)[U][R]) {
+    auto consume_step = [&](const Pos& q, const u32x4(&w)[U][R], const unsigned(&sc)[U][R]) {
         const int c = q.p * cpp + q.cc;
         const int v = c * CV + lane;
         if ((c + 1) * CV <= nvec)
-            gemv_chunk<WT, R, U>(w, xs, v, acc);
+            gemv_chunk<WT, R, U>(w, sc, xs, v, acc);
         else
-            gemv_chunk<WT, R, U, true>(w, xs, v, acc, nvec);
+            gemv_chunk<WT, R, U, true>(w, sc, xs, v, acc, nvec);
         if (q.cc == cpp - 1) {  // item complete: its R partial row sums go to LDS
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -455,12 +464,13 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     // no clamped load is ever issued after its data was consumed (a fresh HBM round trip at the end of
     // every wave).
     u32x4 wbuf[NB][U][R];
+    unsigned sbuf[NB][U][R];  // mxfp4 block scales of wbuf (unused, and so not kept, for the other types)
     const Pos first{ib, ub + ib / CS, ib - (ib / CS) * CS, 0};
     Pos lq = first;  // next step to load
     Pos cq = first;  // next step to consume
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        load_step(lq, wbuf[b]);
+        load_step(lq, wbuf[b], sbuf[b]);
         next(lq);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -473,16 +483,16 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     for (; k + NB < nsteps; k += NB) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-            consume_step(cq, wbuf[b]);
+            consume_step(cq, wbuf[b], sbuf[b]);
             next(cq);
-            load_step(lq, wbuf[b]);  // step k + b + NB, or a duplicate of the wave's last step
+            load_step(lq, wbuf[b], sbuf[b]);  // step k + b + NB, or a duplicate of the wave's last step
             next(lq);
         }
     }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         if (k + b < nsteps) {
-            consume_step(cq, wbuf[b]);
+            consume_step(cq, wbuf[b], sbuf[b]);
             next(cq);
         }
     }
@@ -977,12 +987,20 @@ hipError_t launch_gemv(const WT* W, const GemvIn& in_, const Epi& epi, int units
 // unit's rows over CS column parts (gemv.h gemv_block): CS = the power of two that gives every wave of the
 // chip an item, at the widest U whose chunks still cover CS parts per row (U, then 2, then 1). Full-size
 // matrices (every TP-1 projection) keep CS = 1.
+// mxfp4 (32 columns per vector) takes a quarter of U by the same rule (tools/gemv_lab mxfp4 for the tuned values).
 struct GemvSplit {
     int cs, u;  // column parts per unit, vectors per lane per chunk
 };
+constexpr int kMxOpR = 1, kMxOpU = 1;  // sli_matmul_mxfp4: rows per unit, vectors per lane per chunk (gemv_lab mxfp4)
+constexpr int kMxWoU = 1, kMxWoNB = 2;  // the merge-staged wo GEMV (engine.hip gemv_wo / gemv_wo_ks) at mxfp4
+template <typename WT, int U>
+constexpr int gemv_uw() {
+    if (is_mx<WT>::value) return U >= 4 ? U / 4 : 1;
+    return std::is_same<WT, int8_t>::value && U >= 2 ? U / 2 : U;
+}
 template <typename WT, int U>
 inline GemvSplit gemv_split(int units, int cols) {
-    constexpr int UW = std::is_same<WT, int8_t>::value && U >= 2 ? U / 2 : U;
+    constexpr int UW = gemv_uw<WT, U>();
     const int waves = gemv_max_blocks() * (kGemvThreads / 64);
     int need = 1;
     while (need < 8 && units * need < waves) need *= 2;
@@ -995,7 +1013,7 @@ inline GemvSplit gemv_split(int units, int cols) {
 }
 template <typename WT, int R, int U, bool NT, class Epi>
 hipError_t launch_gemv_u(const WT* W, const GemvIn& in_, const Epi& epi, int units, hipStream_t s) {
-    constexpr int UW = std::is_same<WT, int8_t>::value && U >= 2 ? U / 2 : U;
+    constexpr int UW = gemv_uw<WT, U>();
     GemvIn in = in_;
     const GemvSplit sp = gemv_split<WT, U>(units, in.cols);
     in.csplit = sp.cs;

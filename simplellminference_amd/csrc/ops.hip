@@ -120,6 +120,15 @@ __global__ void embedding_kernel(int token_host, const int32_t* token_dev, const
         out[i] = ok ? to_f32(table[(size_t)token * dim + i]) * s : __int_as_float(0x7FC00000);  // poison: NaN
 }
 
+// an MXFP4 table (mxfp4.h): the row dequantised by table decode
+__global__ void embedding_mx_kernel(int token_host, const int32_t* token_dev, const uint8_t* __restrict__ data,
+                                    const uint8_t* __restrict__ scales, float* __restrict__ out, int vocab, int dim) {
+    const int token = token_dev ? *token_dev : token_host;
+    const bool ok = token >= 0 && token < vocab;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dim; i += gridDim.x * blockDim.x)
+        out[i] = ok ? mx_element(data, scales, (size_t)token, dim, i) : __int_as_float(0x7FC00000);  // poison: NaN
+}
+
 // ---------------------------------------------------------------- argmax (argmax.cpp:7-17)
 __global__ void __launch_bounds__(1024) argmax_kernel(const float* __restrict__ x, int n, int32_t* out) {
     __shared__ unsigned long long red[16];
@@ -135,6 +144,27 @@ __global__ void __launch_bounds__(1024) argmax_kernel(const float* __restrict__ 
         unsigned long long b = 0;
         for (int i = 0; i < (int)(blockDim.x >> 6); ++i) b = red[i] > b ? red[i] : b;
         *out = (int32_t)argmax_key_index(b);
+    }
+}
+
+// ---------------------------------------------------------------- MXFP4 (mxfp4.h): quantise / dequantise
+// one thread per block of 32 columns
+__global__ void __launch_bounds__(256) mx_quant_kernel(const float* __restrict__ src, uint8_t* __restrict__ data,
+                                                       uint8_t* __restrict__ scales, size_t nblk) {
+    for (size_t b = blockIdx.x * (size_t)blockDim.x + threadIdx.x; b < nblk; b += (size_t)gridDim.x * blockDim.x) {
+        const float* p = src + b * kMxBlock;
+        mx_quant_block([&](int i) { return p[i]; }, data, scales, b);
+    }
+}
+// one thread per data byte (two elements)
+__global__ void __launch_bounds__(256) mx_dequant_kernel(const uint8_t* __restrict__ data,
+                                                         const uint8_t* __restrict__ scales, float* __restrict__ dst,
+                                                         size_t nbytes) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nbytes; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned b = data[i];
+        const int e = (int)scales[i / (kMxBlock / 2)] - 127;
+        dst[2 * i] = mx_decode(b & 15u, e);
+        dst[2 * i + 1] = mx_decode(b >> 4, e);
     }
 }
 
@@ -304,6 +334,9 @@ int embedding_launch(int token, const int32_t* token_dev, const void* table, int
     else if (dtype == SLI_DT_I8)
         hipLaunchKernelGGL(embedding_kernel<int8_t>, dim3(blocks), dim3(256), 0, s, token, token_dev,
                            (const int8_t*)table, row_scale, out, vocab, dim);
+    else if (dtype == SLI_DT_MXFP4)  // (the engine only: row_scale carries the table's block scales)
+        hipLaunchKernelGGL(embedding_mx_kernel, dim3(blocks), dim3(256), 0, s, token, token_dev, (const uint8_t*)table,
+                           reinterpret_cast<const uint8_t*>(row_scale), out, vocab, dim);
     else
         return fail(SLI_ERR_ARG, "embedding: bad dtype");
     SLI_HIP(hipGetLastError());
@@ -329,6 +362,56 @@ int sli_matmul(const float* x, const void* w, int w_dtype, const float* w_row_sc
             return matmul_dispatch<int8_t>(x, (const int8_t*)w, w_row_scale, y, rows, cols, scale, s);
         default: return fail(SLI_ERR_ARG, "sli_matmul: bad dtype");
     }
+}
+
+int sli_mxfp4_bytes(int32_t rows, int32_t cols, size_t* data_bytes, size_t* scale_bytes) {
+    SLI_CHECK(rows > 0 && cols > 0, SLI_ERR_SHAPE, "sli_mxfp4_bytes: Tensor with Wrong Dim!");
+    SLI_CHECK(cols % kMxBlock == 0, SLI_ERR_SHAPE, "sli_mxfp4_bytes: cols must be a multiple of 32");
+    if (data_bytes) *data_bytes = (size_t)rows * (size_t)(cols / 2);
+    if (scale_bytes) *scale_bytes = (size_t)rows * (size_t)(cols / kMxBlock);
+    return SLI_OK;
+}
+
+int sli_quant_mxfp4(const float* src, void* data, void* scales, int32_t rows, int32_t cols, sli_stream_t stream) {
+    SLI_CHECK(src && data && scales, SLI_ERR_ARG, "sli_quant_mxfp4: null pointer");
+    SLI_CHECK(rows > 0 && cols > 0 && cols % kMxBlock == 0, SLI_ERR_SHAPE,
+              "sli_quant_mxfp4: cols must be a multiple of 32");
+    SLI_CHECK((uintptr_t)data % 16 == 0, SLI_ERR_ARG, "sli_quant_mxfp4: data needs 16-byte alignment");
+    const size_t nblk = (size_t)rows * (size_t)(cols / kMxBlock);
+    const int blocks = (int)std::min<size_t>(4096, (nblk + 255) / 256);
+    hipLaunchKernelGGL(mx_quant_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), src, (uint8_t*)data,
+                       (uint8_t*)scales, nblk);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+int sli_dequant_mxfp4(const void* data, const void* scales, float* dst, int32_t rows, int32_t cols,
+                      sli_stream_t stream) {
+    SLI_CHECK(data && scales && dst, SLI_ERR_ARG, "sli_dequant_mxfp4: null pointer");
+    SLI_CHECK(rows > 0 && cols > 0 && cols % kMxBlock == 0, SLI_ERR_SHAPE,
+              "sli_dequant_mxfp4: cols must be a multiple of 32");
+    const size_t nbytes = (size_t)rows * (size_t)(cols / 2);
+    const int blocks = (int)std::min<size_t>(4096, (nbytes + 255) / 256);
+    hipLaunchKernelGGL(mx_dequant_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (const uint8_t*)data,
+                       (const uint8_t*)scales, dst, nbytes);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+int sli_matmul_mxfp4(const float* x, const void* data, const void* scales, float* y, int32_t rows, int32_t cols,
+                     float scale, sli_stream_t stream) {
+    SLI_CHECK(x && data && scales && y, SLI_ERR_ARG, "sli_matmul_mxfp4: null pointer");
+    SLI_CHECK(rows > 0 && cols > 0, SLI_ERR_SHAPE, "sli_matmul_mxfp4: Tensor with Wrong Dim!");
+    SLI_CHECK(cols % kMxBlock == 0, SLI_ERR_SHAPE, "sli_matmul_mxfp4: cols must be a multiple of 32");
+    SLI_CHECK(cols <= kGemvMaxCols, SLI_ERR_SHAPE, "sli_matmul_mxfp4: too many columns for the staged input");
+    SLI_CHECK((uintptr_t)data % 16 == 0 && (uintptr_t)x % 16 == 0, SLI_ERR_ARG,
+              "sli_matmul_mxfp4: x and data need 16-byte alignment");
+    EpiStore<kMxOpR> epi{y, nullptr, nullptr, scale, rows};
+    GemvIn in{x, nullptr, 0.0f, cols};
+    in.wscale = (const uint8_t*)scales;
+    SLI_HIP((launch_gemv_u<mxfp4, kMxOpR, 4 * kMxOpU, true>((const mxfp4*)data, in, epi, (rows + kMxOpR - 1) / kMxOpR,
+                                                            as_stream(stream))));  // column split below 4096 units
+    return SLI_OK;
 }
 
 size_t sli_matmul_batch_workspace_bytes(int32_t rows, int32_t cols, int32_t batch) {
@@ -451,6 +534,7 @@ int sli_embedding(int32_t token, const int32_t* token_dev, const void* table, in
     SLI_CHECK(vocab > 0 && dim > 0, SLI_ERR_SHAPE, "sli_embedding: shape");
     SLI_CHECK(token_dev || (token >= 0 && token < vocab), SLI_ERR_RANGE, "Token index is greater than vocab size.");
     SLI_CHECK(dtype != SLI_DT_I8 || row_scale, SLI_ERR_ARG, "sli_embedding: int8 table needs row scales");
+    SLI_CHECK(dtype != SLI_DT_MXFP4, SLI_ERR_ARG, "sli_embedding: bad dtype");
     return embedding_launch(token, token_dev, table, dtype, row_scale, out, vocab, dim, as_stream(stream));
 }
 

@@ -16,9 +16,10 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib
-from ._lib import DT_F16, DT_F32, DT_I8, ModelConfig, call
+from ._lib import DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
 
-_DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8}
+_DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8,
+           "mxfp4": DT_MXFP4, "fp4": DT_MXFP4}
 
 
 @dataclass(frozen=True)

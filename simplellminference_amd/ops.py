@@ -41,6 +41,48 @@ def matmul(x, w, y=None, scale: float = 1.0, row_scale=None):
     return y
 
 
+def mxfp4_bytes(rows: int, cols: int) -> tuple[int, int]:
+    """(data bytes, scale bytes) of a [rows, cols] MXFP4 tensor (sli.h); cols % 32 != 0 raises SliError."""
+    d, s = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    call("sli_mxfp4_bytes", rows, cols, ctypes.byref(d), ctypes.byref(s))
+    return d.value, s.value
+
+
+def quant_mxfp4(w, data=None, scales=None):
+    """fp32 [rows, cols] -> (data uint8 [rows, cols/2], scales uint8 [rows, cols/32]), the rule of sli.h."""
+    rows, cols = w.shape
+    mxfp4_bytes(rows, cols)
+    data = torch.empty(rows, cols // 2, device=w.device, dtype=torch.uint8) if data is None else data
+    scales = torch.empty(rows, cols // 32, device=w.device, dtype=torch.uint8) if scales is None else scales
+    _dev(w, data, scales)
+    if w.dtype != torch.float32:
+        raise ValueError("quant_mxfp4 takes fp32")
+    call("sli_quant_mxfp4", _p(w), _p(data), _p(scales), rows, cols, _s())
+    return data, scales
+
+
+def dequant_mxfp4(data, scales, out=None):
+    """(data, scales) -> fp32 [rows, cols], exact."""
+    rows, cols = data.shape[0], data.shape[1] * 2
+    if scales.shape != (rows, cols // 32):
+        raise ValueError("Tensor with Wrong Dim!")
+    out = torch.empty(rows, cols, device=data.device, dtype=torch.float32) if out is None else out
+    _dev(data, scales, out)
+    call("sli_dequant_mxfp4", _p(data), _p(scales), _p(out), rows, cols, _s())
+    return out
+
+
+def matmul_mxfp4(x, data, scales, y=None, scale: float = 1.0):
+    """y = scale * W @ x for MXFP4 weights (data uint8 [rows, cols/2], scales uint8 [rows, cols/32]), x fp32."""
+    rows, cols = data.shape[0], data.shape[1] * 2
+    if x.numel() != cols or scales.shape != (rows, cols // 32):
+        raise ValueError("Tensor with Wrong Dim!")
+    y = torch.empty(rows, device=x.device, dtype=torch.float32) if y is None else y
+    _dev(x, data, scales, y)
+    call("sli_matmul_mxfp4", _p(x), _p(data), _p(scales), _p(y), rows, cols, scale, _s())
+    return y
+
+
 def matmul_batch(x, w, y=None):
     """Batched projection for B <= 8 sequences on MFMA (bgemm.h): y[b] = W @ x[b]; x [B, cols] fp32, W
     [rows, cols] fp16, y [B, rows] fp32. No reference counterpart (the reference is batch 1)."""

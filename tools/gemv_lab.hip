@@ -563,6 +563,55 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (mode == "mxfp4") {
+        // MXFP4 weights (the fp16 buffers reinterpreted: the first quarter of their bytes as data, the next
+        // sixty-fourth as block scales, set to 127), every (R, U, NB) on each shape, and the streaming-read ceiling
+        // of the same bytes (data + scales: 0.53125 B per weight)
+        using MxRun = std::function<void(const mxfp4*, const GemvIn&, float*, int, hipStream_t)>;
+        auto mk = [](auto r_tag, auto u_tag, auto nb_tag) -> MxRun {
+            constexpr int R = decltype(r_tag)::value, U = decltype(u_tag)::value, NB = decltype(nb_tag)::value;
+            return [](const mxfp4* W, const GemvIn& in, float* y, int rows, hipStream_t s) {
+                EpiStore<R> e{y, nullptr, nullptr, 1.0f, rows};
+                CK((launch_gemv<mxfp4, R, U, true, EpiStore<R>, NB>(W, in, e, (rows + R - 1) / R, s)));
+            };
+        };
+        using I1 = std::integral_constant<int, 1>;
+        using I2 = std::integral_constant<int, 2>;
+        using I3 = std::integral_constant<int, 3>;
+        using I4 = std::integral_constant<int, 4>;
+        std::vector<std::pair<const char*, MxRun>> cf = {
+            {"R1U1", mk(I1{}, I1{}, I2{})},    {"R1U1NB3", mk(I1{}, I1{}, I3{})}, {"R1U1NB4", mk(I1{}, I1{}, I4{})},
+            {"R1U2", mk(I1{}, I2{}, I2{})},    {"R1U2NB3", mk(I1{}, I2{}, I3{})}, {"R1U4", mk(I1{}, I4{}, I2{})},
+            {"R2U1", mk(I2{}, I1{}, I2{})},    {"R2U1NB3", mk(I2{}, I1{}, I3{})}, {"R2U1NB4", mk(I2{}, I1{}, I4{})},
+            {"R2U2", mk(I2{}, I2{}, I2{})},    {"R2U2NB3", mk(I2{}, I2{}, I3{})}, {"R4U1", mk(I4{}, I1{}, I2{})},
+            {"R4U1NB3", mk(I4{}, I1{}, I3{})}, {"R4U2", mk(I4{}, I2{}, I2{})}};
+        for (int si = 0; si < 5; ++si) {
+            const Shape& sh = kShapes[si];
+            const size_t n = (size_t)sh.rows * sh.cols;
+            const int layers = (int)w[si].size();
+            for (int l = 0; l < layers; ++l) CK(hipMemsetAsync((char*)w[si][l] + n / 2, 127, n / 32, s));
+            const double bytes = (double)n * 0.53125;
+            for (auto& c : cf) {
+                const float ms = time_graph(s, [&] {
+                    for (int l = 0; l < layers; ++l) {
+                        GemvIn in = in_for0(si);
+                        in.wscale = (const uint8_t*)w[si][l] + n / 2;
+                        c.second((const mxfp4*)w[si][l], in, y, sh.rows, s);
+                    }
+                });
+                const double us = 1000.0 * ms / layers;
+                printf("mxfp4 %-5s %-8s %8.2f us  %7.1f GB/s\n", sh.name, c.first, us, bytes / (us * 1e-6) / 1e9);
+            }
+            const float ms = time_graph(s, [&] {
+                for (int l = 0; l < layers; ++l)
+                    hipLaunchKernelGGL(stream_kernel<8>, dim3(256), dim3(1024), 0, s, (const char*)w[si][l],
+                                       (long long)bytes, y2, nullptr);
+            });
+            const double us = 1000.0 * ms / layers;
+            printf("mxfp4 %-5s %-8s %8.2f us  %7.1f GB/s\n", sh.name, "stream", us, bytes / (us * 1e-6) / 1e9);
+        }
+        return 0;
+    }
     if (mode == "tail") {
         // raw per-wave stamps (entry, staged, exit, steps | xcd << 32) of the R1U4 GEMV on every shape, launches
         // 2..NL-1, written to argv[2] for offline analysis (tools/gemv_tail.py)
