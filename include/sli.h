@@ -341,6 +341,73 @@ int sli_model_time_stream(sli_model* m, int32_t iters, double* us);
  * *waited_ms = the wall time the wait took. */
 int sli_debug_bounded_wait(int32_t mode, double deadline_ms, double* waited_ms);
 
+/* ---------------------------------------------------------------- prefill stages, for tests and labs
+ * The kernels of the prompt prefill (csrc/prefill.h), one launch each, without a model: device pointers and a
+ * stream, as sli_matmul. The tiling of the GEMM and the attention kernel are chosen by the functions the engine's
+ * prefill uses (prefill.h pg_pick, launch_pf_attn), so what runs here is what sli_model_prefill runs. fp16 arrays
+ * ("hi" / "lo" operands, fp16 caches) are IEEE binary16. Every device pointer is 16-byte aligned. Anything the
+ * kernels cannot take is SLI_ERR_ARG. `state` is 8 bytes of device memory that the call fills on the stream with
+ * the chunk's start position p0 and valid-row count nv (prefill.h PfState) ahead of the launch.
+ *
+ * sli_prefill_norm_split: x [M][D] fp32 -> hi, lo [M][D] fp16: h = RMSNorm(x row) * w (w NULL: h = x),
+ * hi = fp16(h), lo = fp16(h - hi). D % 4 == 0, D <= 8192, M >= 1. */
+int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, int32_t M, int32_t D, float eps,
+                           sli_stream_t stream);
+
+/* The tiling a sli_prefill_gemm call ran (prefill.h PgCfg): a workgroup owns 16 * AT * WR weight rows x BM chunk
+ * rows; S stages in the LDS ring, PIPE the pipelined fragment reads, SA > 0 the depth of the weights' own ring. */
+typedef struct {
+    int32_t BM, WR, S, AT, PIPE, SA;
+} sli_pgemm_tiling;
+
+/* The fused epilogue of a sli_prefill_gemm call; the fields of the other roles are ignored.
+ * role 0, q/k/v: N = (hq + 2 hkv) * hd rows [q heads; k heads; v heads], hd 64 or 128. Row scale, then rotate-half
+ *   RoPE of the q and k rows at position p0 + m (clamped to T - 1) with sin_t / cos_t [T][hd / 2]; q [M][hq * hd]
+ *   fp32 is stored for every chunk row m < M; the K and V rows go to kc / vc, one layer's cache [hkv][T][hd] in
+ *   kv_dtype (SLI_DT_F16 / SLI_DT_F32), at position p0 + m for m < nv and p0 + m < T only.
+ * role 1, gate/up: N = 2 * inter rows [gate; up]; sigmoid(g) * u (act_mode 0) or SiLU(g) * u (1) as fp16 hi / lo
+ *   in ahi / alo [M][inter].
+ * role 2, wo / down: y[m][r] = (resid ? resid[m][r] : 0) + sum * row scale, y and resid [M][ld] fp32, ld >= N,
+ *   ld % 4 == 0 (resid may be y). */
+typedef struct {
+    int32_t role;
+    /* role 0 */
+    float* q;
+    void* kc;
+    void* vc;
+    int32_t kv_dtype;
+    const float* sin_t;
+    const float* cos_t;
+    int32_t hq, hkv, hd, T;
+    /* role 1 */
+    void* ahi;
+    void* alo;
+    int32_t inter, act_mode;
+    /* role 2 */
+    float* y;
+    const float* resid;
+    int32_t ld;
+} sli_pgemm_epilogue;
+
+/* One pgemm_kernel launch: sums[m][r] = sum_k W[r][k] * (hi[m][k] + lo[m][k]) in fp32 on MFMA, then the epilogue.
+ * W [N][K] in w_dtype (SLI_DT_F16 / SLI_DT_I8), w_row_scale [N] or NULL, hi / lo [M][K] fp16, M one of 32, 64,
+ * 128, 256, K % 64 == 0, N % 16 == 0, 0 <= p0, 1 <= nv <= M. *tiling (optional) receives the tiling that ran. */
+int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
+                     int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                     sli_pgemm_tiling* tiling, sli_stream_t stream);
+
+/* Block-causal attention of M chunk rows (32, 64, 128 or 256): row m of head h attends the cache rows 0 .. p0 + m
+ * of kv head h / (hq / hkv); q [rows][hq * hd] fp32, kc / vc one layer's cache [hkv][T][hd] in kv_dtype, the result
+ * as fp16 hi / lo in ohi / olo [rows][hq * hd]. hd 64 or 128, hq % hkv == 0, 0 <= p0 < T. SLI_DT_F16 runs
+ * pf_attn_mfma_kernel, SLI_DT_F32 pf_attn_kernel. Rows at positions >= T are computed from clamped cache reads and
+ * mean nothing.
+ * Buffer contract: the fp32-cache kernel works in blocks of 64 chunk rows, so at M = 32 it reads q and writes
+ * ohi / olo for rows 32 .. 63 as well. rows_allocated is the number of rows q, ohi and olo really hold; the call is
+ * refused unless it covers the rows the kernel touches (M for an fp16 cache, M rounded up to 64 for fp32). */
+int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
+                     int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
+                     sli_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

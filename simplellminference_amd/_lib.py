@@ -42,6 +42,18 @@ class ShardWindow(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("row_lo", "n_rows", "col_lo", "n_cols", "full_cols", "dst_row_off")]
 
 
+class PgemmTiling(ctypes.Structure):  # sli_pgemm_tiling
+    _fields_ = [(n, c_i32) for n in ("BM", "WR", "S", "AT", "PIPE", "SA")]
+
+
+class PgemmEpilogue(ctypes.Structure):  # sli_pgemm_epilogue
+    _fields_ = [("role", c_i32),
+                ("q", c_vp), ("kc", c_vp), ("vc", c_vp), ("kv_dtype", c_i32), ("sin_t", c_vp), ("cos_t", c_vp),
+                ("hq", c_i32), ("hkv", c_i32), ("hd", c_i32), ("T", c_i32),
+                ("ahi", c_vp), ("alo", c_vp), ("inter", c_i32), ("act_mode", c_i32),
+                ("y", c_vp), ("resid", c_vp), ("ld", c_i32)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "sli_version": (c_int, []),
@@ -118,6 +130,11 @@ _SIGS = {
     "sli_model_time_families": (c_int, [c_vp, c_i32, P_d, P_d, P_i32]),
     "sli_model_time_stream": (c_int, [c_vp, c_i32, P_d]),
     "sli_debug_bounded_wait": (c_int, [c_i32, c_d, P_d]),
+    "sli_prefill_norm_split": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_vp]),
+    "sli_prefill_gemm": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                 ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_attn": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                 c_vp, c_vp]),
     "sli_tp_group_create": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(c_vp)]),
     "sli_tp_group_destroy": (c_int, [c_vp]),
     "sli_tp_group_rank": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),

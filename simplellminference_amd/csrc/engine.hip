@@ -144,7 +144,6 @@ struct sli_model {
 // device-side reduction over the ranks' buffers in rank order (the ranks' kernels are the multi-GPU
 // ones, so the sharded engine itself is what the group tests run).
 constexpr int kMaxGroup = 8;
-constexpr int kPfSizes[4] = {32, 64, 128, 256};  // prefill chunk sizes (the last is prefill.h kPfMaxChunk)
 struct sli_tp_group {
     int n = 0;
     int device = 0;
@@ -1094,44 +1093,16 @@ struct StepRecorder {
             return SLI_OK;
         }
     }
-    // The GEMM tiling (prefill.h PgCfg<BM, WR, S, AT, PIPE>) per weight type, projection role and chunk size: the
-    // fastest of the tools/pgemm_lab sweeps on the 7B shapes (profiles/r3_pgemm_lab.txt; round 6: the pipelined
-    // fragment reads, 5-20 % faster at every tiling, the M = 128 choices, profiles/r6b_pg_pipe.txt, and the M = 256
-    // ones re-timed with the weights streamed from HBM as in the engine, profiles/r6b_pg_cold.txt).
-    // role 0: qkv, 1: gate/up, 2: wo / down (N = D: few row blocks, so small chunk blocks for a full grid).
-    // f(PgCfg<...>{}) is called with the chosen tiling (pg launches it, allow_pg sets its LDS limit).
-    template <class F>
-    static int pg_pick(int M, int role, F&& f) {
-        if constexpr (std::is_same<WT, int8_t>::value) {
-            if (M == 32) return f(PgCfg<32, 2, 4, 2, true>{});
-            if (role == 2) return M == 256 ? f(PgCfg<64, 2, 2, 2, true>{}) : f(PgCfg<32, 2, 4, 2, true>{});
-            if (role == 1) return M == 128 ? f(PgCfg<128, 4, 2, 2, true>{}) : f(PgCfg<64, 4, 2, 2, true>{});
-            return M == 256 ? f(PgCfg<128, 4, 2, 2, true>{}) : f(PgCfg<64, 4, 2, 2, true>{});
-        } else {
-            if (M == 32) return f(PgCfg<32, 2, 4, 2, true>{});
-            if (role == 2) return M == 256 ? f(PgCfg<64, 2, 3, 2, true>{}) : f(PgCfg<32, 2, 4, 2, true>{});
-            if (M == 64 || (M == 128 && role == 0)) return f(PgCfg<64, 2, 3, 2, true>{});
-            // M = 256 with the weights streamed from HBM (profiles/r6b_pg_cold.txt): 8-wave workgroups
-            // (q/k/v: the weights in a 4-deep ring of their own, profiles/r6b_pg_split.txt)
-            if (M == 256) return role == 0 ? f(PgCfg<128, 4, 2, 2, true, 4>{}) : f(PgCfg<64, 4, 3, 2, true>{});
-            return f(PgCfg<128, 2, 2, 2, true>{});
-        }
-    }
+    // the tiling per weight type, projection role and chunk size: prefill.h pg_pick (the one table)
     template <class Epi>
     static int pg(sli_model* m, const void* W, int N, int K, const __half* hi, const __half* lo, const Epi& e, int M,
                   int role) {
-        return pg_pick(M, role, [&](auto cfg) { return pg_cfg<Epi, decltype(cfg)>(m, W, N, K, hi, lo, e, M); });
+        return pg_pick<WT>(M, role, [&](auto cfg) { return pg_cfg<Epi, decltype(cfg)>(m, W, N, K, hi, lo, e, M); });
     }
     template <class Epi>
     static int allow_pg(sli_model*) {
-        if constexpr (std::is_same<WT, int8_t>::value || std::is_same<WT, __half>::value) {
-            for (int M : {32, 64, 128, 256})
-                for (int role = 0; role < 3; ++role)
-                    SLI_TRY(pg_pick(M, role, [&](auto cfg) -> int {
-                        SLI_HIP((pgemm_allow_lds<Epi, decltype(cfg), WT>()));
-                        return SLI_OK;
-                    }));
-        }
+        if constexpr (std::is_same<WT, int8_t>::value || std::is_same<WT, __half>::value)
+            SLI_HIP((pg_allow_lds_all<Epi, WT>()));
         return SLI_OK;
     }
     static int prepare_prefill(sli_model* m) {
@@ -1164,20 +1135,7 @@ struct StepRecorder {
             SLI_TRY(pg(m, w.qkv, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
             PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
                               1.0f / sqrtf((float)hd)};
-            if constexpr (std::is_same<KT, __half>::value) {  // MFMA, 16 chunk rows per workgroup
-                const dim3 ag(M / 16, m->hq);
-                if (hd == 128)
-                    hipLaunchKernelGGL((pf_attn_mfma_kernel<128>), ag, dim3(256), 0, s, aa, f.ps);
-                else
-                    hipLaunchKernelGGL((pf_attn_mfma_kernel<64>), ag, dim3(256), 0, s, aa, f.ps);
-            } else {  // fp32 cache: fp32 VALU, 64 chunk rows per workgroup
-                const dim3 ag((M + kPaQB - 1) / kPaQB, m->hq);
-                if (hd == 128)
-                    hipLaunchKernelGGL((pf_attn_kernel<KT, 128>), ag, dim3(256), 0, s, aa, f.ps);
-                else
-                    hipLaunchKernelGGL((pf_attn_kernel<KT, 64>), ag, dim3(256), 0, s, aa, f.ps);
-            }
-            SLI_HIP(hipGetLastError());
+            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.ps, s));  // fp16 cache: MFMA; fp32: VALU (prefill.h)
             er.rscale = w.wo_s;
             return pg(m, w.wo, D, QD, f.hhi, f.hlo, er, M, 2);
         }
@@ -2673,3 +2631,7 @@ int sli_tp_group_predict_batch(sli_tp_group* g, const int32_t* prompts, const in
 }
 
 }  // extern "C"
+
+// the prefill stages as kernel-level entry points (sli.h "prefill stages, for tests and labs"), compiled here so
+// that they launch this translation unit's copies of the prefill kernels
+#include "prefill_ops.h"

@@ -26,11 +26,13 @@
 // The chunk's start position and valid count live in device memory (PfState), so one captured graph per
 // chunk size serves every chunk of every prompt.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace sli {
 
-constexpr int kPfMaxChunk = 256;   // prompt positions per weight pass
+constexpr int kPfMaxChunk = 256;  // prompt positions per weight pass
 
 struct PfState {
     int32_t p0;  // position of chunk row 0
@@ -45,8 +47,13 @@ __device__ __forceinline__ pf_float4 pf_mfma(const u32x4& a, const u32x4& b, pf_
                                                   0, 0, 0);
 }
 
-// fp32 -> fp16 hi + fp16 lo
+// fp32 -> fp16 hi + fp16 lo. v is pinned in a register first. Without that the split fuses into the expression that
+// produced v: a product a * b contracts into v_fma_mixlo_f16, once for the hi that is stored (the rounded product
+// converted) and once more inside the subtraction (the unrounded product). The two hi differ when the product sits
+// next to an fp16 tie, lo then has the wrong sign, and hi + lo is one fp16 ulp of hi (2^-11 relative) off: about
+// one SwiGLU or attention output in 10^4 (tests/test_gpu_prefill_kernels.py found it).
 __device__ __forceinline__ void pf_split(float v, __half& hi, __half& lo) {
+    asm("" : "+v"(v));
     hi = __float2half_rn(v);
     lo = __float2half_rn(v - __half2float(hi));
 }
@@ -588,6 +595,46 @@ hipError_t pgemm_allow_lds() {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeo<Cfg, WT>::LDS);
 }
 
+// The GEMM tiling (PgCfg<BM, WR, S, AT, PIPE, SA>) per weight type, projection role and chunk size: the fastest of
+// the tools/pgemm_lab sweeps on the 7B shapes (profiles/r3_pgemm_lab.txt; round 6: the pipelined fragment reads,
+// 5-20 % faster at every tiling, the M = 128 choices, profiles/r6b_pg_pipe.txt, and the M = 256 ones re-timed with
+// the weights streamed from HBM as in the engine, profiles/r6b_pg_cold.txt).
+// role 0: qkv, 1: gate/up, 2: wo / down (N = D: few row blocks, so small chunk blocks for a full grid).
+// f(PgCfg<...>{}) is called with the chosen tiling. The one table: the engine's launches, its LDS opt-in and the
+// kernel-level entry point (sli_prefill_gemm) all pick through it.
+template <typename WT, class F>
+int pg_pick(int M, int role, F&& f) {
+    if constexpr (std::is_same<WT, int8_t>::value) {
+        if (M == 32) return f(PgCfg<32, 2, 4, 2, true>{});
+        if (role == 2) return M == 256 ? f(PgCfg<64, 2, 2, 2, true>{}) : f(PgCfg<32, 2, 4, 2, true>{});
+        if (role == 1) return M == 128 ? f(PgCfg<128, 4, 2, 2, true>{}) : f(PgCfg<64, 4, 2, 2, true>{});
+        return M == 256 ? f(PgCfg<128, 4, 2, 2, true>{}) : f(PgCfg<64, 4, 2, 2, true>{});
+    } else {
+        if (M == 32) return f(PgCfg<32, 2, 4, 2, true>{});
+        if (role == 2) return M == 256 ? f(PgCfg<64, 2, 3, 2, true>{}) : f(PgCfg<32, 2, 4, 2, true>{});
+        if (M == 64 || (M == 128 && role == 0)) return f(PgCfg<64, 2, 3, 2, true>{});
+        // M = 256 with the weights streamed from HBM (profiles/r6b_pg_cold.txt): 8-wave workgroups
+        // (q/k/v: the weights in a 4-deep ring of their own, profiles/r6b_pg_split.txt)
+        if (M == 256) return role == 0 ? f(PgCfg<128, 4, 2, 2, true, 4>{}) : f(PgCfg<64, 4, 3, 2, true>{});
+        return f(PgCfg<128, 2, 2, 2, true>{});
+    }
+}
+
+constexpr int kPfSizes[4] = {32, 64, 128, 256};  // prefill chunk sizes, the rows of the table (the last is kPfMaxChunk)
+
+// the LDS opt-in of every tiling the table can pick for this epilogue and weight type
+template <class Epi, typename WT>
+hipError_t pg_allow_lds_all() {
+    hipError_t err = hipSuccess;
+    for (int M : kPfSizes)
+        for (int role = 0; role < 3; ++role)
+            pg_pick<WT>(M, role, [&](auto cfg) {
+                if (err == hipSuccess) err = pgemm_allow_lds<Epi, decltype(cfg), WT>();
+                return 0;
+            });
+    return err;
+}
+
 // ---------------------------------------------------------------- 3. block-causal attention
 // grid (M / 64, hq); 4 waves x 16 queries; lane l: query l & 15 of the wave, dims [c * HD/4, (c+1) * HD/4) with
 // c = l >> 4. Scores: the 4 lanes of a query add their quarter dot products (xor 16 / 32 exchanges); every lane
@@ -853,6 +900,30 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
         *reinterpret_cast<uint2*>(a.ohi + idx) = *reinterpret_cast<const uint2*>(hh);
         *reinterpret_cast<uint2*>(a.olo + idx) = *reinterpret_cast<const uint2*>(hl);
     }
+}
+
+// The attention of M chunk rows (hd 64 or 128: the caller's check): an fp16 cache on MFMA, 16 chunk rows per
+// workgroup; an fp32 cache on the VALU kernel, 64 chunk rows per workgroup, so at M = 32 it reads q and writes
+// ohi / olo for rows 32 .. 63 too (the buffers hold at least 64 rows). The engine and sli_prefill_attn launch
+// through here.
+constexpr int pf_attn_rows(bool f16_cache, int M) { return f16_cache ? M : (M + kPaQB - 1) / kPaQB * kPaQB; }
+
+template <typename KT>
+hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const PfState* ps, hipStream_t s) {
+    if constexpr (std::is_same<KT, __half>::value) {
+        const dim3 ag(M / 16, aa.hq);
+        if (hd == 128)
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<128>), ag, dim3(256), 0, s, aa, ps);
+        else
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<64>), ag, dim3(256), 0, s, aa, ps);
+    } else {
+        const dim3 ag((M + kPaQB - 1) / kPaQB, aa.hq);
+        if (hd == 128)
+            hipLaunchKernelGGL((pf_attn_kernel<KT, 128>), ag, dim3(256), 0, s, aa, ps);
+        else
+            hipLaunchKernelGGL((pf_attn_kernel<KT, 64>), ag, dim3(256), 0, s, aa, ps);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace sli

@@ -1,0 +1,162 @@
+// prefill_ops.h — the prefill stages as kernel-level entry points (include/sli.h "prefill stages, for tests and
+// labs"): one launch of pf_norm_split_kernel, pgemm_kernel or a prefill attention kernel on caller-provided device
+// buffers. Included once, at the end of engine.hip, so the library holds ONE compiled copy of every prefill kernel:
+// the entries launch the very code objects sli_model_prefill launches. The GEMM tiling comes from prefill.h pg_pick
+// and the attention kernel from launch_pf_attn, the functions the engine's record_pf_phase uses. The checks mirror
+// the engine's pf_supported and the contracts stated in prefill.h: whatever a kernel would read or write out of
+// bounds for is refused here.
+#pragma once
+#include <cmath>
+
+#include "common.h"
+#include "prefill.h"
+
+namespace sli {
+
+__global__ void pf_set_state_kernel(PfState* ps, int p0, int nv) {
+    ps->p0 = p0;
+    ps->nv = nv;
+}
+
+static int pf_set_state(void* state, int p0, int nv, hipStream_t s) {
+    hipLaunchKernelGGL(pf_set_state_kernel, dim3(1), dim3(1), 0, s, (PfState*)state, p0, nv);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+static bool pf_chunk_size(int M) {
+    for (int s : kPfSizes)
+        if (M == s) return true;
+    return false;
+}
+
+static bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+template <class Epi, typename WT>
+static int pf_gemm_launch(const void* w, const void* hi, const void* lo, int N, int K, int M, int role, const Epi& e,
+                          const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
+    SLI_HIP((pg_allow_lds_all<Epi, WT>()));
+    const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M};
+    return pg_pick<WT>(M, role, [&](auto cfg) -> int {
+        using Cfg = decltype(cfg);
+        if (tiling) *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA};
+        SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
+        return SLI_OK;
+    });
+}
+
+template <typename WT>
+static int pf_gemm_role(const void* w, const float* rs, const void* hi, const void* lo, int N, int K, int M,
+                        const sli_pgemm_epilogue& e, const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
+    if (e.role == 0) {
+        if (e.kv_dtype == SLI_DT_F16) {
+            const PgEpiQKV<__half> q{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
+            return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, hi, lo, N, K, M, 0, q, ps, tiling, s);
+        }
+        const PgEpiQKV<float> q{e.q, (float*)e.kc, (float*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
+        return pf_gemm_launch<PgEpiQKV<float>, WT>(w, hi, lo, N, K, M, 0, q, ps, tiling, s);
+    }
+    if (e.role == 1) {
+        const PgEpiSwiGLU g{(__half*)e.ahi, (__half*)e.alo, rs, e.inter, e.act_mode};
+        return pf_gemm_launch<PgEpiSwiGLU, WT>(w, hi, lo, N, K, M, 1, g, ps, tiling, s);
+    }
+    const PgEpiResid r{e.y, e.resid, rs, N, e.ld};
+    return pf_gemm_launch<PgEpiResid, WT>(w, hi, lo, N, K, M, 2, r, ps, tiling, s);
+}
+
+}  // namespace sli
+
+using namespace sli;
+
+extern "C" {
+
+int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, int32_t M, int32_t D, float eps,
+                           sli_stream_t stream) {
+    SLI_CHECK(x && hi && lo, SLI_ERR_ARG, "sli_prefill_norm_split: null pointer");
+    SLI_CHECK(M >= 1 && M <= 65535, SLI_ERR_ARG, "sli_prefill_norm_split: M must be in [1, 65535]");
+    SLI_CHECK(D >= 4 && D % 4 == 0 && D <= 8192, SLI_ERR_ARG,
+              "sli_prefill_norm_split: D must be a multiple of 4, at most 8192 (the row is held in registers)");
+    SLI_CHECK(al16(x) && al16(w) && al16(hi) && al16(lo), SLI_ERR_ARG, "sli_prefill_norm_split: 16-byte alignment");
+    hipLaunchKernelGGL(pf_norm_split_kernel, dim3(M), dim3(256), 0, as_stream(stream), x, w, (__half*)hi, (__half*)lo,
+                       D, eps);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
+                     int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                     sli_pgemm_tiling* tiling, sli_stream_t stream) {
+    SLI_CHECK(w && hi && lo && epi && state, SLI_ERR_ARG, "sli_prefill_gemm: null pointer");
+    SLI_CHECK(w_dtype == SLI_DT_F16 || w_dtype == SLI_DT_I8, SLI_ERR_ARG,
+              "sli_prefill_gemm: fp16 or int8 weights (fp32 and MXFP4 have no GEMM prefill)");
+    SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_gemm: M must be 32, 64, 128 or 256");
+    SLI_CHECK(K >= 64 && K % 64 == 0, SLI_ERR_ARG, "sli_prefill_gemm: K must be a multiple of 64");
+    SLI_CHECK(N >= 16 && N % 16 == 0, SLI_ERR_ARG, "sli_prefill_gemm: N must be a multiple of 16");
+    SLI_CHECK((int64_t)N * K < ((int64_t)1 << 40) && K <= (1 << 20), SLI_ERR_ARG, "sli_prefill_gemm: shape too large");
+    SLI_CHECK(p0 >= 0 && p0 <= (1 << 30) && nv >= 1 && nv <= M, SLI_ERR_ARG,
+              "sli_prefill_gemm: p0 must be >= 0 and nv in [1, M]");
+    SLI_CHECK(al16(w) && al16(w_row_scale) && al16(hi) && al16(lo) && (uintptr_t)state % 8 == 0, SLI_ERR_ARG,
+              "sli_prefill_gemm: 16-byte alignment");
+    const sli_pgemm_epilogue& e = *epi;
+    switch (e.role) {
+        case 0:
+            SLI_CHECK(e.q && e.kc && e.vc && e.sin_t && e.cos_t, SLI_ERR_ARG, "sli_prefill_gemm: null q/k/v operand");
+            SLI_CHECK(e.kv_dtype == SLI_DT_F16 || e.kv_dtype == SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_gemm: bad kv dtype");
+            SLI_CHECK(e.hd == 64 || e.hd == 128, SLI_ERR_ARG, "sli_prefill_gemm: head_dim must be 64 or 128");
+            SLI_CHECK(e.hq >= 1 && e.hkv >= 1 && e.hq % e.hkv == 0, SLI_ERR_ARG,
+                      "sli_prefill_gemm: hq must be a multiple of hkv");
+            SLI_CHECK((int64_t)N == ((int64_t)e.hq + 2 * (int64_t)e.hkv) * e.hd, SLI_ERR_ARG,
+                      "sli_prefill_gemm: N must be (hq + 2 hkv) * hd");
+            SLI_CHECK(e.T >= 1, SLI_ERR_ARG, "sli_prefill_gemm: T must be positive");
+            SLI_CHECK(al16(e.q) && al16(e.kc) && al16(e.vc) && al16(e.sin_t) && al16(e.cos_t), SLI_ERR_ARG,
+                      "sli_prefill_gemm: 16-byte alignment");
+            break;
+        case 1:
+            SLI_CHECK(e.ahi && e.alo, SLI_ERR_ARG, "sli_prefill_gemm: null gate/up operand");
+            SLI_CHECK(e.inter >= 8 && N == 2 * e.inter, SLI_ERR_ARG, "sli_prefill_gemm: N must be 2 * inter");
+            SLI_CHECK(e.act_mode == 0 || e.act_mode == 1, SLI_ERR_ARG, "sli_prefill_gemm: act_mode must be 0 or 1");
+            SLI_CHECK(al16(e.ahi) && al16(e.alo), SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
+            break;
+        case 2:
+            SLI_CHECK(e.y, SLI_ERR_ARG, "sli_prefill_gemm: null y");
+            SLI_CHECK(e.ld >= N && e.ld % 4 == 0, SLI_ERR_ARG, "sli_prefill_gemm: ld must be >= N and a multiple of 4");
+            SLI_CHECK(al16(e.y) && al16(e.resid), SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
+            break;
+        default: return fail(SLI_ERR_ARG, "sli_prefill_gemm: role must be 0 (qkv), 1 (gate/up) or 2 (wo/down)");
+    }
+    hipStream_t s = as_stream(stream);
+    if (int rc = pf_set_state(state, p0, nv, s)) return rc;
+    const PfState* ps = (const PfState*)state;
+    if (w_dtype == SLI_DT_I8) return pf_gemm_role<int8_t>(w, w_row_scale, hi, lo, N, K, M, e, ps, tiling, s);
+    return pf_gemm_role<__half>(w, w_row_scale, hi, lo, N, K, M, e, ps, tiling, s);
+}
+
+int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
+                     int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
+                     sli_stream_t stream) {
+    SLI_CHECK(q && kc && vc && ohi && olo && state, SLI_ERR_ARG, "sli_prefill_attn: null pointer");
+    SLI_CHECK(kv_dtype == SLI_DT_F16 || kv_dtype == SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_attn: bad kv dtype");
+    SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_attn: M must be 32, 64, 128 or 256");
+    SLI_CHECK(hd == 64 || hd == 128, SLI_ERR_ARG, "sli_prefill_attn: head_dim must be 64 or 128");
+    SLI_CHECK(hq >= 1 && hkv >= 1 && hq % hkv == 0 && hq <= 65535, SLI_ERR_ARG,
+              "sli_prefill_attn: hq must be a multiple of hkv");
+    SLI_CHECK(T >= 1 && p0 >= 0 && p0 < T, SLI_ERR_ARG, "sli_prefill_attn: p0 must be in [0, T)");
+    SLI_CHECK(rows_allocated >= pf_attn_rows(kv_dtype == SLI_DT_F16, M), SLI_ERR_ARG,
+              "sli_prefill_attn: q / ohi / olo must hold M rows (fp32 cache: M rounded up to 64, the kernel's block)");
+    SLI_CHECK(al16(q) && al16(kc) && al16(vc) && al16(ohi) && al16(olo) && (uintptr_t)state % 8 == 0, SLI_ERR_ARG,
+              "sli_prefill_attn: 16-byte alignment");
+    hipStream_t s = as_stream(stream);
+    if (int rc = pf_set_state(state, p0, M, s)) return rc;
+    const PfState* ps = (const PfState*)state;
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (kv_dtype == SLI_DT_F16) {
+        const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<__half>(aa, hd, M, ps, s));
+    } else {
+        const PfAttnArgs<float> aa{q, (const float*)kc, (const float*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<float>(aa, hd, M, ps, s));
+    }
+    return SLI_OK;
+}
+
+}  // extern "C"

@@ -172,6 +172,94 @@ def embedding(token, table, out=None, row_scale=None):
     return out
 
 
+# ---------------------------------------------------------------- prefill stages (sli.h "for tests and labs")
+PF_ROLE_QKV, PF_ROLE_GATE_UP, PF_ROLE_RESID = 0, 1, 2
+
+
+def _pf_state(device):
+    return torch.empty(2, device=device, dtype=torch.int32)
+
+
+def prefill_norm_split(x, w, eps: float):
+    """pf_norm_split_kernel: x [M, D] fp32 -> (hi, lo) [M, D] fp16; w None: the plain split of x."""
+    M, D = x.shape
+    hi = torch.empty(M, D, device=x.device, dtype=torch.float16)
+    lo = torch.empty_like(hi)
+    _dev(x, w, hi, lo)
+    call("sli_prefill_norm_split", _p(x), _p(w), _p(hi), _p(lo), M, D, eps, _s())
+    return hi, lo
+
+
+def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi):
+    N, K = w.shape
+    M = hi.shape[0]
+    if hi.shape != (M, K) or lo.shape != (M, K) or hi.dtype != torch.float16 or lo.dtype != torch.float16:
+        raise ValueError("Tensor with Wrong Dim!")
+    if w.dtype not in (torch.float16, torch.int8):
+        raise ValueError("prefill GEMM takes fp16 or int8 weights")
+    state = _pf_state(w.device)
+    _dev(w, row_scale, hi, lo)
+    tl = _lib.PgemmTiling()
+    call("sli_prefill_gemm", _p(w), _DT[w.dtype], _p(row_scale), _p(hi), _p(lo), N, K, M, p0, nv, ctypes.byref(epi),
+         _p(state), ctypes.byref(tl), _s())
+    return {n: getattr(tl, n) for n, _ in tl._fields_}
+
+
+def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, p0: int, nv: int,
+                     row_scale=None):
+    """One pgemm_kernel launch with the q/k/v epilogue: W [(hq + 2 hkv) hd, K]; q [M, hq hd] fp32 gets every chunk
+    row; kc / vc, one layer's cache [hkv, T, hd] (f16 or f32), get rows p0 + m for m < nv, p0 + m < T. Returns the
+    tiling that ran."""
+    if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[1]
+    if q.shape != (hi.shape[0], hq * hd) or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, sin_t, cos_t)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_DT[kc.dtype], sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
+                           hd=hd, T=T)
+    return _prefill_gemm(w, row_scale, hi, lo, p0, nv, e)
+
+
+def prefill_gemm_gate_up(w, hi, lo, ahi, alo, act_mode: int = 0, row_scale=None):
+    """One pgemm_kernel launch with the SwiGLU epilogue: W [2 inter, K] = [gate; up]; ahi / alo [M, inter] fp16."""
+    inter = w.shape[0] // 2
+    if ahi.shape != (hi.shape[0], inter) or alo.shape != ahi.shape:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(ahi, alo)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_GATE_UP, ahi=ahi.data_ptr(), alo=alo.data_ptr(), inter=inter,
+                           act_mode=act_mode)
+    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e)
+
+
+def prefill_gemm_resid(w, hi, lo, y, resid=None, row_scale=None):
+    """One pgemm_kernel launch with the wo / down epilogue: y [M, ld] = (resid or 0) + W (hi + lo) * row scale."""
+    if y.shape[0] != hi.shape[0] or (resid is not None and resid.shape != y.shape):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_RESID, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                           ld=y.shape[1])
+    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e)
+
+
+def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int):
+    """Block-causal prefill attention of chunk rows 0 .. M-1 at positions p0 + m over one layer's cache [hkv, T, hd]
+    (f16: MFMA kernel, f32: VALU kernel). q [rows, hq hd] fp32 with rows >= M (f32 cache: >= M rounded up to 64, the
+    contract of sli_prefill_attn); returns (ohi, olo) [rows, hq hd] fp16."""
+    rows = q.shape[0]
+    if q.shape != (rows, hq * hd) or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[1]
+    ohi = torch.zeros(rows, hq * hd, device=q.device, dtype=torch.float16)
+    olo = torch.zeros_like(ohi)
+    state = _pf_state(q.device)
+    _dev(q, kc, vc)
+    call("sli_prefill_attn", _p(q), _p(kc), _p(vc), _DT[kc.dtype], _p(ohi), _p(olo), M, rows, p0, hq, hkv, hd, T,
+         _p(state), _s())
+    return ohi, olo
+
+
 def argmax(logits, out=None):
     """argmaxLayer::forward (argmax.cpp:7-17) on device: first index of the maximum."""
     out = torch.empty(1, device=logits.device, dtype=torch.int32) if out is None else out
