@@ -227,7 +227,8 @@ int sli_model_get_state_seq(sli_model* m, int32_t seq, int32_t* pos, int32_t* to
                             int32_t* error);
 /* Prompt prefill (batch-1 models): positions 0 .. n-2 of the prompt run through the layers in chunks of up
  * to 256 positions, every projection one MFMA GEMM over the chunk and attention block-causal over the
- * cache (fp16 / int8 weights, head_dim 64 / 128; otherwise through the decode step, teacher-forced; under
+ * cache (fp16 / int8 weights, MXFP4 after sli_model_set_prefill(SLI_PREFILL_GEMM), head_dim 64 / 128; otherwise
+ * through the decode step, teacher-forced; under
  * multi-process tensor parallelism every rank calls it, the chunk's residual rows all-reduced over RCCL
  * twice per layer), filling the K/V cache; the state is left at
  * (token ids[n-1], position n-1, advancing, prompt = ids), so the next sli_model_step yields the first
@@ -236,6 +237,14 @@ int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n);
 /* Which path sli_model_prefill takes for this model: 1 = chunked MFMA GEMMs (prefill.h), 0 = the decode step,
  * teacher-forced (fp32 weights, batch > 1, unsupported shapes, or a TP rank without an RCCL communicator). */
 int sli_model_prefill_path(const sli_model* m);
+/* Which path the next prefill takes. SLI_PREFILL_AUTO (the default): the GEMM prefill where the model can take it,
+ * except MXFP4 weights, which stay on the decode step; SLI_PREFILL_GEMM: the chunked MFMA prefill for every weight
+ * type that has one (fp16, int8, MXFP4), SLI_ERR_STATE with the reason where the model cannot take it (fp32 weights,
+ * batch > 1, a TP rank without a communicator, unsupported shapes); SLI_PREFILL_DECODE: the teacher-forced decode
+ * step for any model. May be changed between prefills; sli_model_prefill_path reports the outcome. The ranks of an
+ * in-process group are set through sli_tp_group_set_prefill. */
+enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2 };
+int sli_model_set_prefill(sli_model* m, int32_t mode);
 /* 1: the batch-1 decode step runs each layer's q/k/v projection and attention as ONE launch (qkv_attn.h: the
  * attention's K/V rows below the position stream while the projection runs; q and this step's K/V row are
  * handed over inside the launch); 0: separate launches (model.cpp:70-84's matmul / rope / mha sequence either
@@ -314,6 +323,8 @@ int sli_tp_group_predict_batch(sli_tp_group* g, const int32_t* prompts, const in
 int sli_tp_group_prefill(sli_tp_group* g, const int32_t* ids, int32_t n);
 int sli_tp_group_predict_prefill(sli_tp_group* g, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                                  int32_t* tokens_out, float* logits_out);
+/* sli_model_set_prefill for every rank of the group. */
+int sli_tp_group_set_prefill(sli_tp_group* g, int32_t mode);
 
 /* Roofline probe: replays the step's weight-streaming (GEMV) kernels `iters` times between HIP events
  * on the model's stream; returns mean device time per GEMV launch, algorithmic bytes per launch and
@@ -355,9 +366,11 @@ int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, i
                            sli_stream_t stream);
 
 /* The tiling a sli_prefill_gemm call ran (prefill.h PgCfg): a workgroup owns 16 * AT * WR weight rows x BM chunk
- * rows; S stages in the LDS ring, PIPE the pipelined fragment reads, SA > 0 the depth of the weights' own ring. */
+ * rows; S stages in the LDS ring, PIPE the pipelined fragment reads, SA > 0 the depth of the weights' own ring, KS
+ * the depth (k) one stage covers. */
 typedef struct {
     int32_t BM, WR, S, AT, PIPE, SA;
+    int32_t KS;
 } sli_pgemm_tiling;
 
 /* The fused epilogue of a sli_prefill_gemm call; the fields of the other roles are ignored.
@@ -395,6 +408,14 @@ typedef struct {
 int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
                      int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
                      sli_pgemm_tiling* tiling, sli_stream_t stream);
+/* sli_prefill_gemm for MXFP4 weights (beside it as sli_matmul_mxfp4 is beside sli_matmul): data uint8 [N][K / 2],
+ * scales uint8 [N][K / 32] in the public layout (element 2i in bits 3:0 of byte i, scale 2^(byte - 127)); one
+ * pgemm_mx_kernel launch, the code object an MXFP4 model's GEMM prefill launches. The same checks; data is 16-byte
+ * aligned, scales need no alignment (they are loaded by the byte). The epilogues apply no row scale. Scale bytes
+ * 1 .. 254 are exact (the block scale is applied in fp32). */
+int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N, int32_t K,
+                           int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                           sli_pgemm_tiling* tiling, sli_stream_t stream);
 
 /* Block-causal attention of M chunk rows (32, 64, 128 or 256): row m of head h attends the cache rows 0 .. p0 + m
  * of kv head h / (hq / hkv); q [rows][hq * hd] fp32, kc / vc one layer's cache [hkv][T][hd] in kv_dtype, the result

@@ -43,7 +43,7 @@ class ShardWindow(ctypes.Structure):
 
 
 class PgemmTiling(ctypes.Structure):  # sli_pgemm_tiling
-    _fields_ = [(n, c_i32) for n in ("BM", "WR", "S", "AT", "PIPE", "SA")]
+    _fields_ = [(n, c_i32) for n in ("BM", "WR", "S", "AT", "PIPE", "SA", "KS")]
 
 
 class PgemmEpilogue(ctypes.Structure):  # sli_pgemm_epilogue
@@ -133,6 +133,10 @@ _SIGS = {
     "sli_prefill_norm_split": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_vp]),
     "sli_prefill_gemm": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
                                  ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_gemm_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                       ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_model_set_prefill": (c_int, [c_vp, c_i32]),
+    "sli_tp_group_set_prefill": (c_int, [c_vp, c_i32]),
     "sli_prefill_attn": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                  c_vp, c_vp]),
     "sli_tp_group_create": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(c_vp)]),

@@ -113,6 +113,7 @@ struct sli_model {
         sli::PfState* ps = nullptr;             // chunk start position + valid rows (device)
         hipGraph_t graph[4] = {};
         hipGraphExec_t exec[4] = {};
+        int mode = SLI_PREFILL_AUTO;  // sli_model_set_prefill
     } pf;
     // tensor-parallel all-reduce: SLI_ALLREDUCE_RCCL (ncclAllReduce) or SLI_ALLREDUCE_ONESHOT (oneshot.h)
     int ar_mode = SLI_ALLREDUCE_RCCL;
@@ -1082,11 +1083,16 @@ struct StepRecorder {
     // GEMM just wrote. No LM head: the prompt's logits are not used (teacher forcing); the last prompt
     // position runs as an ordinary decode step. Phases as record_phase: 2l = qkv, attention, wo; 2l+1 =
     // gate/up, down; under tensor parallelism each ends with the all-reduce of the chunk's residual rows.
+    // Ws: the e8m0 block scales of an mxfp4 matrix (the LayerW *_s pointer; the epilogue's rscale is null then)
     template <class Epi, class Cfg>
-    static int pg_cfg(sli_model* m, const void* W, int N, int K, const __half* hi, const __half* lo, const Epi& e,
-                      int M) {
-        if constexpr (std::is_same<WT, float>::value || MX) {
-            return fail(SLI_ERR_ARG, "prefill needs fp16 or int8 weights");
+    static int pg_cfg(sli_model* m, const void* W, const void* Ws, int N, int K, const __half* hi, const __half* lo,
+                      const Epi& e, int M) {
+        if constexpr (std::is_same<WT, float>::value) {
+            return fail(SLI_ERR_ARG, "prefill needs fp16, int8 or mxfp4 weights");
+        } else if constexpr (MX) {
+            const PgInMx in{(const uint8_t*)W, (const uint8_t*)Ws, hi, lo, N, K, M};
+            SLI_HIP((launch_pgemm_mx<Epi, Cfg>(in, e, m->pf.ps, m->stream)));
+            return SLI_OK;
         } else {
             const PgIn<WT> in{(const WT*)W, hi, lo, N, K, M};
             SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, m->pf.ps, m->stream)));
@@ -1095,14 +1101,13 @@ struct StepRecorder {
     }
     // the tiling per weight type, projection role and chunk size: prefill.h pg_pick (the one table)
     template <class Epi>
-    static int pg(sli_model* m, const void* W, int N, int K, const __half* hi, const __half* lo, const Epi& e, int M,
-                  int role) {
-        return pg_pick<WT>(M, role, [&](auto cfg) { return pg_cfg<Epi, decltype(cfg)>(m, W, N, K, hi, lo, e, M); });
+    static int pg(sli_model* m, const void* W, const void* Ws, int N, int K, const __half* hi, const __half* lo,
+                  const Epi& e, int M, int role) {
+        return pg_pick<WT>(M, role, [&](auto cfg) { return pg_cfg<Epi, decltype(cfg)>(m, W, Ws, N, K, hi, lo, e, M); });
     }
     template <class Epi>
     static int allow_pg(sli_model*) {
-        if constexpr (std::is_same<WT, int8_t>::value || std::is_same<WT, __half>::value)
-            SLI_HIP((pg_allow_lds_all<Epi, WT>()));
+        if constexpr (!std::is_same<WT, float>::value) SLI_HIP((pg_allow_lds_all<Epi, WT>()));
         return SLI_OK;
     }
     static int prepare_prefill(sli_model* m) {
@@ -1115,34 +1120,39 @@ struct StepRecorder {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
-        if constexpr (!MX) {  // (mxfp4 has no GEMM prefill: pf_supported; pg_cfg fails below)
-            if (p == 0) {
+        if (p == 0) {
+            if constexpr (MX)
+                hipLaunchKernelGGL(pf_embed_mx_kernel, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const uint8_t*)m->emb,
+                                   (const uint8_t*)m->emb_s, f.x, D);
+            else
                 hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
                                    m->emb_s, f.x, D);
-                SLI_HIP(hipGetLastError());
-            }
+            SLI_HIP(hipGetLastError());
         }
         const int l = p / 2;
         const LayerW& w = m->layers[l];
         const bool tp = m->partial;
+        // int8: the *_s pointers are row scales for the epilogue; mxfp4: block scales for the GEMM's own loads
+        auto rs = [](const float* sc) { return MX ? nullptr : sc; };
         PgEpiResid er{tp ? f.xpart : f.x, (!tp || m->c.tp_rank == 0) ? f.x : nullptr, nullptr, D, D};
         hipLaunchKernelGGL(pf_norm_split_kernel, dim3(M), dim3(256), 0, s, f.x, m->norms + (size_t)p * D, f.hhi, f.hlo,
                            D, m->c.eps);
         SLI_HIP(hipGetLastError());
         if (p % 2 == 0) {
             const size_t ls = (size_t)l * m->hkv * m->T * hd;
-            PgEpiQKV<KT> eq{f.q, (KT*)m->kc + ls, (KT*)m->vc + ls, w.qkv_s, m->sin_t, m->cos_t, m->hq, m->hkv, hd, m->T};
-            SLI_TRY(pg(m, w.qkv, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
+            PgEpiQKV<KT> eq{f.q, (KT*)m->kc + ls, (KT*)m->vc + ls, rs(w.qkv_s), m->sin_t, m->cos_t, m->hq, m->hkv, hd,
+                            m->T};
+            SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
             PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
                               1.0f / sqrtf((float)hd)};
             SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.ps, s));  // fp16 cache: MFMA; fp32: VALU (prefill.h)
-            er.rscale = w.wo_s;
-            return pg(m, w.wo, D, QD, f.hhi, f.hlo, er, M, 2);
+            er.rscale = rs(w.wo_s);
+            return pg(m, w.wo, w.wo_s, D, QD, f.hhi, f.hlo, er, M, 2);
         }
-        PgEpiSwiGLU eg{f.ahi, f.alo, w.gu_s, m->Il, m->c.act_mode};
-        SLI_TRY(pg(m, w.gu, 2 * m->Il, D, f.hhi, f.hlo, eg, M, 1));
-        er.rscale = w.down_s;
-        return pg(m, w.down, D, m->Il, f.ahi, f.alo, er, M, 2);
+        PgEpiSwiGLU eg{f.ahi, f.alo, rs(w.gu_s), m->Il, m->c.act_mode};
+        SLI_TRY(pg(m, w.gu, w.gu_s, 2 * m->Il, D, f.hhi, f.hlo, eg, M, 1));
+        er.rscale = rs(w.down_s);
+        return pg(m, w.down, w.down_s, D, m->Il, f.ahi, f.alo, er, M, 2);
     }
     static int record_prefill(sli_model* m, int M) {
         for (int p = 0; p < 2 * m->L; ++p) {
@@ -1835,17 +1845,32 @@ static int get_state(sli_model* m, int seq, int32_t* pos, int32_t* token, int32_
 }  // extern "C" (reopened below)
 
 // ---------------------------------------------------------------- prompt prefill
-// The GEMM prefill (prefill.h) needs fp16 or int8 weights, batch 1, head_dim 64 or 128 and 64-multiple
-// projection depths; otherwise the prompt runs through the decode step itself (teacher forcing), which gives
-// the same tokens.
+// The GEMM prefill (prefill.h) needs fp16, int8 or MXFP4 weights (MXFP4 only on request: sli_model_set_prefill),
+// batch 1, head_dim 64 or 128 and 64-multiple projection depths; otherwise the prompt runs through the decode step
+// itself (teacher forcing), which gives the same tokens.
 // The chunked MFMA prefill (prefill.h) takes GEMM depths that are multiples of 64 (int8: 128-deep stages with a
 // half last stage). A multi-process TP rank without an RCCL communicator (SLI_DEBUG_NOCOMM, with or without the
 // one-shot exchange) has no all-reduce for a chunk's M x D residual rows, so it prefills through the decode step,
 // whose exchange it does have; an in-process group sums the chunk rows itself (record_group_prefill).
 static bool pf_supported(const sli_model* m) {
     if (m->partial && !m->collectives && !m->group) return false;
-    return m->c.w_dtype != SLI_DT_F32 && m->c.w_dtype != SLI_DT_MXFP4 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
+    return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
            m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
+}
+// What the next prefill runs (sli_model_set_prefill): the chunks are captured graphs of the GEMM path alone and the
+// stepwise path replays the decode graph, so the mode only selects which of the two is launched; nothing captured
+// depends on it. auto keeps MXFP4 on the decode step (the default flips once the tests that pin it are revisited).
+static bool pf_use_gemm(const sli_model* m) {
+    if (m->pf.mode == SLI_PREFILL_DECODE || !pf_supported(m)) return false;
+    return m->pf.mode == SLI_PREFILL_GEMM || m->c.w_dtype != SLI_DT_MXFP4;
+}
+static int pf_set_mode(sli_model* m, int mode) {
+    SLI_CHECK(mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_DECODE, SLI_ERR_ARG, "set_prefill: mode must be 0, 1 or 2");
+    SLI_CHECK(mode != SLI_PREFILL_GEMM || pf_supported(m), SLI_ERR_STATE,
+              "set_prefill: this model cannot take the GEMM prefill (fp32 weights, batch > 1, a TP rank without a "
+              "communicator, head_dim not 64 / 128, or a projection depth that is no multiple of 64)");
+    m->pf.mode = mode;
+    return SLI_OK;
 }
 
 static int pf_bucket(int nv) {
@@ -1881,7 +1906,23 @@ static std::vector<PfState> pf_chunks(int n) {
     return cs;
 }
 
-extern "C" int sli_model_prefill_path(const sli_model* m) { return m && m->B == 1 && pf_supported(m) ? 1 : 0; }
+extern "C" int sli_model_prefill_path(const sli_model* m) { return m && m->B == 1 && pf_use_gemm(m) ? 1 : 0; }
+
+extern "C" int sli_model_set_prefill(sli_model* m, int32_t mode) {
+    SLI_CHECK(m, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(!m->group, SLI_ERR_STATE, "set_prefill: ranks of an in-process group are set through sli_tp_group_set_prefill");
+    return pf_set_mode(m, mode);
+}
+
+extern "C" int sli_tp_group_set_prefill(sli_tp_group* g, int32_t mode) {
+    SLI_CHECK(g, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_DECODE, SLI_ERR_ARG, "set_prefill: mode must be 0, 1 or 2");
+    for (sli_model* m : g->ranks)
+        SLI_CHECK(mode != SLI_PREFILL_GEMM || pf_supported(m), SLI_ERR_STATE,
+                  "set_prefill: this group cannot take the GEMM prefill");
+    for (sli_model* m : g->ranks) SLI_TRY(pf_set_mode(m, mode));
+    return SLI_OK;
+}
 
 extern "C" int sli_model_fused_qkv_attn(sli_model* m) {
     if (!m || m->B != 1) return 0;
@@ -1900,7 +1941,7 @@ extern "C" int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n) {
     SLI_HIP(hipSetDevice(m->c.device));
     SLI_TRY(set_prompt(m, 0, ids, n));
     SLI_HIP(hipMemcpyAsync(m->hist, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, m->stream));
-    if (n > 1 && pf_supported(m)) {
+    if (n > 1 && pf_use_gemm(m)) {
         SLI_TRY(pf_alloc(m));
         const std::vector<PfState> cs = pf_chunks(n);
         for (const PfState& c : cs) {  // capture before anything is enqueued behind the capture
@@ -1933,7 +1974,7 @@ extern "C" int sli_tp_group_prefill(sli_tp_group* g, const int32_t* ids, int32_t
         SLI_TRY(set_prompt(m, 0, ids, n));
         SLI_HIP(hipMemcpyAsync(m->hist, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, m->stream));
     }
-    if (n > 1 && pf_supported(m0)) {
+    if (n > 1 && pf_use_gemm(m0)) {
         for (sli_model* m : g->ranks) SLI_TRY(pf_alloc(m));
         const std::vector<PfState> cs = pf_chunks(n);
         for (const PfState& c : cs) {

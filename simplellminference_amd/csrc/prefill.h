@@ -22,13 +22,15 @@
 //      (ds_read_b64_tr_b16) from LDS-DMA'd K/V tiles; pf_attn_kernel, the VALU form (fp32, 64-position query
 //      blocks, K/V tiles of 64 positions in LDS), serves fp32 KV caches.
 // int8 weights: stages of 128 k; a depth that is 64 mod 128 (e.g. Llama-2-7B int8 down at TP 4, 2752) ends with
-// a half stage (pgemm_kernel).
+// a half stage (pgemm_kernel). MXFP4 weights: pgemm_mx_kernel, the same ring with a scale image per stage and the
+// block scale applied to each k-block's tile in fp32 (below, "MXFP4 weights").
 // The chunk's start position and valid count live in device memory (PfState), so one captured graph per
 // chunk size serves every chunk of every prompt.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "mxfp4.h"
 
 namespace sli {
 
@@ -69,6 +71,16 @@ __global__ void __launch_bounds__(256) pf_embed_kernel(const PfState* __restrict
     const int tok = prompt[ps->p0 + min(m, nv - 1)];
     const float s = emb_s ? emb_s[tok] : 1.0f;
     for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = to_f32(emb[(size_t)tok * D + i]) * s;
+}
+
+// MXFP4 table (mxfp4.h layout): a table decode per element, the block scales behind emb_s
+__global__ void __launch_bounds__(256) pf_embed_mx_kernel(const PfState* __restrict__ ps, const int32_t* __restrict__ prompt,
+                                                         const uint8_t* __restrict__ emb, const uint8_t* __restrict__ emb_s,
+                                                         float* __restrict__ x, int D) {
+    const int m = blockIdx.x;
+    const int nv = ps->nv;
+    const int tok = prompt[ps->p0 + min(m, nv - 1)];
+    for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = mx_element(emb, emb_s, (size_t)tok, D, i);
 }
 
 // one workgroup per chunk row: h = (x * 1/rms) * w (rms_kernel.cpp:12-22) or plain x (w == nullptr), as hi/lo.
@@ -160,9 +172,10 @@ struct PgIn {
 // SA_ > 0 (PIPE only): the weight (A) images get a ring of their own, SA_ stages deep (SA_ - 1 issued ahead), and
 // the activation (B) images a 2-stage ring (one ahead): the A bytes come from HBM (read once per chunk), the B bytes
 // from L2, so only A needs the deep prefetch, and B, the larger image, does not pay for it in LDS.
-template <int BM_, int WR_, int S_, int AT_ = 2, bool PIPE_ = false, int SA_ = 0>
+// KS_ (mxfp4 only, pgemm_mx_kernel): the depth a stage covers, 128 or 256 (0: 128).
+template <int BM_, int WR_, int S_, int AT_ = 2, bool PIPE_ = false, int SA_ = 0, int KS_ = 0>
 struct PgCfg {
-    static constexpr int BM = BM_, WR = WR_, S = S_, AT = AT_, SA = SA_;
+    static constexpr int BM = BM_, WR = WR_, S = S_, AT = AT_, SA = SA_, KS = KS_;
     static constexpr bool PIPE = PIPE_;
 };
 
@@ -186,7 +199,7 @@ struct PgGeo {
     static constexpr int B_BYTES = STAGE - A_BYTES;
     static constexpr int DPA = SA ? A_BYTES / 1024 / WAVES : 0, DPB = SA ? B_BYTES / 1024 / WAVES : 0;
     static constexpr size_t LDS = SA ? (size_t)SA * A_BYTES + (size_t)S * B_BYTES : (size_t)S * STAGE;
-    static_assert(A_ROW == 128 && WPT >= 1 && NDMA % WAVES == 0, "tiling");
+    static_assert(A_ROW == 128 && WPT >= 1 && NDMA % WAVES == 0 && Cfg::KS == 0, "tiling");
     static_assert(S >= 2 && (S - 1) * DPW <= 63, "ring depth (vmcnt counts 63 loads)");
     // (SA > S: A(s) must be issued in an earlier iteration than B(s), the wait below counts on it; SA == S computed
     // wrong sums in tools/pgemm_lab)
@@ -467,6 +480,245 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
     }
 }
 
+// ---- MXFP4 weights (mxfp4.h: data [N][K/2], e8m0 scales [N][K/32]). A stage covers 128 k (PgCfg::KS 0 / 128): a
+// weight row's slice is half a line (64 B, one 1-KiB piece = one 16-row image), a chunk row's hi / lo slice two lines,
+// the int8 geometry, so BM = 128 still fits two stages; or 256 k (KS 256): whole weight lines, but the activation
+// image doubles to 16 KiB per position tile and BM <= 64 (the activations, 32 x the weight bytes per k, are what the
+// ring carries). pg_pick<mxfp4> holds whichever tools/pgemm_lab measured faster per cell.
+// Scale scheme: one MFMA k-block is one MX block, so a (weight row, k-block) has one scale 2^e. The e2m1 codes are
+// decoded to fp16 exactly and UNSCALED (a byte LUT through v_perm: the fp16 of every e2m1 magnitude has a zero low
+// byte); the hi and lo MFMAs of a k-block run into a zeroed tile and acc = fma(tile, 2^e_row, acc) per C-fragment row
+// in fp32, where every e8m0 byte 1 .. 254 is a normal number: no fp16 overflow or flush at any block exponent.
+// The scale bytes travel through the ring too: global_load_lds_ubyte, a byte per lane into a dword of the stage's
+// scale image [k-block][tile row], so a lane's four C rows of a tile are one ds_read_b128 and 2^e is dword << 23.
+// Every wave issues the same number of pieces per stage (NPW: A, B and scale pieces), all LDS-DMA, all counted by
+// pg_wait_stages<NPW>; the kernel has no plain global load between its first DMA and its last wait.
+template <class Cfg>
+struct PgGeoMx {
+    static constexpr int BM = Cfg::BM, WR = Cfg::WR, S = Cfg::S, AT = Cfg::AT;
+    static constexpr int WAVES = 2 * WR, THREADS = 64 * WAVES, BN = 16 * AT * WR;
+    static constexpr int KS = Cfg::KS ? Cfg::KS : 128, KBS = KS / 32;
+    static constexpr int A_ROW = KS / 2, B_ROW = KS * 2;  // 64 B and 256 B, or 128 B and 512 B
+    static constexpr int A_IMG = 16 * A_ROW, B_IMG = 16 * B_ROW;
+    static constexpr int PT = BM / 16, WPT = PT / 2, NA = AT * WR;
+    static constexpr int A_BYTES = NA * A_IMG, B_BYTES = 2 * PT * B_IMG;
+    static constexpr int SC_BYTES = NA * 16 * KBS * 4;  // a dword per (tile row, k-block)
+    static constexpr int STAGE = A_BYTES + B_BYTES + SC_BYTES;
+    static constexpr int DPA = A_BYTES / 1024 / WAVES, DPB = B_BYTES / 1024 / WAVES, DPS = SC_BYTES / 256 / WAVES;
+    static constexpr int NPW = DPA + DPB + DPS;  // LDS-DMA instructions per wave and stage
+    static constexpr size_t LDS = (size_t)S * STAGE;
+    static_assert((KS == 128 || KS == 256) && WPT >= 1 && (AT == 2 || AT == 4), "tiling");
+    static_assert((A_BYTES / 1024) % WAVES == 0 && (B_BYTES / 1024) % WAVES == 0 && (SC_BYTES / 256) % WAVES == 0, "pieces");
+    static_assert(S >= 2 && S <= 8 && (S - 1) * NPW <= 63, "ring depth (vmcnt counts 63 loads)");
+    static_assert(Cfg::SA == 0, "mxfp4: one ring");
+    static_assert(LDS <= 160 * 1024, "LDS");
+};
+
+// chunk swizzle of a weight image row (64 or 128 B): a k-block's fragment read is 16 rows x 16 B, 4 B per lane
+__device__ __forceinline__ int pg_mx_swz(int row, int row_bytes) { return row_bytes == 64 ? (row >> 2) & 3 : (row >> 1) & 7; }
+
+// LDS-DMA of 64 single bytes: lane i's byte at gsrc lands, zero-extended, in the dword at LDS byte lds + 4 i
+__device__ __forceinline__ void pf_dma_u8(const void* gsrc, unsigned lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_ubyte %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(gsrc), "s"(lds)
+        : "memory");
+}
+
+// 8 e2m1 codes (element 2i in bits 3:0 of byte i) -> 8 fp16, exact and unscaled, in element order. The high byte
+// of the fp16 of magnitude code c is {00, 38, 3C, 3E, 40, 42, 44, 46}[c] (0, .5, 1, 1.5, 2, 3, 4, 6), the low byte 0.
+__device__ __forceinline__ u32x4 pg_fp4_to_f16(unsigned w) {
+    const unsigned lut_hi = 0x46444240u, lut_lo = 0x3E3C3800u;
+    unsigned ev = __builtin_amdgcn_perm(lut_hi, lut_lo, w & 0x07070707u);         // elements 0, 2, 4, 6
+    unsigned od = __builtin_amdgcn_perm(lut_hi, lut_lo, (w >> 4) & 0x07070707u);  // elements 1, 3, 5, 7
+    ev |= (w & 0x08080808u) << 4;  // the sign bits
+    od |= w & 0x80808080u;
+    u32x4 r;  // dword i = {00, ev_i, 00, od_i} (selector 0x0c: a zero byte)
+    r[0] = __builtin_amdgcn_perm(od, ev, 0x040c000cu);
+    r[1] = __builtin_amdgcn_perm(od, ev, 0x050c010cu);
+    r[2] = __builtin_amdgcn_perm(od, ev, 0x060c020cu);
+    r[3] = __builtin_amdgcn_perm(od, ev, 0x070c030cu);
+    return r;
+}
+
+struct PgInMx {
+    const uint8_t* W;   // [N][K / 2]
+    const uint8_t* Ws;  // [N][K / 32]
+    const __half* Bhi;
+    const __half* Blo;
+    int N, K, M;
+};
+
+template <class Epi, class Cfg>
+__global__ void __launch_bounds__(128 * Cfg::WR) pgemm_mx_kernel(PgInMx in, Epi epi, const PfState* __restrict__ ps) {
+    using Geo = PgGeoMx<Cfg>;
+    constexpr int KBS = Geo::KBS, BM = Geo::BM, WR = Geo::WR, S = Geo::S, AT = Geo::AT, NA = Geo::NA;
+    extern __shared__ __attribute__((aligned(1024))) char pg_smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wr = wave % WR, wp = wave / WR;
+    const int PB = in.M / BM;
+    const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;  // as pgemm_kernel
+    const int rb = (slot / PB) * 8 + xcd, pb = slot - (slot / PB) * PB;
+    const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
+    if (rb >= nrb) return;
+    // K % 64 == 0: the last stage may hold 64 k (128-k stages) or 64, 128 or 192 k (256-k stages), kt / 32 whole
+    // k-blocks. Its pieces past the row's end (data, scales and activations alike) reload the valid part of the
+    // stage instead (logical chunk c -> c % valid chunks: in bounds; never read), and only its valid k-blocks are
+    // multiplied.
+    const int ns = (in.K + Geo::KS - 1) / Geo::KS;
+    const int kt = in.K % Geo::KS;  // k of a short last stage (0: none)
+    const bool half_tail = kt != 0;
+    const int vkb = half_tail ? kt / 32 : KBS;  // its k-blocks: a 16-B weight chunk and a scale byte each
+    const int nt = in.N >> 4;
+    const unsigned ring = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)pg_smem;
+
+    // this wave's pieces: DPA weight pieces (16 rows x 64 B with the 16-B chunks XORed with row / 4, or 8 rows x
+    // 128 B XORed with row / 2: the fragment reads, 4 B per lane, then cover 64 banks), DPB activation pieces (4 rows
+    // x 256 B or 2 x 512 B, chunks XORed with the row), DPS scale pieces
+    const char* src[Geo::NPW];
+    int adv[Geo::NPW], back[Geo::NPW];
+    unsigned dsto[Geo::NPW];
+#pragma unroll
+    for (int j = 0; j < Geo::NPW; ++j) {
+        if (j < Geo::DPA) {
+            constexpr int cpr = Geo::A_ROW / 16;
+            const int off = (wave * Geo::DPA + j) * 1024;
+            const int ti = off / Geo::A_IMG;  // weight tile of the block
+            const int r = (off % Geo::A_IMG) / Geo::A_ROW + lane / cpr;
+            const int c = (lane % cpr) ^ pg_mx_swz(r, Geo::A_ROW);
+            const int row = epi.row(min(rb * NA + ti, nt - 1), r);
+            src[j] = reinterpret_cast<const char*>(in.W) + (size_t)row * (in.K / 2) + c * 16;
+            adv[j] = Geo::A_ROW;
+            back[j] = (c - c % vkb) * 16;
+            dsto[j] = (unsigned)off;
+        } else if (j < Geo::DPA + Geo::DPB) {
+            constexpr int cpr = Geo::B_ROW / 16;
+            const int o2 = (wave * Geo::DPB + j - Geo::DPA) * 1024;
+            const int u = o2 / Geo::B_IMG, pt = u >> 1;
+            const int r = (o2 % Geo::B_IMG) / Geo::B_ROW + lane / cpr;
+            const int c = (lane % cpr) ^ pg_swz(r, Geo::B_ROW);
+            const __half* B = (u & 1) ? in.Blo : in.Bhi;
+            const int m = pb * BM + pt * 16 + r;
+            src[j] = reinterpret_cast<const char*>(B) + (size_t)m * in.K * 2 + c * 16;
+            adv[j] = Geo::B_ROW;
+            back[j] = (c - c % (4 * vkb)) * 16;  // four 16-B chunks of 8 fp16 per k-block
+            dsto[j] = (unsigned)(Geo::A_BYTES + o2);
+        } else {  // dword d of the scale image [k-block][tile row]
+            const int q = wave * Geo::DPS + j - Geo::DPA - Geo::DPB;
+            const int d = q * 64 + lane;
+            const int kb = d / (NA * 16), tr = d - kb * (NA * 16);
+            const int row = epi.row(min(rb * NA + (tr >> 4), nt - 1), tr & 15);
+            src[j] = reinterpret_cast<const char*>(in.Ws) + (size_t)row * (in.K / kMxBlock) + kb;
+            adv[j] = KBS;
+            back[j] = kb - kb % vkb;
+            dsto[j] = (unsigned)(Geo::A_BYTES + Geo::B_BYTES + q * 256);
+        }
+    }
+    auto issue = [&](int s) {
+        const unsigned dst = ring + (unsigned)((s % S) * Geo::STAGE);
+        const bool tail = half_tail && s == ns - 1;
+#pragma unroll
+        for (int j = 0; j < Geo::NPW; ++j) {
+            const char* g = src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0);
+            if (j < Geo::DPA + Geo::DPB)
+                pf_dma(g, dst + dsto[j]);
+            else
+                pf_dma_u8(g, dst + dsto[j]);
+        }
+    };
+    pf_float4 acc[AT][Geo::WPT];
+#pragma unroll
+    for (int a = 0; a < AT; ++a)
+#pragma unroll
+        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int kg = lane >> 4, r16 = lane & 15;
+    const int sa = pg_mx_swz(r16, Geo::A_ROW), sb = pg_swz(r16, Geo::B_ROW);
+    for (int s = 0; s < S - 1 && s < ns; ++s) issue(s);
+    for (int s = 0; s < ns; ++s) {
+        // this wave's NPW pieces of stage s landed: it issued whole stages only, NPW LDS-DMAs each and nothing else
+        // that the counter counts, so at most min(S - 2, ns - 1 - s) later stages are behind them in order
+        pg_wait_stages<Geo::NPW>(min(S - 2, ns - 1 - s));
+        __builtin_amdgcn_s_barrier();  // every wave's pieces of s landed; every wave has read s - 1 (its MFMAs, which
+                                       // wait for their operands, precede this barrier in program order)
+        if (s + S - 1 < ns) issue(s + S - 1);
+        const char* st = pg_smem + (size_t)(s % S) * Geo::STAGE;
+        const char* stb = st + Geo::A_BYTES;
+        const char* sts = stb + Geo::B_BYTES;
+        const int kbs = s == ns - 1 ? vkb : KBS;  // wave-uniform
+#pragma unroll
+        for (int kb = 0; kb < KBS; ++kb) {
+            if (kb >= kbs) break;
+            u32x4 af[AT], sc[AT], bh[Geo::WPT], bl[Geo::WPT];
+#pragma unroll
+            for (int a = 0; a < AT; ++a) {
+                const int ti = wr * AT + a;
+                // k 32 kb + 8 kg .. +8 of row r16: chunk kb, bytes 4 kg .. +4
+                const unsigned w = *reinterpret_cast<const unsigned*>(st + ti * Geo::A_IMG + r16 * Geo::A_ROW +
+                                                                      ((kb ^ sa) * 16) + 4 * kg);
+                af[a] = pg_fp4_to_f16(w);
+                // the scale dwords of this lane's C rows 4 kg .. +4 of the tile
+                sc[a] = *reinterpret_cast<const u32x4*>(sts + ((kb * NA + ti) * 16 + 4 * kg) * 4);
+            }
+#pragma unroll
+            for (int b = 0; b < Geo::WPT; ++b) {
+                const int pt = wp * Geo::WPT + b;
+                const char* img = stb + (2 * pt) * Geo::B_IMG + r16 * Geo::B_ROW + ((4 * kb + kg) ^ sb) * 16;
+                bh[b] = *reinterpret_cast<const u32x4*>(img);
+                bl[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
+            }
+            pf_float4 tmp[AT][Geo::WPT];
+#pragma unroll
+            for (int b = 0; b < Geo::WPT; ++b)
+#pragma unroll
+                for (int a = 0; a < AT; ++a) tmp[a][b] = pf_mfma(af[a], bh[b], pf_float4{0.0f, 0.0f, 0.0f, 0.0f});
+#pragma unroll
+            for (int b = 0; b < Geo::WPT; ++b)
+#pragma unroll
+                for (int a = 0; a < AT; ++a) tmp[a][b] = pf_mfma(af[a], bl[b], tmp[a][b]);
+#pragma unroll
+            for (int a = 0; a < AT; ++a) {
+                float f[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(sc[a][e] << 23);  // 2^(byte - 127)
+#pragma unroll
+                for (int b = 0; b < Geo::WPT; ++b)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[a][b][e] = fmaf(tmp[a][b][e], f[e], acc[a][b][e]);
+            }
+        }
+    }
+    const int i0 = 4 * (lane >> 4);
+#pragma unroll
+    for (int a = 0; a < AT; ++a) {
+        const int t = rb * NA + wr * AT + a;
+        if (t >= nt) continue;
+#pragma unroll
+        for (int b = 0; b < Geo::WPT; ++b) {
+            const int m = pb * BM + (wp * Geo::WPT + b) * 16 + r16;
+            const float v[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
+            epi.store(t, i0, m, v, ps);
+        }
+    }
+}
+
+template <class Epi, class Cfg>
+hipError_t launch_pgemm_mx(const PgInMx& in, const Epi& epi, const PfState* ps, hipStream_t s) {
+    using Geo = PgGeoMx<Cfg>;
+    const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
+    const int nrb8 = (nrb + 7) / 8 * 8;
+    const dim3 grid(nrb8 * (in.M / Geo::BM));
+    hipLaunchKernelGGL((pgemm_mx_kernel<Epi, Cfg>), grid, dim3(Geo::THREADS), Geo::LDS, s, in, epi, ps);
+    return hipGetLastError();
+}
+
 // ---- epilogues. Tiles hold 4-row groups {first(u), first(u + 1), second(u), second(u + 1)} where a pair is a
 // RoPE pair {d, d + hd/2} (q/k/v) or {gate u, up u}, so each lane's 4 rows are 2 complete pairs.
 template <typename KT>
@@ -591,8 +843,12 @@ hipError_t launch_pgemm(const PgIn<WT>& in, const Epi& epi, const PfState* ps, h
 
 template <class Epi, class Cfg, typename WT>
 hipError_t pgemm_allow_lds() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_kernel<Epi, Cfg, WT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeo<Cfg, WT>::LDS);
+    if constexpr (is_mx<WT>::value)
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_mx_kernel<Epi, Cfg>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeoMx<Cfg>::LDS);
+    else
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_kernel<Epi, Cfg, WT>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeo<Cfg, WT>::LDS);
 }
 
 // The GEMM tiling (PgCfg<BM, WR, S, AT, PIPE, SA>) per weight type, projection role and chunk size: the fastest of
@@ -604,7 +860,18 @@ hipError_t pgemm_allow_lds() {
 // kernel-level entry point (sli_prefill_gemm) all pick through it.
 template <typename WT, class F>
 int pg_pick(int M, int role, F&& f) {
-    if constexpr (std::is_same<WT, int8_t>::value) {
+    if constexpr (is_mx<WT>::value) {
+        // pgemm_mx_kernel (PIPE and SA are not knobs of it): the fastest of tools/pgemm_lab's LAB_MX sweep per 7B
+        // shape and chunk size, weights rotated over four copies (profiles/mxfp4_pgemm_lab.txt). 256-k stages tie the
+        // 128-k ones at BM = 32 (within 1 %), lose at BM = 64 (148 KiB: one workgroup per CU) and cannot take BM = 128
+        // or 8 waves at BM = 64, the fastest q/k/v and gate/up tilings, so every cell is a 128-k one; wo / down (N = D,
+        // few row blocks) want 32-row chunk blocks.
+        if (M == 32) return f(PgCfg<32, 2, 4, 2>{});
+        if (role == 2) return M == 256 ? f(PgCfg<32, 4, 4, 2>{}) : f(PgCfg<32, 2, 4, 2>{});
+        if (role == 1) return M == 128 ? f(PgCfg<128, 4, 2, 2>{}) : f(PgCfg<64, 4, 3, 2>{});
+        if (M == 256) return f(PgCfg<128, 4, 2, 2>{});
+        return M == 128 ? f(PgCfg<64, 4, 3, 2>{}) : f(PgCfg<32, 4, 4, 2>{});
+    } else if constexpr (std::is_same<WT, int8_t>::value) {
         if (M == 32) return f(PgCfg<32, 2, 4, 2, true>{});
         if (role == 2) return M == 256 ? f(PgCfg<64, 2, 2, 2, true>{}) : f(PgCfg<32, 2, 4, 2, true>{});
         if (role == 1) return M == 128 ? f(PgCfg<128, 4, 2, 2, true>{}) : f(PgCfg<64, 4, 2, 2, true>{});

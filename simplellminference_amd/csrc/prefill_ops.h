@@ -33,35 +33,46 @@ static bool pf_chunk_size(int M) {
 static bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 template <class Epi, typename WT>
-static int pf_gemm_launch(const void* w, const void* hi, const void* lo, int N, int K, int M, int role, const Epi& e,
+static int pf_gemm_launch(const void* w, const void* ws, const void* hi, const void* lo, int N, int K, int M, int role, const Epi& e,
                           const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
     SLI_HIP((pg_allow_lds_all<Epi, WT>()));
-    const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M};
     return pg_pick<WT>(M, role, [&](auto cfg) -> int {
         using Cfg = decltype(cfg);
-        if (tiling) *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA};
-        SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
+        if constexpr (is_mx<WT>::value) {  // ws: the e8m0 block scales
+            if (tiling)
+                *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeoMx<Cfg>::KS};
+            const PgInMx in{(const uint8_t*)w, (const uint8_t*)ws, (const __half*)hi, (const __half*)lo, N, K, M};
+            SLI_HIP((launch_pgemm_mx<Epi, Cfg>(in, e, ps, s)));
+        } else {
+            if (tiling)
+                *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeo<Cfg, WT>::KS};
+            const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M};
+            SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
+        }
         return SLI_OK;
     });
 }
 
+// rs: int8 row scales for the epilogue (nullable); mxfp4: ws, the block scales for the GEMM, and no row scale
 template <typename WT>
-static int pf_gemm_role(const void* w, const float* rs, const void* hi, const void* lo, int N, int K, int M,
+static int pf_gemm_role(const void* w, const float* rs_in, const void* hi, const void* lo, int N, int K, int M,
                         const sli_pgemm_epilogue& e, const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
+    const void* ws = is_mx<WT>::value ? (const void*)rs_in : nullptr;
+    const float* rs = is_mx<WT>::value ? nullptr : rs_in;
     if (e.role == 0) {
         if (e.kv_dtype == SLI_DT_F16) {
             const PgEpiQKV<__half> q{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
-            return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, hi, lo, N, K, M, 0, q, ps, tiling, s);
+            return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
         }
         const PgEpiQKV<float> q{e.q, (float*)e.kc, (float*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
-        return pf_gemm_launch<PgEpiQKV<float>, WT>(w, hi, lo, N, K, M, 0, q, ps, tiling, s);
+        return pf_gemm_launch<PgEpiQKV<float>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
     }
     if (e.role == 1) {
         const PgEpiSwiGLU g{(__half*)e.ahi, (__half*)e.alo, rs, e.inter, e.act_mode};
-        return pf_gemm_launch<PgEpiSwiGLU, WT>(w, hi, lo, N, K, M, 1, g, ps, tiling, s);
+        return pf_gemm_launch<PgEpiSwiGLU, WT>(w, ws, hi, lo, N, K, M, 1, g, ps, tiling, s);
     }
     const PgEpiResid r{e.y, e.resid, rs, N, e.ld};
-    return pf_gemm_launch<PgEpiResid, WT>(w, hi, lo, N, K, M, 2, r, ps, tiling, s);
+    return pf_gemm_launch<PgEpiResid, WT>(w, ws, hi, lo, N, K, M, 2, r, ps, tiling, s);
 }
 
 }  // namespace sli
@@ -83,20 +94,18 @@ int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, i
     return SLI_OK;
 }
 
-int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
-                     int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
-                     sli_pgemm_tiling* tiling, sli_stream_t stream) {
-    SLI_CHECK(w && hi && lo && epi && state, SLI_ERR_ARG, "sli_prefill_gemm: null pointer");
-    SLI_CHECK(w_dtype == SLI_DT_F16 || w_dtype == SLI_DT_I8, SLI_ERR_ARG,
-              "sli_prefill_gemm: fp16 or int8 weights (fp32 and MXFP4 have no GEMM prefill)");
+// the checks of both GEMM entries and the launch; ws: mxfp4 block scales (w_dtype SLI_DT_MXFP4) or int8 row scales
+static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
+                         int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                         sli_pgemm_tiling* tiling, sli_stream_t stream) {
     SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_gemm: M must be 32, 64, 128 or 256");
     SLI_CHECK(K >= 64 && K % 64 == 0, SLI_ERR_ARG, "sli_prefill_gemm: K must be a multiple of 64");
     SLI_CHECK(N >= 16 && N % 16 == 0, SLI_ERR_ARG, "sli_prefill_gemm: N must be a multiple of 16");
     SLI_CHECK((int64_t)N * K < ((int64_t)1 << 40) && K <= (1 << 20), SLI_ERR_ARG, "sli_prefill_gemm: shape too large");
     SLI_CHECK(p0 >= 0 && p0 <= (1 << 30) && nv >= 1 && nv <= M, SLI_ERR_ARG,
               "sli_prefill_gemm: p0 must be >= 0 and nv in [1, M]");
-    SLI_CHECK(al16(w) && al16(w_row_scale) && al16(hi) && al16(lo) && (uintptr_t)state % 8 == 0, SLI_ERR_ARG,
-              "sli_prefill_gemm: 16-byte alignment");
+    SLI_CHECK(al16(w) && (w_dtype == SLI_DT_MXFP4 || al16(ws)) && al16(hi) && al16(lo) && (uintptr_t)state % 8 == 0,
+              SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
     const sli_pgemm_epilogue& e = *epi;
     switch (e.role) {
         case 0:
@@ -127,8 +136,26 @@ int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const
     hipStream_t s = as_stream(stream);
     if (int rc = pf_set_state(state, p0, nv, s)) return rc;
     const PfState* ps = (const PfState*)state;
-    if (w_dtype == SLI_DT_I8) return pf_gemm_role<int8_t>(w, w_row_scale, hi, lo, N, K, M, e, ps, tiling, s);
-    return pf_gemm_role<__half>(w, w_row_scale, hi, lo, N, K, M, e, ps, tiling, s);
+    const float* rs = (const float*)ws;
+    if (w_dtype == SLI_DT_MXFP4) return pf_gemm_role<mxfp4>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
+    if (w_dtype == SLI_DT_I8) return pf_gemm_role<int8_t>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
+    return pf_gemm_role<__half>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
+}
+
+int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
+                     int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                     sli_pgemm_tiling* tiling, sli_stream_t stream) {
+    SLI_CHECK(w && hi && lo && epi && state, SLI_ERR_ARG, "sli_prefill_gemm: null pointer");
+    SLI_CHECK(w_dtype == SLI_DT_F16 || w_dtype == SLI_DT_I8, SLI_ERR_ARG,
+              "sli_prefill_gemm: fp16 or int8 weights (fp32 and MXFP4 have no GEMM prefill)");
+    return pf_gemm_entry(w, w_dtype, w_row_scale, hi, lo, N, K, M, p0, nv, epi, state, tiling, stream);
+}
+
+int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N, int32_t K,
+                           int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                           sli_pgemm_tiling* tiling, sli_stream_t stream) {
+    SLI_CHECK(data && scales && hi && lo && epi && state, SLI_ERR_ARG, "sli_prefill_gemm_mxfp4: null pointer");
+    return pf_gemm_entry(data, SLI_DT_MXFP4, scales, hi, lo, N, K, M, p0, nv, epi, state, tiling, stream);
 }
 
 int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,

@@ -20,6 +20,7 @@ from ._lib import DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
 
 _DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8,
            "mxfp4": DT_MXFP4, "fp4": DT_MXFP4}
+_PREFILL_MODES = {"auto": 0, "gemm": 1, "decode": 2}  # SLI_PREFILL_*
 
 
 @dataclass(frozen=True)
@@ -272,6 +273,12 @@ class LlamaModel:
         """'mfma' (chunked MFMA GEMMs) or 'decode' (teacher-forced decode steps): sli_model_prefill_path."""
         return "mfma" if _lib.load().sli_model_prefill_path(self._h) == 1 else "decode"
 
+    def set_prefill(self, mode: str):
+        """Which path the next prefill takes (sli_model_set_prefill): 'auto' (the GEMM prefill where the model can
+        take it, MXFP4 weights excepted), 'gemm' (the chunked MFMA prefill; an error where the model cannot take it)
+        or 'decode' (teacher-forced decode steps). prefill_path() reports the outcome."""
+        call("sli_model_set_prefill", self._h, _PREFILL_MODES[mode])
+
     def fused_qkv_attn(self) -> int:
         """1 when the decode step runs q/k/v + attention as one launch per layer, 0 otherwise:
         sli_model_fused_qkv_attn."""
@@ -453,6 +460,13 @@ class TPGroup:
              lens.ctypes.data_as(ctypes.c_void_p), ld, max_length, toks.ctypes.data_as(ctypes.c_void_p),
              logits.ctypes.data_as(ctypes.c_void_p) if want_logits else None)
         return (toks, logits.transpose(1, 0, 2).copy()) if want_logits else toks
+
+    def set_prefill(self, mode: str):
+        """LlamaModel.set_prefill for every rank (sli_tp_group_set_prefill)."""
+        call("sli_tp_group_set_prefill", self._g, _PREFILL_MODES[mode])
+
+    def prefill_path(self) -> str:
+        return self.ranks[0].prefill_path()
 
     def prefill(self, prompt_ids):
         """sli_tp_group_prefill: the ranks' prefill chunks in lockstep (batch-1 groups)."""

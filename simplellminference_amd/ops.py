@@ -190,7 +190,27 @@ def prefill_norm_split(x, w, eps: float):
     return hi, lo
 
 
-def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi):
+def _prefill_gemm_mxfp4(w, scales, hi, lo, p0, nv, epi):
+    """sli_prefill_gemm_mxfp4: w uint8 [N, K/2] (two e2m1 codes per byte), scales uint8 [N, K/32] (e8m0)."""
+    N, K = w.shape[0], w.shape[1] * 2
+    M = hi.shape[0]
+    if w.dtype != torch.uint8 or scales.dtype != torch.uint8 or scales.shape != (N, K // 32) or K % 32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if hi.shape != (M, K) or lo.shape != (M, K) or hi.dtype != torch.float16 or lo.dtype != torch.float16:
+        raise ValueError("Tensor with Wrong Dim!")
+    state = _pf_state(w.device)
+    _dev(w, scales, hi, lo)
+    tl = _lib.PgemmTiling()
+    call("sli_prefill_gemm_mxfp4", _p(w), _p(scales), _p(hi), _p(lo), N, K, M, p0, nv, ctypes.byref(epi), _p(state),
+         ctypes.byref(tl), _s())
+    return {n: getattr(tl, n) for n, _ in tl._fields_}
+
+
+def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi, scales=None):
+    if scales is not None:
+        if row_scale is not None:
+            raise ValueError("prefill GEMM: MXFP4 weights (scales=) take no row_scale")
+        return _prefill_gemm_mxfp4(w, scales, hi, lo, p0, nv, epi)
     N, K = w.shape
     M = hi.shape[0]
     if hi.shape != (M, K) or lo.shape != (M, K) or hi.dtype != torch.float16 or lo.dtype != torch.float16:
@@ -206,10 +226,10 @@ def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi):
 
 
 def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, p0: int, nv: int,
-                     row_scale=None):
+                     row_scale=None, scales=None):
     """One pgemm_kernel launch with the q/k/v epilogue: W [(hq + 2 hkv) hd, K]; q [M, hq hd] fp32 gets every chunk
     row; kc / vc, one layer's cache [hkv, T, hd] (f16 or f32), get rows p0 + m for m < nv, p0 + m < T. Returns the
-    tiling that ran."""
+    tiling that ran. scales (uint8 [N, K/32]): W is MXFP4, uint8 [N, K/2] (pgemm_mx_kernel); no row_scale then."""
     if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
         raise ValueError("Tensor with Wrong Dim!")
     T = kc.shape[1]
@@ -219,10 +239,10 @@ def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: 
     e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
                            kv_dtype=_DT[kc.dtype], sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
                            hd=hd, T=T)
-    return _prefill_gemm(w, row_scale, hi, lo, p0, nv, e)
+    return _prefill_gemm(w, row_scale, hi, lo, p0, nv, e, scales)
 
 
-def prefill_gemm_gate_up(w, hi, lo, ahi, alo, act_mode: int = 0, row_scale=None):
+def prefill_gemm_gate_up(w, hi, lo, ahi, alo, act_mode: int = 0, row_scale=None, scales=None):
     """One pgemm_kernel launch with the SwiGLU epilogue: W [2 inter, K] = [gate; up]; ahi / alo [M, inter] fp16."""
     inter = w.shape[0] // 2
     if ahi.shape != (hi.shape[0], inter) or alo.shape != ahi.shape:
@@ -230,17 +250,17 @@ def prefill_gemm_gate_up(w, hi, lo, ahi, alo, act_mode: int = 0, row_scale=None)
     _dev(ahi, alo)
     e = _lib.PgemmEpilogue(role=PF_ROLE_GATE_UP, ahi=ahi.data_ptr(), alo=alo.data_ptr(), inter=inter,
                            act_mode=act_mode)
-    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e)
+    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
 
 
-def prefill_gemm_resid(w, hi, lo, y, resid=None, row_scale=None):
+def prefill_gemm_resid(w, hi, lo, y, resid=None, row_scale=None, scales=None):
     """One pgemm_kernel launch with the wo / down epilogue: y [M, ld] = (resid or 0) + W (hi + lo) * row scale."""
     if y.shape[0] != hi.shape[0] or (resid is not None and resid.shape != y.shape):
         raise ValueError("Tensor with Wrong Dim!")
     _dev(y, resid)
     e = _lib.PgemmEpilogue(role=PF_ROLE_RESID, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
                            ld=y.shape[1])
-    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e)
+    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
 
 
 def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int):

@@ -191,9 +191,142 @@ static void sweep(const Shape& sh, int M) {
     release(b);
 }
 
+// ---- MXFP4 (pgemm_mx_kernel): data [N][K/2], scale bytes 120 .. 126, 128-k and 256-k stages
+struct BufsMx {
+    std::vector<uint8_t*> Wc, Sc;  // rotated copies, as Bufs::Wc
+    __half *hi, *lo;
+    float* y;
+    PfState* ps;
+    std::vector<uint8_t> hW, hS;
+    std::vector<__half> hhi, hlo;
+};
+
+static double mx_host(const BufsMx& b, int K, int row, int k) {
+    static const double mag[8] = {0, .5, 1, 1.5, 2, 3, 4, 6};
+    const uint8_t byte = b.hW[(size_t)row * (K / 2) + k / 2];
+    const unsigned c = (k & 1) ? byte >> 4 : byte & 15;
+    return ((c & 8) ? -mag[c & 7] : mag[c & 7]) * ldexp(1.0, (int)b.hS[(size_t)row * (K / 32) + k / 32] - 127);
+}
+
+static void make_mx(BufsMx& b, int N, int K, int M) {
+    uint64_t s = 999 + N + K;
+    b.hW.resize((size_t)N * K / 2);
+    b.hS.resize((size_t)N * K / 32);
+    for (auto& w : b.hW) w = (uint8_t)rng(s);
+    for (auto& w : b.hS) w = (uint8_t)(120 + rng(s) % 7);
+    b.hhi.resize((size_t)M * K);
+    b.hlo.resize((size_t)M * K);
+    for (size_t i = 0; i < b.hhi.size(); ++i) {
+        const float v = ((int)(rng(s) % 200001) - 100000) * 1e-5f;
+        b.hhi[i] = __float2half(v);
+        b.hlo[i] = __float2half(v - __half2float(b.hhi[i]));
+    }
+    const int ncopy = getenv("LAB_HOT") ? 1 : 4;
+    for (int c = 0; c < ncopy; ++c) {
+        uint8_t *w, *sc;
+        CK(hipMalloc(&w, b.hW.size()));
+        CK(hipMalloc(&sc, b.hS.size()));
+        CK(hipMemcpy(w, b.hW.data(), b.hW.size(), hipMemcpyHostToDevice));
+        CK(hipMemcpy(sc, b.hS.data(), b.hS.size(), hipMemcpyHostToDevice));
+        b.Wc.push_back(w);
+        b.Sc.push_back(sc);
+    }
+    CK(hipMalloc(&b.hi, 2 * b.hhi.size()));
+    CK(hipMalloc(&b.lo, 2 * b.hlo.size()));
+    CK(hipMalloc(&b.y, sizeof(float) * (size_t)M * N));
+    CK(hipMalloc(&b.ps, sizeof(PfState)));
+    CK(hipMemcpy(b.hi, b.hhi.data(), 2 * b.hhi.size(), hipMemcpyHostToDevice));
+    CK(hipMemcpy(b.lo, b.hlo.data(), 2 * b.hlo.size(), hipMemcpyHostToDevice));
+    PfState p{0, M};
+    CK(hipMemcpy(b.ps, &p, sizeof p, hipMemcpyHostToDevice));
+}
+
+template <class Cfg>
+static void run_mx(const char* tag, BufsMx& b, const Shape& sh, int M) {
+    using Geo = PgGeoMx<Cfg>;
+    if (M % Geo::BM) return;
+    CK((pgemm_allow_lds<PgEpiResid, Cfg, mxfp4>()));
+    PgInMx in{b.Wc[0], b.Sc[0], b.hi, b.lo, sh.N, sh.K, M};
+    PgEpiResid e{b.y, nullptr, nullptr, sh.N, sh.N};
+    CK(hipMemset(b.y, 0, sizeof(float) * (size_t)M * sh.N));
+    CK((launch_pgemm_mx<PgEpiResid, Cfg>(in, e, b.ps, 0)));
+    CK(hipDeviceSynchronize());
+    std::vector<float> y((size_t)M * sh.N);
+    CK(hipMemcpy(y.data(), b.y, sizeof(float) * y.size(), hipMemcpyDeviceToHost));
+    double maxrel = 0.0;
+    uint64_t s = 777;
+    for (int i = 0; i < 64; ++i) {
+        const int m = rng(s) % M, row = rng(s) % sh.N;
+        double ref = 0.0, mag = 0.0;
+        for (int k = 0; k < sh.K; ++k) {
+            const double x = (double)h2f(b.hhi[(size_t)m * sh.K + k]) + (double)h2f(b.hlo[(size_t)m * sh.K + k]);
+            const double w = mx_host(b, sh.K, row, k);
+            ref += w * x;
+            mag += fabs(w * x);
+        }
+        maxrel = fmax(maxrel, fabs(y[(size_t)m * sh.N + row] - ref) / (mag + 1e-30));
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    const int iters = 20;
+    CK(hipEventRecord(e0, 0));
+    for (int i = 0; i < iters; ++i) {
+        PgInMx ic = in;
+        ic.W = b.Wc[i % b.Wc.size()];
+        ic.Ws = b.Sc[i % b.Sc.size()];
+        CK((launch_pgemm_mx<PgEpiResid, Cfg>(ic, e, b.ps, 0)));
+    }
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    const double us = 1000.0 * ms / iters;
+    const double tf = 4.0 * sh.N * sh.K * (double)M / (us * 1e-6) / 1e12;
+    const int nrb = (sh.N + Geo::BN - 1) / Geo::BN;
+    printf("%-5s mxfp4  %-26s grid %5d lds %6zu  %8.1f us  %6.1f TF issued  relerr %.1e\n", sh.name, tag,
+           nrb * (M / Geo::BM), Geo::LDS, us, tf, maxrel);
+    fflush(stdout);
+    CK(hipEventDestroy(e0));
+    CK(hipEventDestroy(e1));
+}
+
+#define RUNX(BM, WR, S, AT, KS) \
+    run_mx<PgCfg<BM, WR, S, AT, false, 0, KS>>("BM" #BM " WR" #WR " S" #S " AT" #AT " KS" #KS, b, sh, M)
+
+static void sweep_mx(const Shape& sh, int M) {
+    BufsMx b;
+    make_mx(b, sh.N, sh.K, M);
+    RUNX(128, 4, 2, 2, 128);
+    RUNX(128, 2, 2, 2, 128);
+    RUNX(64, 4, 2, 2, 128);
+    RUNX(64, 4, 3, 2, 128);
+    RUNX(64, 2, 2, 2, 128);
+    RUNX(64, 2, 3, 2, 128);
+    RUNX(64, 2, 4, 2, 128);
+    RUNX(64, 2, 2, 4, 128);
+    RUNX(32, 2, 4, 2, 128);
+    RUNX(32, 4, 4, 2, 128);
+    RUNX(64, 2, 2, 2, 256);
+    RUNX(32, 2, 2, 2, 256);
+    RUNX(32, 2, 3, 2, 256);
+    RUNX(32, 4, 2, 2, 256);
+    RUNX(32, 4, 3, 2, 256);
+    for (auto* p : b.Wc) CK(hipFree(p));
+    for (auto* p : b.Sc) CK(hipFree(p));
+    CK(hipFree(b.hi));
+    CK(hipFree(b.lo));
+    CK(hipFree(b.y));
+    CK(hipFree(b.ps));
+}
+
 int main(int argc, char** argv) {
     const int M = argc > 1 ? atoi(argv[1]) : 256;
     const Shape shapes[] = {{"qkv", 12288, 4096}, {"gu", 22016, 4096}, {"wo", 4096, 4096}, {"down", 4096, 11008}};
+    if (getenv("LAB_MX")) {  // the MXFP4 kernel alone
+        for (const Shape& sh : shapes) sweep_mx(sh, M);
+        return 0;
+    }
     for (const Shape& sh : shapes) sweep<__half>(sh, M);
     for (const Shape& sh : shapes) sweep<int8_t>(sh, M);
     return 0;
