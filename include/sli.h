@@ -101,6 +101,16 @@ size_t sli_matmul_batch_workspace_bytes(int32_t rows, int32_t cols, int32_t batc
 int sli_matmul_batch(const float* x, const void* w, int w_dtype, float* y, int32_t rows, int32_t cols, int32_t batch,
                      void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
+/* The same projection from int8 weights (per-row symmetric): y[b][r] = (sum_c x[b][c] * W[r][c]) * w_row_scale[r]
+ * (NULL scale: 1). W row-major int8 [rows][cols]; the bytes become the MFMA's fp16 A operand exactly in registers,
+ * the row scale multiplies the finished fp32 row sum. tiled = 0 streams W as given; tiled = 1 first re-lays W into
+ * the model's fragment layout inside the workspace (the tile kernel and row map of the batched model's plain-row
+ * projections) and streams that image. Checks and statuses as sli_matmul_batch; the workspace size depends on
+ * `tiled` (0 = unsupported shape; no device needed). */
+size_t sli_matmul_batch_i8_workspace_bytes(int32_t rows, int32_t cols, int32_t batch, int32_t tiled);
+int sli_matmul_batch_i8(const float* x, const void* w, const float* w_row_scale, float* y, int32_t rows, int32_t cols,
+                        int32_t batch, int32_t tiled, void* workspace, size_t workspace_bytes, sli_stream_t stream);
+
 /* kernel::rmsnorm_kernel_cuda (rms_kernel.cuh:6-7; CPU rms_kernel.cpp:5-23): y = x / sqrt(mean(x^2)+eps) * w.
  * Single-workgroup reduction: no atomics, no per-call allocation (the reference allocates + memsets a
  * {1} tensor per call and races across blocks, rms_kernel.cu:29-33,48-51). */
@@ -151,7 +161,7 @@ int sli_argmax(const float* logits, int32_t n, int32_t* out_dev, sli_stream_t st
 typedef struct {
     int32_t vocab, dim, n_heads, n_kv_heads, head_dim, ffn, n_layers, max_len;
     float eps, theta;
-    int32_t w_dtype;  /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_I8 (per-row symmetric) / SLI_DT_MXFP4 (fp32 weights handed to
+    int32_t w_dtype;  /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_I8 (per-row symmetric; any batch) / SLI_DT_MXFP4 (fp32 weights handed to
                          the model are quantised by the rule at sli_quant_mxfp4; batch 1 only, the launch graph only,
                          no GEMM prefill; dim, the local ffn width and the local q width multiples of 32, else
                          SLI_ERR_SHAPE) */
@@ -160,7 +170,8 @@ typedef struct {
     int32_t tp_rank, tp_size;
     int32_t device;
     int32_t batch;    /* sequences decoding in lockstep, <= 8 (0 or 1: batch 1, the reference's case).
-                         batch > 1 runs the projections on MFMA (sli_matmul_batch) and needs fp16 weights */
+                         batch > 1 runs the projections on MFMA (sli_matmul_batch, sli_matmul_batch_i8) and needs
+                         fp16 or int8 weights */
 } sli_model_config;
 
 typedef struct sli_model sli_model;

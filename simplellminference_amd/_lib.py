@@ -77,6 +77,8 @@ _SIGS = {
     "sli_matmul_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_vp]),
     "sli_matmul_batch_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "sli_matmul_batch": (c_int, [c_vp, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "sli_matmul_batch_i8_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "sli_matmul_batch_i8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "sli_rmsnorm": (c_int, [c_vp, c_vp, c_vp, c_i32, c_f, c_vp]),
     "sli_rope_cache": (c_int, [c_i32, c_i32, c_vp, c_vp, c_f, c_vp]),
     "sli_rope": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
@@ -182,6 +184,7 @@ def call(name: str, *args) -> int:
     rc = getattr(load(), name)(*args)
     if isinstance(rc, int) and name not in ("sli_version", "sli_mha_workspace_bytes", "sli_comm_id_bytes",
                                                  "sli_model_comm_handle_bytes",
-                                                 "sli_matmul_batch_workspace_bytes"):
+                                                 "sli_matmul_batch_workspace_bytes",
+                                                 "sli_matmul_batch_i8_workspace_bytes"):
         check(rc, name)
     return rc

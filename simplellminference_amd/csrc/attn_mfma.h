@@ -92,7 +92,6 @@ __device__ __forceinline__ uint2 am_tr_read(unsigned lds_addr) {
     return v;
 }
 typedef _Float16 am_half8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float am_float4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ am_float4 am_mfma(const u32x4& a, const u32x4& b, am_float4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(am_half8, a), __builtin_bit_cast(am_half8, b), c,

@@ -21,7 +21,19 @@
 //   * splits > 1: per-tile partials are published write-through (sc1) and the group's last-arriving
 //     workgroup sums them in split order (deterministic) and runs the epilogue (the hand-off recipe of
 //     attention.h, MI355X_MICROARCH.md).
+//
+// int8 weights (WT = int8_t, per-row symmetric): the same kernel with another A operand. A lane's 8 weights of
+// a 16x32 block are 8 bytes in HBM (one 8-byte load per lane and block, half the fp16 path's bytes), turned
+// into the fp16 A fragment exactly in registers right before the MFMA (common.h i8x8_to_f16: 2 xor, 4 byte
+// permutes, 4 packed subtracts per operand). The row scale is NOT applied to the operand: it multiplies the
+// finished fp32 row sum in the epilogue (Epi::rscale; after the per-sequence 1/rms of the NORM plans, before
+// anything else the epilogue does). The k-block stays the unit of everything else (per-wave ranges, steps,
+// clamped duplicate loads, the plan table), so every K % 32 == 0 and every per-wave block count the fp16
+// kernel takes works unchanged, with nothing read past the matrix. The weight type is a template parameter;
+// the fp16 instantiations have no int8 code in them.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace sli {
@@ -68,7 +80,12 @@ struct BgIn {
     unsigned long long* stamps = nullptr;  // diagnostic (tools/bgemm_lab): per-workgroup s_memrealtime x4
     // W in the fragment layout (bg_tile_kernel): tile t's k-block kb is 1 KiB at ((t * K/32) + kb) * 1024, lane l's
     // 16-byte A operand at l * 16 — one wave load is one contiguous KiB (8 full 128-B lines) instead of 16 rows x
-    // 64 B (16 half lines). 0: W row-major [rows][K] (the op-level entry, tools/bgemm_lab)
+    // 64 B (16 half lines). 0: W row-major [rows][K] (the op-level entry, tools/bgemm_lab).
+    // int8: the same order at half the size — block kb of tile t is 512 B at ((t * K/32) + kb) * 512, lane l's 8
+    // bytes W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7] at l * 8: one wave load is one contiguous, fully used run
+    // of four 128-B lines (row-major: 16 rows x 32 B, 16 quarter lines), and a wave's consecutive blocks are
+    // consecutive in memory, so the loads of one step cover one run of kBgU * 512 B. (Pairing two k-blocks into
+    // 16-byte lane loads would tie the image to the plan: a wave's first block is odd or even with the split.)
     int tiled = 0;
 };
 
@@ -164,8 +181,12 @@ __device__ __forceinline__ void bg_split8(const float* y, u32x4& hi, u32x4& lo) 
 //                               activation loads (pre_a) and right after the first weight steps (pre_b, for
 //                               loads that depend on pre_a's), so they land during the stream instead of
 //                               costing a round trip after it
-template <class Epi, bool NORM, int kBgU = 4>
-__global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const __half* __restrict__ W, BgIn in, Epi epi_in) {
+template <class Epi, bool NORM, int kBgU = 4, typename WT = __half>
+__global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict__ W, BgIn in, Epi epi_in) {
+    static_assert(std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value, "fp16 or int8 weights");
+    constexpr bool I8 = std::is_same<WT, int8_t>::value;
+    constexpr size_t ES = sizeof(WT);  // a lane's A operand of one k-block: 8 elements = 8 * ES bytes
+    using WV = typename std::conditional<I8, u32x2, u32x4>::type;
     Epi epi = epi_in;
     extern __shared__ __attribute__((aligned(16))) char bg_smem[];
     float* red = reinterpret_cast<float*>(bg_smem);  // [16][8]
@@ -239,26 +260,29 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const __half* __restr
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- 2. the first two weight steps
-    const size_t row_bytes = (size_t)K * 2;
+    const size_t row_bytes = (size_t)K * ES;
     const int q8 = (lane >> 4) * 8;  // this lane's k offset inside a 32-k block
-    const size_t bstride = in.tiled ? 1024 : 64;  // bytes between a lane's consecutive k-blocks
-    auto load_step = [&](int k, u32x4(&w)[kBgU]) {
+    const size_t bstride = in.tiled ? 512 * ES : 32 * ES;  // bytes between a lane's consecutive k-blocks
+    auto load_step = [&](int k, WV(&w)[kBgU]) {
         const int kk = min(k, nsteps - 1);
         const int j = kk / cpt, c = kk - j * cpt;
         const char* base;
         if (in.tiled) {
-            base = reinterpret_cast<const char*>(W) + (size_t)(t0 + j) * nkb * 1024 + (size_t)lane * 16;
+            base = reinterpret_cast<const char*>(W) + (size_t)(t0 + j) * nkb * (512 * ES) + (size_t)lane * (8 * ES);
         } else {
             const int row = epi.row(t0 + j, lane & 15);
-            base = reinterpret_cast<const char*>(W) + (size_t)row * row_bytes + (size_t)q8 * 2;
+            base = reinterpret_cast<const char*>(W) + (size_t)row * row_bytes + (size_t)q8 * ES;
         }
 #pragma unroll
         for (int u = 0; u < kBgU; ++u) {
             const int bi = wb0 + min(c * kBgU + u, max(wnb - 1, 0));
-            w[u] = load16<true>(base + (size_t)bi * bstride);
+            if constexpr (I8)
+                w[u] = load8<true>(base + (size_t)bi * bstride);
+            else
+                w[u] = load16<true>(base + (size_t)bi * bstride);
         }
     };
-    u32x4 wa[kBgU], wb[kBgU];  // (a third step in flight measured slower: C4 1660 -> 1546 tok/s)
+    WV wa[kBgU], wb[kBgU];  // (a third step in flight measured slower: C4 1660 -> 1546 tok/s)
     load_step(0, wa);
     load_step(1, wb);
     __builtin_amdgcn_sched_barrier(0);
@@ -300,12 +324,16 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const __half* __restr
     // ---- 5. stream the tiles
     bg_float4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const u32x4* wimg = img + (size_t)(wb0 - kb0) * 64 + lane;
-    auto mfma_step = [&](int k, const u32x4(&w)[kBgU]) {
+    auto mfma_step = [&](int k, const WV(&w)[kBgU]) {
         const int c = k - (k / cpt) * cpt;
 #pragma unroll
         for (int u = 0; u < kBgU; ++u) {
             const int r = c * kBgU + u;
-            if (r < wnb) acc = bg_mfma(w[u], wimg[(size_t)r * 64], acc);
+            if constexpr (I8) {
+                if (r < wnb) acc = bg_mfma(i8x8_to_f16(w[u].x, w[u].y), wimg[(size_t)r * 64], acc);
+            } else {
+                if (r < wnb) acc = bg_mfma(w[u], wimg[(size_t)r * 64], acc);
+            }
         }
     };
     auto tile_end = [&](int k) {
@@ -456,6 +484,7 @@ struct BgEpiQKV {
                      // (prefill lanes of one sequence at consecutive positions)
     int p_t = -1, p_i = 0, p_b = 0, p_pos = 0;  // the prefetched item: its position, then its RoPE row
     float p_sin = 0.0f, p_cos = 0.0f;
+    const float* rscale = nullptr;  // int8: per-row weight scales [(hq + 2 hkv) hd], applied before the rotation
     __device__ void pre_a(int t0, int ntg, int B) {
         const int it = threadIdx.x;
         if (it >= ntg * 64 || (it & 7) >= B) return;
@@ -484,6 +513,10 @@ struct BgEpiQKV {
         const int half = hd >> 1;
         const int u = t * 8 + i;
         const int uh = u / half, d = u - uh * half;
+        if (rscale) {
+            a0 *= rscale[uh * hd + d];
+            a1 *= rscale[uh * hd + d + half];
+        }
         const bool pre = t == p_t && i == p_i && b == p_b;
         const int pos = pre ? p_pos : pos_dev[(size_t)b * pos_stride];
         if (uh < hq + hkv) {  // rope_kernel.cpp:30-38
@@ -514,10 +547,15 @@ struct BgEpiSwiGLU {
     float* act;  // [B][inter]
     int inter;
     int silu;
+    const float* rscale = nullptr;  // int8: per-row weight scales [2 inter], applied before the activation
     __device__ int row(int t, int i) const { return t * 8 + (i & 7) + (i >= 8 ? inter : 0); }
     __device__ void pre_a(int, int, int) {}
     __device__ void pre_b() {}
     __device__ void store(int t, int i, int b, float g, float up, unsigned long long*) const {
+        if (rscale) {
+            g *= rscale[t * 8 + i];
+            up *= rscale[inter + t * 8 + i];
+        }
         float sg = 1.0f / (1.0f + expf(-g));  // swiglu_kernel.cpp:12
         if (silu) sg = g * sg;
         act[(size_t)b * inter + t * 8 + i] = sg * up;  // :13
@@ -531,11 +569,13 @@ struct BgEpiLogits {
     float* logits;                 // [B][ld]
     unsigned long long* keys_out;  // [B][key_ld]
     int nrows, ld, vocab_off, key_ld;
+    const float* rscale = nullptr;  // int8: the row scales of this rank's rows of the table [nrows]
     __device__ int row(int t, int i) const { return min(t * 16 + i, nrows - 1); }
     __device__ void pre_a(int, int, int) {}
     __device__ void pre_b() {}
     __device__ void one(int row, int b, float v, unsigned long long* kl) const {
         if (row >= nrows) return;
+        if (rscale) v *= rscale[row];  // the argmax key is taken after the scale
         logits[(size_t)b * ld + row] = v;
         atomicMax(kl + b, argmax_key(v, (unsigned)(row + vocab_off)));  // a max: order-independent
     }
@@ -551,10 +591,13 @@ struct BgEpiLogits {
 
 // Row-major W [rows][K] -> the fragment layout of BgIn::tiled, rows in the epilogue's tile order (Epi::row:
 // RoPE pairs, gate/up pairs, the last tile's clamped rows): out[(t * K/32 + kb) * 64 + l] (16-byte pieces) =
-// W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7]. Init-time only (weights placed or replaced).
-template <class Epi>
-__global__ void __launch_bounds__(256) bg_tile_kernel(const __half* __restrict__ W, int K, int ntiles, Epi epi,
-                                                       uint4* __restrict__ out) {
+// W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7]; int8: the same pieces at 8 bytes each (BgIn::tiled). Init-time
+// only (weights placed or replaced).
+template <class Epi, typename WT>
+__global__ void __launch_bounds__(256) bg_tile_kernel(const WT* __restrict__ W, int K, int ntiles, Epi epi,
+                                                       void* __restrict__ out_) {
+    using PV = typename std::conditional<sizeof(WT) == 1, uint2, uint4>::type;  // a lane's 8 weights
+    PV* out = reinterpret_cast<PV*>(out_);
     const int nkb = K / 32;
     const size_t n = (size_t)ntiles * nkb * 64;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
@@ -562,32 +605,33 @@ __global__ void __launch_bounds__(256) bg_tile_kernel(const __half* __restrict__
         const size_t tb = p >> 6;
         const int t = (int)(tb / nkb), kb = (int)(tb - (size_t)t * nkb);
         const int row = epi.row(t, l & 15);
-        out[p] = *reinterpret_cast<const uint4*>(W + (size_t)row * K + (size_t)kb * 32 + 8 * (l >> 4));
+        out[p] = *reinterpret_cast<const PV*>(W + (size_t)row * K + (size_t)kb * 32 + 8 * (l >> 4));
     }
 }
 
-template <class Epi>
-hipError_t launch_bg_tile(const __half* W, int K, int ntiles, const Epi& epi, void* out, hipStream_t s) {
+template <class Epi, typename WT>
+hipError_t launch_bg_tile(const WT* W, int K, int ntiles, const Epi& epi, void* out, hipStream_t s) {
     if (K % 32) return hipErrorInvalidValue;
     const size_t n = (size_t)ntiles * (K / 32) * 64;
     const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
-    hipLaunchKernelGGL((bg_tile_kernel<Epi>), dim3(blocks), dim3(256), 0, s, W, K, ntiles, epi,
-                       reinterpret_cast<uint4*>(out));
+    hipLaunchKernelGGL((bg_tile_kernel<Epi, WT>), dim3(blocks), dim3(256), 0, s, W, K, ntiles, epi, out);
     return hipGetLastError();
 }
-// bytes of a tiled matrix
-inline size_t bg_tiled_bytes(int ntiles, int K) { return (size_t)ntiles * (size_t)(K / 32) * 1024; }
+// bytes of a tiled matrix of `esize`-byte weights (2: fp16, 1: int8)
+inline size_t bg_tiled_bytes(int ntiles, int K, int esize = 2) {
+    return (size_t)ntiles * (size_t)(K / 32) * 512 * (size_t)esize;
+}
 
 // Allow the kernel its full dynamic LDS (once per instantiation; call outside stream capture).
-template <class Epi, bool NORM>
+template <class Epi, bool NORM, typename WT = __half>
 hipError_t bg_allow_lds() {
     static const hipError_t e = [] {
-        const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 4>),
+        const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 4, WT>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
-        const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 2>),
+        const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 2, WT>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
         if (!NORM) {
-            const hipError_t e7 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 7>),
+            const hipError_t e7 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 7, WT>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
             if (e7 != hipSuccess) return e7;
         }
@@ -596,8 +640,8 @@ hipError_t bg_allow_lds() {
     return e;
 }
 
-template <class Epi>
-hipError_t launch_bgemm(const __half* W, const BgIn& in_, const Epi& epi, const BgPlan& p, hipStream_t s) {
+template <class Epi, typename WT>
+hipError_t launch_bgemm(const WT* W, const BgIn& in_, const Epi& epi, const BgPlan& p, hipStream_t s) {
     BgIn in = in_;
     in.ntiles = p.ntiles;
     in.tpw = p.tpw;
@@ -606,15 +650,15 @@ hipError_t launch_bgemm(const __half* W, const BgIn& in_, const Epi& epi, const 
     if (in.norm_w && p.splits != 1) return hipErrorInvalidValue;  // the fused RMS runs on one split only
     const bool u2 = bg_step_width(p.tpw) == 2;
     if (in.norm_w && u2)
-        hipLaunchKernelGGL((bgemm_kernel<Epi, true, 2>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
+        hipLaunchKernelGGL((bgemm_kernel<Epi, true, 2, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else if (in.norm_w)
-        hipLaunchKernelGGL((bgemm_kernel<Epi, true, 4>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
+        hipLaunchKernelGGL((bgemm_kernel<Epi, true, 4, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else if (u2)
-        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 2>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
+        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 2, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else if (bg_seven_blocks(p.splits, in.K))
-        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 7>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
+        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 7, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else
-        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 4>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
+        hipLaunchKernelGGL((bgemm_kernel<Epi, false, 4, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     return hipGetLastError();
 }
 

@@ -149,6 +149,35 @@ __device__ __forceinline__ u32x4 load16(const void* p) {
     }
 }
 
+// 8-byte load (a lane's 8 int8 weights of a 16x32 MFMA A block)
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+template <bool NT>
+__device__ __forceinline__ u32x2 load8(const void* p) {
+    if constexpr (NT) {
+        return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+    } else {
+        return *reinterpret_cast<const u32x2*>(p);
+    }
+}
+
+// 8 int8 weights (w0: bytes 0..3, w1: bytes 4..7) -> 8 fp16 (exact for all of -128..127): fp16 bits
+// 0x6400 | (b ^ 0x80) = 1024 + b + 128, minus 1152. The MFMA GEMMs' int8 A operand (prefill.h, bgemm.h).
+__device__ __forceinline__ u32x4 i8x8_to_f16(unsigned w0, unsigned w1) {
+    u32x4 r;
+    const unsigned x[2] = {w0 ^ 0x80808080u, w1 ^ 0x80808080u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // bytes b0 b1 -> halves (0x64 b0), (0x64 b1) via byte permutes
+        const unsigned lo = __builtin_amdgcn_perm(0x64646464u, x[h], 0x05010400u);  // {b0, 0x64, b1, 0x64}
+        const unsigned hi = __builtin_amdgcn_perm(0x64646464u, x[h], 0x07030602u);  // {b2, 0x64, b3, 0x64}
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        const h2 k = {(_Float16)1152.0f, (_Float16)1152.0f};
+        r[2 * h] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, lo) - k);
+        r[2 * h + 1] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, hi) - k);
+    }
+    return r;
+}
+
 // element types of a 16-byte vector
 template <typename T>
 struct Vec16;

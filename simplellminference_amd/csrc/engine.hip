@@ -50,7 +50,7 @@ struct LayerW {
     float* gu_s = nullptr;
     void* down = nullptr;  // [D][Il]      (column slice of down)
     float* down_s = nullptr;
-    // batch > 1, fp16: the same matrices in bgemm's fragment layout (bgemm.h BgIn::tiled), rows in each
+    // batch > 1 (fp16 or int8): the same matrices in bgemm's fragment layout (bgemm.h BgIn::tiled), rows in each
     // epilogue's tile order; the decode step streams these, the row-major copies serve prefill-free readback
     void *qkv_t = nullptr, *wo_t = nullptr, *gu_t = nullptr, *down_t = nullptr;
 };
@@ -855,18 +855,20 @@ struct StepRecorder {
 
     // ---- batch > 1: the same step for B sequences, projections on MFMA (bgemm.h)
     static constexpr int kPosStride = (int)(sizeof(DevState) / sizeof(int32_t));
+    // weight types bgemm.h streams; int8: every epilogue gets the matrix's row scales (null for fp16)
+    static constexpr bool kBgWT = std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value;
     template <class Epi>
     static int bg(sli_model* m, const void* W, const BgIn& in, const Epi& e, const BgPlan& p) {
-        if constexpr (std::is_same<WT, __half>::value) {
-            SLI_HIP(launch_bgemm((const __half*)W, in, e, p, m->stream));
+        if constexpr (kBgWT) {
+            SLI_HIP(launch_bgemm((const WT*)W, in, e, p, m->stream));
             return SLI_OK;
         } else {
-            return fail(SLI_ERR_ARG, "batch > 1 needs fp16 weights");
+            return fail(SLI_ERR_ARG, "batch > 1 needs fp16 or int8 weights");
         }
     }
     template <class Epi, bool NORM>
     static int allow(sli_model*) {
-        if constexpr (std::is_same<WT, __half>::value) SLI_HIP((bg_allow_lds<Epi, NORM>()));
+        if constexpr (kBgWT) SLI_HIP((bg_allow_lds<Epi, NORM, WT>()));
         return SLI_OK;
     }
     // raise the LDS limit of every batched kernel once, before any capture
@@ -894,11 +896,13 @@ struct StepRecorder {
         const size_t lay = (size_t)l * m->B * m->hkv * m->T * m->hd;
         BgEpiQKV<KT> e{m->q, (KT*)m->kc + lay, (KT*)m->vc + lay, &m->st->pos, kPosStride, m->sin_t, m->cos_t,
                        m->hq, m->hkv, m->hd, m->T};
+        e.rscale = rs(m->layers[l].qkv_s);
         return bg(m, m->bg_tiled ? m->layers[l].qkv_t : m->layers[l].qkv, bin(m, m->x, m->norms + (size_t)(2 * l) * m->D, m->D), e, m->bp_qkv);
     }
     // batched wo / down with the exchange per group (oneshot.h BgEpiPush; region 3: wo, 4: down)
-    static BgEpiPush push_bg(sli_model* m, int region, const BgPlan& p) {
+    static BgEpiPush push_bg(sli_model* m, int region, const BgPlan& p, const float* rscale) {
         BgEpiPush e{};
+        e.rscale = rs(rscale);
         e.resid = m->c.tp_rank == 0 ? m->x : nullptr;
         for (int r = 0; r < m->c.tp_size; ++r) e.os.peers[r] = m->os_peer[r];
         e.os.rank = m->c.tp_rank;
@@ -922,23 +926,23 @@ struct StepRecorder {
     static int b_wo(sli_model* m, int l) {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].wo_t : m->layers[l].wo;
-        if (fused_ar(m)) return bg(m, w, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo), m->bp_wo);
-        BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, nullptr, 1.0f, m->D, m->D};
+        if (fused_ar(m)) return bg(m, w, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo, m->layers[l].wo_s), m->bp_wo);
+        BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].wo_s), 1.0f, m->D, m->D};
         return bg(m, w, bin(m, m->attn, nullptr, m->hq * m->hd), e, m->bp_wo);
     }
     static int b_gu(sli_model* m, int l) {
-        BgEpiSwiGLU e{m->act, m->Il, m->c.act_mode};
+        BgEpiSwiGLU e{m->act, m->Il, m->c.act_mode, rs(m->layers[l].gu_s)};
         return bg(m, m->bg_tiled ? m->layers[l].gu_t : m->layers[l].gu, bin(m, m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->D), e, m->bp_gu);
     }
     static int b_down(sli_model* m, int l) {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].down_t : m->layers[l].down;
-        if (fused_ar(m)) return bg(m, w, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down), m->bp_down);
-        BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, nullptr, 1.0f, m->D, m->D};
+        if (fused_ar(m)) return bg(m, w, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down, m->layers[l].down_s), m->bp_down);
+        BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].down_s), 1.0f, m->D, m->D};
         return bg(m, w, bin(m, m->act, nullptr, m->Il), e, m->bp_down);
     }
     static int b_lm(sli_model* m) {
-        BgEpiLogits e{m->logits, m->keys, m->v_n, m->v_n, m->v_lo, m->key_ld};
+        BgEpiLogits e{m->logits, m->keys, m->v_n, m->v_n, m->v_lo, m->key_ld, m->emb_s && !MX ? m->emb_s + m->v_lo : nullptr};
         const void* w = m->bg_tiled ? m->lm_t : wptr(m->emb, m->wbytes, (size_t)m->v_lo * m->D);
         return bg(m, w, bin(m, m->x, m->norms + (size_t)(2 * m->L) * m->D, m->D), e, m->bp_lm);
     }
@@ -953,7 +957,7 @@ struct StepRecorder {
         if (p == 0) {
             if (batched) {
                 if constexpr (MX) {
-                    return fail(SLI_ERR_ARG, "batch > 1 needs fp16 weights");
+                    return fail(SLI_ERR_ARG, "batch > 1 needs fp16 or int8 weights");
                 } else {
                     const int eb = std::min(64, (m->D + 255) / 256);
                     hipLaunchKernelGGL(embedding_batch_kernel<WT>, dim3(eb, m->B), dim3(256), 0, s, m->st,
@@ -1275,8 +1279,8 @@ static int capture_graph(hipStream_t stream, hipGraph_t& graph, hipGraphExec_t& 
 
 // (Re)build the fragment-layout copies of the batched projections from the row-major matrices after weights
 // were placed (bgemm.h bg_tile_kernel; each epilogue's row order), on the model's stream before any use
-static int bg_sync_tiles(sli_model* m) {
-    if (!m->bg_tiled || !m->tiles_dirty) return SLI_OK;
+template <typename WT>
+static int bg_build_tiles(sli_model* m) {
     const int D = m->D, hd = m->hd, QD = m->hq * hd;
     hipStream_t s = m->stream;
     BgEpiQKV<__half> eq{};
@@ -1290,14 +1294,18 @@ static int bg_sync_tiles(sli_model* m) {
     BgEpiLogits el{};
     el.nrows = m->v_n;
     for (const LayerW& w : m->layers) {
-        SLI_HIP(launch_bg_tile((const __half*)w.qkv, D, m->bp_qkv.ntiles, eq, w.qkv_t, s));
-        SLI_HIP(launch_bg_tile((const __half*)w.wo, QD, m->bp_wo.ntiles, eo, w.wo_t, s));
-        SLI_HIP(launch_bg_tile((const __half*)w.gu, D, m->bp_gu.ntiles, eg, w.gu_t, s));
-        SLI_HIP(launch_bg_tile((const __half*)w.down, m->Il, m->bp_down.ntiles, eo, w.down_t, s));
+        SLI_HIP(launch_bg_tile((const WT*)w.qkv, D, m->bp_qkv.ntiles, eq, w.qkv_t, s));
+        SLI_HIP(launch_bg_tile((const WT*)w.wo, QD, m->bp_wo.ntiles, eo, w.wo_t, s));
+        SLI_HIP(launch_bg_tile((const WT*)w.gu, D, m->bp_gu.ntiles, eg, w.gu_t, s));
+        SLI_HIP(launch_bg_tile((const WT*)w.down, m->Il, m->bp_down.ntiles, eo, w.down_t, s));
     }
-    SLI_HIP(launch_bg_tile((const __half*)m->emb + (size_t)m->v_lo * D, D, m->bp_lm.ntiles, el, m->lm_t, s));
+    SLI_HIP(launch_bg_tile((const WT*)m->emb + (size_t)m->v_lo * D, D, m->bp_lm.ntiles, el, m->lm_t, s));
     m->tiles_dirty = false;
     return SLI_OK;
+}
+static int bg_sync_tiles(sli_model* m) {
+    if (!m->bg_tiled || !m->tiles_dirty) return SLI_OK;
+    return m->c.w_dtype == SLI_DT_I8 ? bg_build_tiles<int8_t>(m) : bg_build_tiles<__half>(m);
 }
 
 static int capture(sli_model* m) {
@@ -1475,22 +1483,23 @@ static int wo_ksplit(const sli_model* m) {
 }
 
 // The batched projections' fragment-layout weight copies (bgemm.h BgIn::tiled: one contiguous KiB per wave load;
-// C4 1742 -> 1988 tok/s, profiles/r4_bg_tiled_ab.txt). They double the projection weights in HBM (C4: +15 GB), so
+// C4 1742 -> 1988 tok/s, profiles/r4_bg_tiled_ab.txt; int8: the same pieces at 8 bytes per lane). They double the
+// projection weights in HBM (C4: +15 GB at fp16, +7.5 GB at int8), so
 // they are allocated last and only when they fit beside everything else with 1 GiB to spare; otherwise (or if an
 // allocation fails) the model keeps streaming the row-major matrices (16 rows x 64 B per wave load), which is
 // correct, only slower. SLI_DEBUG_BG_ROWMAJOR=1 forces that fallback (tests).
 static void bg_alloc_tiles(sli_model* m) {
     m->bg_tiled = false;
-    if (m->c.w_dtype != SLI_DT_F16 || std::getenv("SLI_DEBUG_BG_ROWMAJOR")) return;
-    const int D = m->D, QD = m->hq * m->hd;
+    if ((m->c.w_dtype != SLI_DT_F16 && m->c.w_dtype != SLI_DT_I8) || std::getenv("SLI_DEBUG_BG_ROWMAJOR")) return;
+    const int D = m->D, QD = m->hq * m->hd, es = m->c.w_dtype == SLI_DT_I8 ? 1 : 2;
     std::vector<std::pair<void**, size_t>> want;
     for (auto& w : m->layers) {
-        want.push_back({&w.qkv_t, bg_tiled_bytes(m->bp_qkv.ntiles, D)});
-        want.push_back({&w.wo_t, bg_tiled_bytes(m->bp_wo.ntiles, QD)});
-        want.push_back({&w.gu_t, bg_tiled_bytes(m->bp_gu.ntiles, D)});
-        want.push_back({&w.down_t, bg_tiled_bytes(m->bp_down.ntiles, m->Il)});
+        want.push_back({&w.qkv_t, bg_tiled_bytes(m->bp_qkv.ntiles, D, es)});
+        want.push_back({&w.wo_t, bg_tiled_bytes(m->bp_wo.ntiles, QD, es)});
+        want.push_back({&w.gu_t, bg_tiled_bytes(m->bp_gu.ntiles, D, es)});
+        want.push_back({&w.down_t, bg_tiled_bytes(m->bp_down.ntiles, m->Il, es)});
     }
-    want.push_back({&m->lm_t, bg_tiled_bytes(m->bp_lm.ntiles, D)});
+    want.push_back({&m->lm_t, bg_tiled_bytes(m->bp_lm.ntiles, D, es)});
     size_t need = 0, free_b = 0, total_b = 0;
     for (const auto& p : want) need += p.second;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)1 << 30)) return;
@@ -1543,7 +1552,8 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     const int B = c.batch > 0 ? c.batch : 1;
     SLI_CHECK(B <= kBgMaxBatch, SLI_ERR_SHAPE, "batch must be at most 8");
     if (B > 1) {
-        SLI_CHECK(c.w_dtype == SLI_DT_F16, SLI_ERR_ARG, "batch > 1 needs fp16 weights (MFMA projections)");  // mxfp4 too
+        SLI_CHECK(c.w_dtype == SLI_DT_F16 || c.w_dtype == SLI_DT_I8, SLI_ERR_ARG,
+                  "batch > 1 needs fp16 or int8 weights (MFMA projections)");  // f32 and mxfp4 are refused
         SLI_CHECK(c.dim % 32 == 0 && (c.ffn / c.tp_size) % 32 == 0 && ((c.n_heads / c.tp_size) * c.head_dim) % 32 == 0,
                   SLI_ERR_SHAPE, "batch > 1: projection inputs must be multiples of 32");
         SLI_CHECK(c.dim <= kBgMaxStageK, SLI_ERR_SHAPE, "batch > 1: dim must be at most 4096 (RMS staging)");
@@ -2470,22 +2480,25 @@ int sli_model_time_stream(sli_model* m, int32_t iters, double* us) {
     const double wb = m->wbytes;  // (mxfp4: the data bytes; the scales, 1/16 of them, are not part of this floor)
     const long long kvl = (long long)m->B * m->hkv * m->T * hd * m->kvbytes;  // one layer's K (or V)
     const int grid = device_cus();
+    // batch > 1 with the fragment-layout copies: the launches read those (the same bytes; a copy is at least as
+    // large as its matrix, its last tile's clamped rows included), so the floor streams them
+    const bool tl = m->bg_tiled;
     auto launch = [&](int f, int l) {
         const char *a = nullptr, *b = nullptr, *c = nullptr;
         long long na = 0, nb = 0, nc = 0;
         const LayerW& w = m->layers[f == SLI_FAM_LM ? 0 : l];
         switch (f) {
-            case SLI_FAM_QKV: a = (const char*)w.qkv; na = (long long)((m->hq + 2LL * m->hkv) * hd * D * wb); break;
+            case SLI_FAM_QKV: a = (const char*)(tl ? w.qkv_t : w.qkv); na = (long long)((m->hq + 2LL * m->hkv) * hd * D * wb); break;
             case SLI_FAM_ATTN:
                 a = (const char*)m->kc + l * kvl;
                 b = (const char*)m->vc + l * kvl;
                 na = nb = kvl;
                 break;
-            case SLI_FAM_WO: a = (const char*)w.wo; na = (long long)(D * m->hq * hd * wb); break;
-            case SLI_FAM_GU: a = (const char*)w.gu; na = (long long)(2LL * m->Il * D * wb); break;
-            case SLI_FAM_DOWN: a = (const char*)w.down; na = (long long)(D * m->Il * wb); break;
+            case SLI_FAM_WO: a = (const char*)(tl ? w.wo_t : w.wo); na = (long long)(D * m->hq * hd * wb); break;
+            case SLI_FAM_GU: a = (const char*)(tl ? w.gu_t : w.gu); na = (long long)(2LL * m->Il * D * wb); break;
+            case SLI_FAM_DOWN: a = (const char*)(tl ? w.down_t : w.down); na = (long long)(D * m->Il * wb); break;
             default:
-                a = (const char*)m->emb + (long long)((long long)m->v_lo * D * wb);
+                a = tl ? (const char*)m->lm_t : (const char*)m->emb + (long long)((long long)m->v_lo * D * wb);
                 na = (long long)((long long)m->v_n * D * wb);
                 break;
         }

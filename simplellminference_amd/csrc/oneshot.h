@@ -247,6 +247,7 @@ struct BgEpiPush {
     unsigned* wg_epoch;  // [kOsRegions][kOsMaxWg]
     int region;
     int nrows, ld, B, tpw, ntiles;
+    const float* rscale = nullptr;  // int8: per-row weight scales [nrows], applied before the residual and the push
     __device__ int row(int t, int i) const { return min(t * 16 + i, nrows - 1); }
     __device__ void pre_a(int, int, int) {}
     __device__ void pre_b() {}
@@ -254,6 +255,7 @@ struct BgEpiPush {
     __device__ void one(int row, int b, float v, int par) const {
         if (row >= nrows) return;
         const size_t o = (size_t)b * ld + row;
+        if (rscale) v *= rscale[row];
         const float a = resid ? resid[o] + v : v;  // add_kernel.cpp:5-14, once (rank 0)
 #pragma unroll
         for (int p = 0; p < kOsMaxRanks; ++p)

@@ -439,6 +439,45 @@ int sli_matmul_batch(const float* x, const void* w, int w_dtype, float* y, int32
     return SLI_OK;
 }
 
+// int8 workspace: the fp16 entry's (split partials, counters), then for tiled = 1 the fragment-layout image of W
+// at the next 256-byte boundary
+static size_t bg_i8_image_off(const BgPlan& p) { return (bg_ws_bytes(p) + 255) & ~(size_t)255; }
+
+size_t sli_matmul_batch_i8_workspace_bytes(int32_t rows, int32_t cols, int32_t batch, int32_t tiled) {
+    if (rows <= 0 || cols <= 0 || batch <= 0 || batch > kBgMaxBatch || cols % 32 != 0) return 0;
+    const BgPlan p = bg_plan((rows + 15) / 16, cols, batch, false, device_cus());
+    if (p.groups <= 0) return 0;
+    return tiled ? bg_i8_image_off(p) + bg_tiled_bytes(p.ntiles, cols, 1) : bg_ws_bytes(p);
+}
+
+int sli_matmul_batch_i8(const float* x, const void* w, const float* w_row_scale, float* y, int32_t rows, int32_t cols,
+                        int32_t batch, int32_t tiled, void* workspace, size_t workspace_bytes, sli_stream_t stream) {
+    SLI_CHECK(x && w && y && workspace, SLI_ERR_ARG, "sli_matmul_batch_i8: null pointer");
+    SLI_CHECK(rows > 0 && cols > 0 && cols % 32 == 0, SLI_ERR_SHAPE, "sli_matmul_batch_i8: cols must be a multiple of 32");
+    SLI_CHECK(batch >= 1 && batch <= kBgMaxBatch, SLI_ERR_SHAPE, "sli_matmul_batch_i8: batch must be in [1, 8]");
+    SLI_CHECK((uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0, SLI_ERR_ARG, "sli_matmul_batch_i8: 16-byte alignment");
+    SLI_CHECK(!tiled || (uintptr_t)workspace % 16 == 0, SLI_ERR_ARG, "sli_matmul_batch_i8: 16-byte alignment");
+    const BgPlan p = bg_plan((rows + 15) / 16, cols, batch, false, device_cus());
+    SLI_CHECK(p.groups > 0, SLI_ERR_SHAPE, "sli_matmul_batch_i8: no tiling fits");
+    SLI_CHECK(workspace_bytes >= sli_matmul_batch_i8_workspace_bytes(rows, cols, batch, tiled), SLI_ERR_ARG,
+              "sli_matmul_batch_i8: workspace too small");
+    hipStream_t s = as_stream(stream);
+    unsigned* cnt = (unsigned*)((char*)workspace + bg_part_bytes(p));
+    SLI_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * p.groups, s));
+    SLI_HIP((bg_allow_lds<BgEpiStore, false, int8_t>()));
+    BgIn in{x, nullptr, 0.0f, cols, batch, 0, 0, 0, (float*)workspace, cnt};
+    BgEpiStore e{y, nullptr, w_row_scale, 1.0f, rows, rows};
+    const int8_t* wp = (const int8_t*)w;
+    if (tiled) {  // the model's path: the same tile kernel and row map, then the image is streamed
+        void* img = (char*)workspace + bg_i8_image_off(p);
+        SLI_HIP(launch_bg_tile(wp, cols, p.ntiles, e, img, s));
+        wp = (const int8_t*)img;
+        in.tiled = 1;
+    }
+    SLI_HIP(launch_bgemm(wp, in, e, p, s));
+    return SLI_OK;
+}
+
 int sli_rmsnorm(const float* x, const float* w, float* y, int32_t dim, float eps, sli_stream_t stream) {
     SLI_CHECK(x && w && y, SLI_ERR_ARG, "sli_rmsnorm: null pointer");
     SLI_CHECK(dim > 0, SLI_ERR_SHAPE, "sli_rmsnorm: dim");

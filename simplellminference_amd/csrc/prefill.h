@@ -212,22 +212,8 @@ struct PgGeo {
 // bank span, so the chunk index is XORed with row / 2; rows of 256 B with the row
 __device__ __forceinline__ int pg_swz(int row, int row_bytes) { return row_bytes == 128 ? (row >> 1) & 7 : row & 15; }
 
-// 8 int8 weights -> 8 fp16 (exact): fp16 bits 0x6400 | (b ^ 0x80) = 1024 + b + 128, minus 1152
-__device__ __forceinline__ u32x4 pg_i8_to_f16(uint2 w) {
-    u32x4 r;
-    const unsigned x[2] = {w.x ^ 0x80808080u, w.y ^ 0x80808080u};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        // bytes b0 b1 -> halves (0x64 b0), (0x64 b1) via byte permutes
-        const unsigned lo = __builtin_amdgcn_perm(0x64646464u, x[h], 0x05010400u);  // {b0, 0x64, b1, 0x64}
-        const unsigned hi = __builtin_amdgcn_perm(0x64646464u, x[h], 0x07030602u);  // {b2, 0x64, b3, 0x64}
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const h2 k = {(_Float16)1152.0f, (_Float16)1152.0f};
-        r[2 * h] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, lo) - k);
-        r[2 * h + 1] = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, hi) - k);
-    }
-    return r;
-}
+// 8 int8 weights -> 8 fp16 (exact): common.h i8x8_to_f16
+__device__ __forceinline__ u32x4 pg_i8_to_f16(uint2 w) { return i8x8_to_f16(w.x, w.y); }
 
 // wait until at most `later` stages of DPW images each are still in flight (later: 0 .. 6)
 template <int DPW>

@@ -100,6 +100,25 @@ def matmul_batch(x, w, y=None):
     return y
 
 
+def matmul_batch_i8(x, w, row_scale=None, tiled: bool = False, y=None):
+    """The batched projection from int8 weights: y[b][r] = (W[r] . x[b]) * row_scale[r]; x [B, cols] fp32, W
+    [rows, cols] int8, row_scale [rows] fp32 or None (1), y [B, rows] fp32. tiled=True first re-lays W into the
+    model's fragment layout (inside the workspace) and streams that image, the path a batched int8 model runs."""
+    batch, cols = x.shape
+    rows = w.shape[0]
+    if w.shape[1] != cols or w.dtype != torch.int8 or (row_scale is not None and row_scale.numel() != rows):
+        raise ValueError("Tensor with Wrong Dim!")
+    y = torch.empty(batch, rows, device=x.device, dtype=torch.float32) if y is None else y
+    nbytes = _lib.load().sli_matmul_batch_i8_workspace_bytes(rows, cols, batch, int(tiled))
+    if nbytes == 0:
+        raise ValueError("unsupported batched shape (cols % 32 != 0 or batch > 8)")
+    ws = torch.empty(nbytes // 4 + 1, device=x.device, dtype=torch.float32)
+    _dev(x, w, row_scale, y, ws)
+    call("sli_matmul_batch_i8", _p(x), _p(w), _p(row_scale), _p(y), rows, cols, batch, int(tiled), _p(ws),
+         ws.numel() * 4, _s())
+    return y
+
+
 def rmsnorm(x, w, eps: float, y=None):
     """rmsnorm_kernel_cuda (rms_kernel.cuh:6-7)."""
     y = torch.empty_like(x) if y is None else y
