@@ -38,8 +38,10 @@ typedef enum {
 
 /* SLI_DT_MXFP4: OCP microscaling FP4 weights (e2m1 elements, one e8m0 scale per 32 consecutive columns; the layout
  * and the quantisation rule are with sli_quant_mxfp4 below). A weight dtype of the model level and of the
- * sli_*_mxfp4 entry points only. */
-typedef enum { SLI_DT_F32 = 0, SLI_DT_F16 = 1, SLI_DT_I8 = 2, SLI_DT_MXFP4 = 3 } sli_dtype;
+ * sli_*_mxfp4 entry points only.
+ * SLI_DT_F8E4M3: OCP FP8 E4M3 ("e4m3fn"), one byte per element and no scale (the format and the quantisation rule
+ * are with sli_quant_f8 below). A K/V cache dtype: sli_mha, sli_mha_strided and the sli_*_f8 entry points. */
+typedef enum { SLI_DT_F32 = 0, SLI_DT_F16 = 1, SLI_DT_I8 = 2, SLI_DT_MXFP4 = 3, SLI_DT_F8E4M3 = 4 } sli_dtype;
 
 typedef void* sli_stream_t;
 
@@ -92,6 +94,19 @@ int sli_dequant_mxfp4(const void* data, const void* scales, float* dst, int32_t 
 int sli_matmul_mxfp4(const float* x, const void* data, const void* scales, float* y, int32_t rows, int32_t cols,
                      float scale, sli_stream_t stream);
 
+/* FP8 E4M3 (SLI_DT_F8E4M3). A byte is 1 sign bit, 4 exponent bits (bias 7) and 3 mantissa bits: exponent field
+ * e > 0 is (-1)^s 2^(e - 7) (1 + m / 8), e == 0 the subnormals (-1)^s m 2^-9; the largest finite value is 448
+ * (0x7E), there are no infinities, and 0x7F / 0xFF are NaN. Decoding is exact in fp16 and fp32.
+ * Quantisation of an fp32 value v (deterministic, the one rule every writer of an FP8 cache shares, common.h
+ * f8e4m3_encode): NaN -> 0x7F; otherwise |v| is first clamped to 448 (so every |v| > 448, +-inf included, saturates
+ * to +-448 and the NaN codes are never produced from a number), then rounded to the nearest representable value,
+ * ties to the even code; the sign bit is v's (-0 -> 0x80). The rule is computed in integer arithmetic, so it does
+ * not depend on a hardware convert's saturation or NaN behaviour.
+ *
+ * sli_quant_f8: device fp32 [n] -> codes uint8 [n]. sli_dequant_f8: the inverse table, fp32 [n] (NaN codes -> NaN). */
+int sli_quant_f8(const float* src, void* codes, size_t n, sli_stream_t stream);
+int sli_dequant_f8(const void* codes, float* dst, size_t n, sli_stream_t stream);
+
 /* Batched projection for B sequences decoding in lockstep (the reference is batch 1; this serves
  * SURVEY.md §8 config C4): y[b][r] = sum_c x[b][c] * W[r][c] for b < batch <= 8, on MFMA
  * (v_mfma_f32_16x16x32_f16; the fp32 input is carried as fp16 hi + lo columns). x [batch][cols] fp32, W
@@ -128,13 +143,23 @@ int sli_rope(float* q, float* k, int32_t pos, const int32_t* pos_dev, const floa
              int32_t q_dim, int32_t k_dim, int32_t head_dim, sli_stream_t stream);
 
 /* kernel::mha_kernel_cuda (mha_kernel.cuh:6-21; CPU mha_kernel.cpp:36-77): decode attention for one
- * layer at position pos over a KV cache in REFERENCE layout [L][T][KV] (fp32 or fp16). Split-context
- * flash-decoding: needs sli_mha_workspace_bytes() of device scratch (the reference's {hd,T} score
- * buffer is not needed). */
+ * layer at position pos over a KV cache in REFERENCE layout [L][T][KV] (fp32, fp16 or SLI_DT_F8E4M3).
+ * Split-context flash-decoding: needs sli_mha_workspace_bytes() of device scratch, the same for every cache
+ * dtype (the reference's {hd,T} score buffer is not needed).
+ * An FP8 cache runs the MFMA kernel of attn_mfma_f8.h only (the codes are widened exactly to fp16 in registers, so
+ * the arithmetic after the decode is the fp16 cache's): q, both cache bases, the row stride and the head stride
+ * must each be a multiple of 16 bytes (SLI_ERR_ARG), head_dim 64 or 128 and n_heads / n_kv_heads in {1, 2, 4, 8}
+ * (SLI_ERR_SHAPE). A NaN code in the cache is out of contract there (the kernel reads it as 480).
+ * sli_mha_strided: the same attention over ONE layer's cache with explicit strides in elements: position p of kv
+ * head h is at k + p * pos_stride + h * head_stride (reference layout: pos_stride = n_kv_heads * head_dim,
+ * head_stride = head_dim; the engine's head-major [Hkv][T][hd]: pos_stride = head_dim, head_stride = T * head_dim). */
 size_t sli_mha_workspace_bytes(int32_t max_seq_len, int32_t n_heads, int32_t head_dim);
 int sli_mha(const float* q, const void* kcache, const void* vcache, int kv_dtype, float* out, int32_t layer,
             int32_t pos, int32_t max_seq_len, int32_t head_dim, int32_t n_heads, int32_t n_kv_heads,
             void* workspace, size_t workspace_bytes, sli_stream_t stream);
+int sli_mha_strided(const float* q, const void* k, const void* v, int kv_dtype, float* out, int32_t pos,
+                    int32_t max_seq_len, int32_t head_dim, int32_t n_heads, int32_t n_kv_heads, int64_t pos_stride,
+                    int64_t head_stride, void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
 /* softmax_kernel_cpu (mha_kernel.cpp:7-20) as a standalone in-place op over n floats. */
 int sli_softmax(float* x, int32_t n, sli_stream_t stream);
@@ -165,7 +190,9 @@ typedef struct {
                          the model are quantised by the rule at sli_quant_mxfp4; batch 1 only, the launch graph only,
                          no GEMM prefill; dim, the local ffn width and the local q width multiples of 32, else
                          SLI_ERR_SHAPE) */
-    int32_t kv_dtype; /* SLI_DT_F32 / SLI_DT_F16 */
+    int32_t kv_dtype; /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_F8E4M3 (one byte per element, the rule at sli_quant_f8; with
+                         fp16 and int8 weights at any batch, MXFP4 at batch 1, not fp32 weights: SLI_ERR_ARG; the launch
+                         graph only, prompts through the decode step, sli_model_get_kv returns the decoded fp32) */
     int32_t act_mode; /* 0: reference sigmoid(gate)*up (swiglu_kernel.cpp:12-13); 1: SiLU(gate)*up */
     int32_t tp_rank, tp_size;
     int32_t device;
@@ -251,7 +278,7 @@ int sli_model_prefill_path(const sli_model* m);
 /* Which path the next prefill takes. SLI_PREFILL_AUTO (the default): the GEMM prefill where the model can take it,
  * except MXFP4 weights, which stay on the decode step; SLI_PREFILL_GEMM: the chunked MFMA prefill for every weight
  * type that has one (fp16, int8, MXFP4), SLI_ERR_STATE with the reason where the model cannot take it (fp32 weights,
- * batch > 1, a TP rank without a communicator, unsupported shapes); SLI_PREFILL_DECODE: the teacher-forced decode
+ * an FP8 K/V cache, batch > 1, a TP rank without a communicator, unsupported shapes); SLI_PREFILL_DECODE: the teacher-forced decode
  * step for any model. May be changed between prefills; sli_model_prefill_path reports the outcome. The ranks of an
  * in-process group are set through sli_tp_group_set_prefill. */
 enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2 };

@@ -16,7 +16,7 @@ SLI_OK = 0
 STATUS = {0: "ok", 1: "invalid argument", 2: "shape mismatch", 3: "index out of range", 4: "HIP runtime error",
           5: "out of device memory", 6: "RCCL error", 7: "invalid state", 8: "communicator wait timed out"}
 SLI_ERR_COMM, SLI_ERR_TIMEOUT = 6, 8
-DT_F32, DT_F16, DT_I8, DT_MXFP4 = 0, 1, 2, 3
+DT_F32, DT_F16, DT_I8, DT_MXFP4, DT_F8E4M3 = 0, 1, 2, 3, 4
 
 c_int, c_i32, c_u32, c_i64, c_f, c_d, c_vp, c_sz = (ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
                                                     ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t)
@@ -84,6 +84,10 @@ _SIGS = {
     "sli_rope": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "sli_mha_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "sli_mha": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "sli_mha_strided": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp,
+                                c_sz, c_vp]),
+    "sli_quant_f8": (c_int, [c_vp, c_vp, c_sz, c_vp]),
+    "sli_dequant_f8": (c_int, [c_vp, c_vp, c_sz, c_vp]),
     "sli_softmax": (c_int, [c_vp, c_i32, c_vp]),
     "sli_swiglu": (c_int, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "sli_add": (c_int, [c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -247,6 +247,61 @@ __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <>
 __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
 
+// OCP FP8 E4M3 (SLI_DT_F8E4M3), the one-byte K/V cache element. The rule of sli.h, in integer arithmetic (host and
+// device compute the same bits; no hardware convert, so neither its saturation nor its NaN handling enters):
+//   NaN -> 0x7F; |v| clamped to 448 (inf included); below 2^-6 the subnormal step 2^-9 is rounded by an fp32 add of
+//   2^14 (one ulp of 2^14 is 2^-9, the add rounds to nearest even); from 2^-6 up the fp32 word is rounded to nearest
+//   even at its 20th bit and re-biased (127 - 7 = 120 exponent steps = 960 codes).
+struct f8e4m3 {
+    uint8_t bits;
+};
+__host__ __device__ __forceinline__ uint8_t f8e4m3_encode(float v) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const unsigned sign = (u >> 24) & 0x80u;
+    unsigned a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return 0x7F;
+    a = a > 0x43E00000u ? 0x43E00000u : a;  // 448
+    if (a < 0x3C800000u) {                  // below 2^-6: 0 .. 8 steps of 2^-9 (8 is the code of 2^-6)
+        const float t = __builtin_bit_cast(float, a) + 16384.0f;
+        return (uint8_t)(sign | (__builtin_bit_cast(unsigned, t) - 0x46800000u));
+    }
+    const unsigned r = a + 0x7FFFFu + ((a >> 20) & 1u);
+    return (uint8_t)(sign | ((r >> 20) - 960u));
+}
+__host__ __device__ __forceinline__ float f8e4m3_decode(uint8_t b) {
+    const unsigned e = (b >> 3) & 15u, m = b & 7u;
+    if ((b & 0x7Fu) == 0x7Fu) return __builtin_bit_cast(float, 0x7FC00000u);
+    const float mag = e ? __builtin_bit_cast(float, ((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+    return (b & 0x80u) ? -mag : mag;
+}
+template <>
+__device__ __forceinline__ float to_f32<f8e4m3>(f8e4m3 v) { return f8e4m3_decode(v.bits); }
+template <>
+__device__ __forceinline__ f8e4m3 from_f32<f8e4m3>(float v) { return f8e4m3{f8e4m3_encode(v)}; }
+
+// 4 E4M3 codes (the bytes of w) -> 4 fp16 (lo: bytes 0, 1; hi: bytes 2, 3), exact (E4M3 is a subset of fp16,
+// subnormals included): a byte moved to the top of its half and shifted right by one arithmetically puts the sign in
+// bit 15, the 4 exponent bits in fp16's exponent bits 13..10 and the mantissa in bits 9..7; masked, that fp16 is the
+// value times 2^-8 (bias 15 against 7; an fp16 subnormal for an E4M3 subnormal), and the packed multiply by 256 is
+// exact. The NaN codes come out as +-480. The MFMA attention's K and V operands (attn_mfma_f8.h).
+__device__ __forceinline__ void f8x4_to_f16(unsigned w, unsigned& lo, unsigned& hi) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    typedef short s2 __attribute__((ext_vector_type(2)));
+    const h2 k = {(_Float16)256.0f, (_Float16)256.0f};
+    const unsigned a = __builtin_amdgcn_perm(0u, w, 0x010C000Cu);  // {0, b0, 0, b1}
+    const unsigned b = __builtin_amdgcn_perm(0u, w, 0x030C020Cu);  // {0, b2, 0, b3}
+    const unsigned x = __builtin_bit_cast(unsigned, __builtin_bit_cast(s2, a) >> 1) & 0xBF80BF80u;
+    const unsigned y = __builtin_bit_cast(unsigned, __builtin_bit_cast(s2, b) >> 1) & 0xBF80BF80u;
+    lo = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, x) * k);
+    hi = __builtin_bit_cast(unsigned, __builtin_bit_cast(h2, y) * k);
+}
+__device__ __forceinline__ u32x4 f8x8_to_f16(unsigned w0, unsigned w1) {
+    unsigned a, b, c, d;
+    f8x4_to_f16(w0, a, b);
+    f8x4_to_f16(w1, c, d);
+    return u32x4{a, b, c, d};
+}
+
 // Orderable 64-bit argmax key: larger value wins; equal values -> lower index wins (std::max_element's
 // first-max rule, source/op/argmax.cpp:11, whose scan is `if (*best < *it) best = it`). Key 0 is below
 // every real key. Exactly that scan's result, including the values `<` does not order:

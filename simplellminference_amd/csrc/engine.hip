@@ -1114,13 +1114,22 @@ struct StepRecorder {
         if constexpr (!std::is_same<WT, float>::value) SLI_HIP((pg_allow_lds_all<Epi, WT>()));
         return SLI_OK;
     }
+    // an FP8 cache has no chunk attention and no prefill q/k/v epilogue: its prompts run through the decode step
+    static constexpr bool kPfKT = !std::is_same<KT, f8e4m3>::value;
     static int prepare_prefill(sli_model* m) {
-        SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
-        SLI_TRY(allow_pg<PgEpiResid>(m));
-        SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
-        return SLI_OK;
+        if constexpr (kPfKT) {
+            SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
+            SLI_TRY(allow_pg<PgEpiResid>(m));
+            SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
+            return SLI_OK;
+        } else {
+            return fail(SLI_ERR_STATE, "an FP8 K/V cache cannot take the GEMM prefill");
+        }
     }
     static int record_pf_phase(sli_model* m, int p, int M) {
+      if constexpr (!kPfKT) {  // (the discarded branch keeps PgEpiQKV / launch_pf_attn from being instantiated)
+        return fail(SLI_ERR_STATE, "an FP8 K/V cache cannot take the GEMM prefill");
+      } else {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
@@ -1157,6 +1166,7 @@ struct StepRecorder {
         SLI_TRY(pg(m, w.gu, w.gu_s, 2 * m->Il, D, f.hhi, f.hlo, eg, M, 1));
         er.rscale = rs(w.down_s);
         return pg(m, w.down, w.down_s, D, m->Il, f.ahi, f.alo, er, M, 2);
+      }
     }
     static int record_prefill(sli_model* m, int M) {
         for (int p = 0; p < 2 * m->L; ++p) {
@@ -1256,6 +1266,9 @@ struct StepRecorder {
         if (wd == SLI_DT_F32 && kd == SLI_DT_F32) return StepRecorder<float, float>::FN(__VA_ARGS__);   \
         if (wd == SLI_DT_I8 && kd == SLI_DT_F16) return StepRecorder<int8_t, __half>::FN(__VA_ARGS__);  \
         if (wd == SLI_DT_MXFP4 && kd == SLI_DT_F16) return StepRecorder<mxfp4, __half>::FN(__VA_ARGS__); \
+        if (wd == SLI_DT_F16 && kd == SLI_DT_F8E4M3) return StepRecorder<__half, f8e4m3>::FN(__VA_ARGS__); \
+        if (wd == SLI_DT_I8 && kd == SLI_DT_F8E4M3) return StepRecorder<int8_t, f8e4m3>::FN(__VA_ARGS__); \
+        if (wd == SLI_DT_MXFP4 && kd == SLI_DT_F8E4M3) return StepRecorder<mxfp4, f8e4m3>::FN(__VA_ARGS__); \
         if (wd == SLI_DT_MXFP4) return StepRecorder<mxfp4, float>::FN(__VA_ARGS__);                     \
         return StepRecorder<int8_t, float>::FN(__VA_ARGS__);                                            \
     })()
@@ -1457,6 +1470,8 @@ int sli_comm_get_id(void* out) {
 // ctx 4096 against 9 at 2048, so there the attention's last-arriving workgroup merges and wo stages a plain
 // input. SLI_WO_MERGE=0|1 forces it (A/B, profiles/r4_wo_merge_ab.txt).
 static int wo_merges(const sli_model* m) {
+    // an FP8 cache's attention (attn_mfma_f8.h) always merges its own splits: plain-input wo, no K-split
+    if (m->c.kv_dtype == SLI_DT_F8E4M3) return 0;
     const char* e = getenv("SLI_WO_MERGE");
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] - '0';
     const int ppwg = attn_wg_positions(m->c.kv_dtype, m->hd);
@@ -1533,7 +1548,10 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
               "kv heads and ffn must divide by tp_size");
     SLI_CHECK((c.ffn / c.tp_size) % 2 == 0, SLI_ERR_SHAPE, "local ffn must be even");
     SLI_CHECK(c.w_dtype >= SLI_DT_F32 && c.w_dtype <= SLI_DT_MXFP4, SLI_ERR_ARG, "bad w_dtype");
-    SLI_CHECK(c.kv_dtype == SLI_DT_F32 || c.kv_dtype == SLI_DT_F16, SLI_ERR_ARG, "bad kv_dtype");
+    SLI_CHECK(c.kv_dtype == SLI_DT_F32 || c.kv_dtype == SLI_DT_F16 || c.kv_dtype == SLI_DT_F8E4M3, SLI_ERR_ARG,
+              "bad kv_dtype");
+    SLI_CHECK(c.kv_dtype != SLI_DT_F8E4M3 || c.w_dtype != SLI_DT_F32, SLI_ERR_ARG,
+              "an FP8 K/V cache needs fp16, int8 or mxfp4 weights");
     SLI_CHECK(c.tp_size == 1 || comm_id || group || std::getenv("SLI_DEBUG_NOCOMM"), SLI_ERR_ARG,
               "tensor parallel needs a comm id");
     const bool mx = c.w_dtype == SLI_DT_MXFP4;
@@ -1588,7 +1606,7 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     m->v_n = vn;
     if (m->v_n <= 0) return bail(fail(SLI_ERR_SHAPE, "vocab shard is empty"));
     m->wbytes = wb;
-    m->kvbytes = c.kv_dtype == SLI_DT_F32 ? 4 : 2;
+    m->kvbytes = c.kv_dtype == SLI_DT_F32 ? 4 : c.kv_dtype == SLI_DT_F16 ? 2 : 1;
     const bool i8 = c.w_dtype == SLI_DT_I8;
     const int D = m->D, hd = m->hd, qkv_rows = (m->hq + 2 * m->hkv) * hd;
 
@@ -1864,6 +1882,7 @@ static int get_state(sli_model* m, int seq, int32_t* pos, int32_t* token, int32_
 // whose exchange it does have; an in-process group sums the chunk rows itself (record_group_prefill).
 static bool pf_supported(const sli_model* m) {
     if (m->partial && !m->collectives && !m->group) return false;
+    if (m->c.kv_dtype == SLI_DT_F8E4M3) return false;  // no chunk attention over an FP8 cache yet
     return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
            m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
 }
@@ -1877,8 +1896,8 @@ static bool pf_use_gemm(const sli_model* m) {
 static int pf_set_mode(sli_model* m, int mode) {
     SLI_CHECK(mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_DECODE, SLI_ERR_ARG, "set_prefill: mode must be 0, 1 or 2");
     SLI_CHECK(mode != SLI_PREFILL_GEMM || pf_supported(m), SLI_ERR_STATE,
-              "set_prefill: this model cannot take the GEMM prefill (fp32 weights, batch > 1, a TP rank without a "
-              "communicator, head_dim not 64 / 128, or a projection depth that is no multiple of 64)");
+              "set_prefill: this model cannot take the GEMM prefill (fp32 weights, an FP8 K/V cache, batch > 1, a TP "
+              "rank without a communicator, head_dim not 64 / 128, or a projection depth that is no multiple of 64)");
     m->pf.mode = mode;
     return SLI_OK;
 }

@@ -6,6 +6,7 @@
 
 #include "attention.h"
 #include "attn_mfma.h"
+#include "attn_mfma_f8.h"
 #include "bgemm.h"
 #include "common.h"
 #include "gemv.h"
@@ -188,6 +189,9 @@ static int matmul_dispatch(const float* x, const WT* w, const float* rscale, flo
 }
 
 int attn_wg_positions(int kv_dtype, int head_dim) {
+    // an FP8 cache runs attn_mfma_f8_launch only, whose split is never shorter than the fp32 kernel's (the partial
+    // buffer's own split): that length, stated explicitly
+    if (kv_dtype == SLI_DT_F8E4M3) return kAttnSlots * (64 / (head_dim / 4));
     const int epv = kv_dtype == SLI_DT_F16 ? 8 : 4;
     return kAttnSlots * (64 / (head_dim / epv));
 }
@@ -240,11 +244,61 @@ static int attn_mfma_launch(AttnArgs<__half> a, int g, int T, hipStream_t s) {
     return SLI_OK;
 }
 
+// The FP8 cache's attention (attn_mfma_f8.h): the same split geometry and the same two host checks as
+// attn_mfma_launch; nothing else runs an FP8 cache, so what that kernel cannot take is an error here. The ring depth
+// is min(tiles per wave, SLI_ATTN_F8_RING) rounded down to 1, 2 or 4 (the A/B of depth 2 and 4).
+#ifndef SLI_ATTN_F8_RING
+#define SLI_ATTN_F8_RING 2
+#endif
+template <int HD, int G>
+static void attn_mfma_f8_go(const AttnArgs<f8e4m3>& a, int blocks, int nbuf, hipStream_t s) {
+    if (nbuf == 1)
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 1>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
+    else if (nbuf < 4)
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 2>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
+    else
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 4>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
+}
+template <int HD>
+static int attn_mfma_f8_launch(AttnArgs<f8e4m3> a, int g, int T, hipStream_t s) {
+    if (!(g == 1 || g == 2 || g == 4 || g == 8))
+        return fail(SLI_ERR_SHAPE, "mha: heads per kv head must be 1, 2, 4 or 8");
+    if (a.cache_heads != 0 || a.defer_merge == 1)
+        return fail(SLI_ERR_ARG, "mha: an FP8 cache takes neither shared cache heads nor a merge in the consumer");
+    // every 16-byte DMA piece aligned: cache bases, row and head strides (in bytes), q
+    if ((uintptr_t)a.k % 16 || (uintptr_t)a.v % 16 || (uintptr_t)a.q % 16 || a.pos_stride % 16 || a.head_stride % 16)
+        return fail(SLI_ERR_ARG, "mha: an FP8 cache needs 16-byte aligned bases, row stride and head stride");
+    const int pf = attn_wg_positions(SLI_DT_F32, HD);  // the partial buffer's split (attn_mfma_launch)
+    const int tpw = std::max(attn_mfma_tpw(a.n_kv_heads, T, device_cus()), (pf + kAmWgKeys - 1) / kAmWgKeys);
+    a.ppwg = kAmWgKeys * tpw;
+    a.max_splits = (T + a.ppwg - 1) / a.ppwg;
+    if (a.max_splits > kAttnMaxWgSplits) return fail(SLI_ERR_SHAPE, "mha: context too long for the split merge");
+    if (a.max_splits > (T + pf - 1) / pf) return fail(SLI_ERR_SHAPE, "mha: more splits than the partial buffer holds");
+    a.defer_merge = 0;  // the head's last-arriving workgroup merges (a requested merge launch becomes that)
+    const int blocks = a.n_kv_heads * a.max_splits, nbuf = std::min(tpw, SLI_ATTN_F8_RING);
+    switch (g) {
+        case 1: attn_mfma_f8_go<HD, 1>(a, blocks, nbuf, s); break;
+        case 2: attn_mfma_f8_go<HD, 2>(a, blocks, nbuf, s); break;
+        case 4: attn_mfma_f8_go<HD, 4>(a, blocks, nbuf, s); break;
+        default: attn_mfma_f8_go<HD, 8>(a, blocks, nbuf, s); break;
+    }
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
 template <typename KT, int HD>
 static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out, int layer, int pos, const int32_t* pos_dev,
                          int T, int H, int Hkv, long long pos_stride, long long head_stride, long long layer_stride,
                          float* part, unsigned* counters, hipStream_t s, int seq_heads, int pos_seq_stride,
                          int cache_heads, int defer_merge) {
+    if constexpr (std::is_same<KT, f8e4m3>::value) {  // never the register-staged kernels of attention.h
+        AttnArgs<KT> a{q,    kc + (long long)layer * layer_stride, vc + (long long)layer * layer_stride, pos_stride,
+                       head_stride, part, out, counters, pos_dev, pos, Hkv, 0, 1.0f / sqrtf((float)HD),
+                       seq_heads > 0 ? seq_heads : Hkv, pos_seq_stride};
+        a.cache_heads = cache_heads;
+        a.defer_merge = defer_merge;
+        return attn_mfma_f8_launch<HD>(a, H / Hkv, T, s);
+    } else {
     using Geo = AttnGeom<KT, HD>;
     constexpr int ppw_wg = Geo::PPWG;
     const int wg_splits = (T + ppw_wg - 1) / ppw_wg;
@@ -290,6 +344,7 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
         SLI_HIP(hipGetLastError());
     }
     return SLI_OK;
+    }
 }
 
 template <typename KT>
@@ -310,6 +365,10 @@ template int mha_launch<float>(const float*, const float*, const float*, float*,
                                int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int, int,
                                int, int);
 template int mha_launch<__half>(const float*, const __half*, const __half*, float*, int, int, const int32_t*, int,
+                                int, int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int,
+                                int, int, int);
+
+template int mha_launch<f8e4m3>(const float*, const f8e4m3*, const f8e4m3*, float*, int, int, const int32_t*, int,
                                 int, int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int,
                                 int, int, int);
 
@@ -538,7 +597,62 @@ int sli_mha(const float* q, const void* kcache, const void* vcache, int kv_dtype
         return mha_launch<__half>(q, (const __half*)kcache, (const __half*)vcache, out, layer, pos, nullptr,
                                   max_seq_len, head_dim, n_heads, n_kv_heads, kv, head_dim, kv * max_seq_len,
                                   (float*)workspace, counters, s);
+    if (kv_dtype == SLI_DT_F8E4M3)
+        return mha_launch<f8e4m3>(q, (const f8e4m3*)kcache, (const f8e4m3*)vcache, out, layer, pos, nullptr,
+                                  max_seq_len, head_dim, n_heads, n_kv_heads, kv, head_dim, kv * max_seq_len,
+                                  (float*)workspace, counters, s);
     return fail(SLI_ERR_ARG, "sli_mha: bad kv dtype");
+}
+
+int sli_mha_strided(const float* q, const void* k, const void* v, int kv_dtype, float* out, int32_t pos,
+                    int32_t max_seq_len, int32_t head_dim, int32_t n_heads, int32_t n_kv_heads, int64_t pos_stride,
+                    int64_t head_stride, void* workspace, size_t workspace_bytes, sli_stream_t stream) {
+    SLI_CHECK(q && k && v && out && workspace, SLI_ERR_ARG, "sli_mha_strided: null pointer");
+    SLI_CHECK(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0, SLI_ERR_SHAPE, "sli_mha_strided: heads");
+    SLI_CHECK(pos >= 0 && pos < max_seq_len, SLI_ERR_RANGE, "sli_mha_strided: position out of range");
+    SLI_CHECK(pos_stride > 0 && head_stride > 0, SLI_ERR_ARG, "sli_mha_strided: strides");
+    SLI_CHECK(workspace_bytes >= mha_workspace_bytes(max_seq_len, n_heads, head_dim), SLI_ERR_ARG,
+              "sli_mha_strided: workspace too small");
+    hipStream_t s = as_stream(stream);
+    unsigned* counters = (unsigned*)((char*)workspace + mha_part_bytes(max_seq_len, n_heads, head_dim));
+    SLI_HIP(hipMemsetAsync(counters, 0, sizeof(unsigned) * n_kv_heads, s));
+    if (kv_dtype == SLI_DT_F32)
+        return mha_launch<float>(q, (const float*)k, (const float*)v, out, 0, pos, nullptr, max_seq_len, head_dim,
+                                 n_heads, n_kv_heads, pos_stride, head_stride, 0, (float*)workspace, counters, s);
+    if (kv_dtype == SLI_DT_F16)
+        return mha_launch<__half>(q, (const __half*)k, (const __half*)v, out, 0, pos, nullptr, max_seq_len, head_dim,
+                                  n_heads, n_kv_heads, pos_stride, head_stride, 0, (float*)workspace, counters, s);
+    if (kv_dtype == SLI_DT_F8E4M3)
+        return mha_launch<f8e4m3>(q, (const f8e4m3*)k, (const f8e4m3*)v, out, 0, pos, nullptr, max_seq_len, head_dim,
+                                  n_heads, n_kv_heads, pos_stride, head_stride, 0, (float*)workspace, counters, s);
+    return fail(SLI_ERR_ARG, "sli_mha_strided: bad kv dtype");
+}
+
+__global__ void quant_f8_kernel(const float* in, uint8_t* out, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = from_f32<f8e4m3>(in[i]).bits;
+}
+__global__ void dequant_f8_kernel(const uint8_t* in, float* out, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = to_f32<f8e4m3>(f8e4m3{in[i]});
+}
+
+int sli_quant_f8(const float* src, void* codes, size_t n, sli_stream_t stream) {
+    SLI_CHECK(src && codes, SLI_ERR_ARG, "sli_quant_f8: null pointer");
+    SLI_CHECK(n > 0, SLI_ERR_SHAPE, "sli_quant_f8: n");
+    const int blocks = (int)std::min<size_t>(1024, (n + 255) / 256);
+    hipLaunchKernelGGL(quant_f8_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), src, (uint8_t*)codes, n);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+int sli_dequant_f8(const void* codes, float* dst, size_t n, sli_stream_t stream) {
+    SLI_CHECK(codes && dst, SLI_ERR_ARG, "sli_dequant_f8: null pointer");
+    SLI_CHECK(n > 0, SLI_ERR_SHAPE, "sli_dequant_f8: n");
+    const int blocks = (int)std::min<size_t>(1024, (n + 255) / 256);
+    hipLaunchKernelGGL(dequant_f8_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (const uint8_t*)codes, dst, n);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
 }
 
 int sli_softmax(float* x, int32_t n, sli_stream_t stream) {

@@ -16,10 +16,11 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib
-from ._lib import DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
+from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
 
 _DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8,
-           "mxfp4": DT_MXFP4, "fp4": DT_MXFP4}
+           "mxfp4": DT_MXFP4, "fp4": DT_MXFP4,
+           "f8": DT_F8E4M3, "fp8": DT_F8E4M3, "e4m3": DT_F8E4M3}  # K/V cache only (OCP FP8 E4M3, sli.h)
 _PREFILL_MODES = {"auto": 0, "gemm": 1, "decode": 2}  # SLI_PREFILL_*
 
 

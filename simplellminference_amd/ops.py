@@ -11,9 +11,23 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import DT_F16, DT_F32, DT_I8, call
+from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, call
 
-_DT = {torch.float32: DT_F32, torch.float16: DT_F16, torch.int8: DT_I8}
+_DT = {torch.float32: DT_F32, torch.float16: DT_F16, torch.int8: DT_I8, torch.float8_e4m3fn: DT_F8E4M3}
+_KV_NAMES = {"f32": DT_F32, "f16": DT_F16, "f8": DT_F8E4M3, "fp8": DT_F8E4M3, "e4m3": DT_F8E4M3}
+
+
+def _kv_dt(cache, kv_dtype):
+    """Cache dtype code: the tensor's own, or kv_dtype="f8" for E4M3 codes held in a uint8 tensor."""
+    if kv_dtype is None:
+        return _DT[cache.dtype]
+    dt = _KV_NAMES[kv_dtype]
+    if dt == DT_F8E4M3:
+        if cache.dtype not in (torch.uint8, torch.float8_e4m3fn):
+            raise ValueError("an f8 cache is a uint8 or float8_e4m3fn tensor")
+    elif _DT.get(cache.dtype) != dt:
+        raise ValueError("kv_dtype does not match the cache tensor")
+    return dt
 
 
 def _p(t):
@@ -83,6 +97,26 @@ def matmul_mxfp4(x, data, scales, y=None, scale: float = 1.0):
     return y
 
 
+def quant_f8(x, out=None):
+    """fp32 -> FP8 E4M3 codes (uint8, same shape), the rule of sli.h: nearest, ties to even, |v| > 448 saturates."""
+    if x.dtype != torch.float32:
+        raise ValueError("quant_f8 takes fp32")
+    out = torch.empty(x.shape, device=x.device, dtype=torch.uint8) if out is None else out
+    _dev(x, out)
+    call("sli_quant_f8", _p(x), _p(out), x.numel(), _s())
+    return out
+
+
+def dequant_f8(codes, out=None):
+    """FP8 E4M3 codes (uint8 or float8_e4m3fn) -> fp32, exact; the NaN codes give NaN."""
+    if codes.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        raise ValueError("dequant_f8 takes uint8 or float8_e4m3fn codes")
+    out = torch.empty(codes.shape, device=codes.device, dtype=torch.float32) if out is None else out
+    _dev(codes, out)
+    call("sli_dequant_f8", _p(codes), _p(out), codes.numel(), _s())
+    return out
+
+
 def matmul_batch(x, w, y=None):
     """Batched projection for B <= 8 sequences on MFMA (bgemm.h): y[b] = W @ x[b]; x [B, cols] fp32, W
     [rows, cols] fp16, y [B, rows] fp32. No reference counterpart (the reference is batch 1)."""
@@ -145,15 +179,30 @@ def rope(q, k, pos, sin_c, cos_c, head_dim: int):
 
 
 def mha(q, kcache, vcache, layer: int, pos: int, max_len: int, head_dim: int, n_heads: int, n_kv_heads: int,
-        out=None, workspace=None):
-    """mha_kernel_cuda (mha_kernel.cuh:6-21) over a reference-layout [L, T, KV] cache (f32 or f16)."""
+        out=None, workspace=None, kv_dtype=None):
+    """mha_kernel_cuda (mha_kernel.cuh:6-21) over a reference-layout [L, T, KV] cache: f32, f16, or FP8 E4M3 as a
+    float8_e4m3fn tensor or as uint8 codes with kv_dtype="f8"."""
     out = torch.empty(n_heads * head_dim, device=q.device, dtype=torch.float32) if out is None else out
     nbytes = _lib.load().sli_mha_workspace_bytes(max_len, n_heads, head_dim)
     if workspace is None:
         workspace = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
     _dev(q, kcache, vcache, out, workspace)
-    call("sli_mha", _p(q), _p(kcache), _p(vcache), _DT[kcache.dtype], _p(out), layer, pos, max_len, head_dim,
+    call("sli_mha", _p(q), _p(kcache), _p(vcache), _kv_dt(kcache, kv_dtype), _p(out), layer, pos, max_len, head_dim,
          n_heads, n_kv_heads, _p(workspace), workspace.numel() * 4, _s())
+    return out
+
+
+def mha_strided(q, k, v, pos: int, max_len: int, head_dim: int, n_heads: int, n_kv_heads: int, pos_stride: int,
+                head_stride: int, out=None, workspace=None, kv_dtype=None):
+    """The same attention over ONE layer's cache with explicit strides in elements (sli_mha_strided): the engine's
+    head-major [Hkv, T, hd] is pos_stride=head_dim, head_stride=max_len * head_dim."""
+    out = torch.empty(n_heads * head_dim, device=q.device, dtype=torch.float32) if out is None else out
+    nbytes = _lib.load().sli_mha_workspace_bytes(max_len, n_heads, head_dim)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
+    _dev(q, k, v, out, workspace)
+    call("sli_mha_strided", _p(q), _p(k), _p(v), _kv_dt(k, kv_dtype), _p(out), pos, max_len, head_dim, n_heads,
+         n_kv_heads, pos_stride, head_stride, _p(workspace), workspace.numel() * 4, _s())
     return out
 
 

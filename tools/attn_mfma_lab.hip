@@ -3,6 +3,9 @@
 // merge), then each timed over NL distinct K/V caches inside a replayed hipGraph in the merge placement the
 // engine uses (register kernel: C1 deferred to wo = partials only, C4 partials + attn_merge_kernel; MFMA
 // kernel: partials only at C1, in-launch merge elsewhere), with per-workgroup phase stamps of the MFMA kernel.
+// `attn_mfma_lab f8`: the FP8-cache kernel (csrc/attn_mfma_f8.h) at ring depths 1, 2 and 4 against the fp16 MFMA
+// kernel over the same values (the fp16 cache holds the decoded codes exactly): outputs compared, each timed the same
+// way (in-launch merge), with the phase stamps of every variant.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include tools/attn_mfma_lab.hip -o tools/attn_mfma_lab
 #include <hip/hip_runtime.h>
 
@@ -11,9 +14,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <string>
 #include <vector>
 
 #include "../simplellminference_amd/csrc/attn_mfma.h"
+#include "../simplellminference_amd/csrc/attn_mfma_f8.h"
 
 using namespace sli;
 
@@ -334,7 +339,187 @@ static void prefetch_test() {
     }
 }
 
+// ---- FP8 mode
+__global__ void fill_8(f8e4m3* c, __half* h, size_t n, unsigned seed) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        unsigned x = (unsigned)i * 2654435761u ^ seed;
+        x ^= x >> 15;
+        x *= 2246822519u;
+        x ^= x >> 13;
+        const f8e4m3 v = from_f32<f8e4m3>(((float)(x & 0xFFFF) / 65536.0f - 0.5f) * 2.0f);
+        c[i] = v;
+        h[i] = __float2half(to_f32(v));  // exact
+    }
+}
+template <int HD, int G>
+static void launch_f8(const AttnArgs<f8e4m3>& a, int blocks, int nbuf, hipStream_t s) {
+    if (nbuf == 1)
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 1>), dim3(blocks), dim3(256), 0, s, a);
+    else if (nbuf == 2)
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 2>), dim3(blocks), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 4>), dim3(blocks), dim3(256), 0, s, a);
+}
+template <int HD, int G>
+static void run8(const char* name, int nkv, int seq_heads, int T, std::vector<int> pos, int NL, int tpw_force = 0) {
+    const int nseq = nkv / seq_heads;
+    const int tpw = tpw_force ? tpw_force : attn_mfma_tpw(nkv, T, cus());
+    const int ppwg = kAmWgKeys * tpw, splits = (T + ppwg - 1) / ppwg, blocks = nkv * splits;
+    const size_t per = (size_t)nkv * T * HD;
+    std::vector<f8e4m3*> K8(NL), V8(NL);
+    std::vector<__half*> K(NL), V(NL);
+    for (int l = 0; l < NL; ++l) {
+        CK(hipMalloc(&K8[l], per));
+        CK(hipMalloc(&V8[l], per));
+        CK(hipMalloc(&K[l], per * 2));
+        CK(hipMalloc(&V[l], per * 2));
+        fill_8<<<1024, 256>>>(K8[l], K[l], per, 3 + l);
+        fill_8<<<1024, 256>>>(V8[l], V[l], per, 7 + l);
+    }
+    const int H = nkv * G;
+    float *q, *out16, *out8, *part;
+    unsigned* cnt;
+    int32_t* posd;
+    unsigned long long* st;
+    CK(hipMalloc(&q, sizeof(float) * H * HD));
+    CK(hipMalloc(&out16, sizeof(float) * H * HD));
+    CK(hipMalloc(&out8, sizeof(float) * H * HD));
+    CK(hipMalloc(&part, sizeof(float) * (size_t)H * splits * (HD + kAttnPartPad)));
+    CK(hipMalloc(&cnt, sizeof(unsigned) * nkv));
+    CK(hipMemset(cnt, 0, sizeof(unsigned) * nkv));
+    CK(hipMalloc(&posd, sizeof(int32_t) * nseq * 16));
+    CK(hipMalloc(&st, sizeof(unsigned long long) * 4 * blocks));
+    std::vector<int32_t> hp(nseq * 16, 0);
+    for (int b = 0; b < nseq; ++b) hp[b * 16] = pos[b % pos.size()];
+    CK(hipMemcpy(posd, hp.data(), hp.size() * 4, hipMemcpyHostToDevice));
+    fill_f<<<64, 256>>>(q, (size_t)H * HD, 11, 2.0f);
+    CK(hipDeviceSynchronize());
+    auto a16 = [&](int l, unsigned long long* stamps) {
+        AttnArgs<__half> a{q, K[l], V[l], HD, (long long)T * HD, part, out16, cnt, posd, 0, nkv, splits,
+                           1.0f / sqrtf((float)HD), seq_heads, 16, stamps};
+        a.ppwg = ppwg;
+        return a;
+    };
+    auto a8 = [&](int l, unsigned long long* stamps) {
+        AttnArgs<f8e4m3> a{q, K8[l], V8[l], HD, (long long)T * HD, part, out8, cnt, posd, 0, nkv, splits,
+                           1.0f / sqrtf((float)HD), seq_heads, 16, stamps};
+        a.ppwg = ppwg;
+        return a;
+    };
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    // variant 0: the fp16 kernel (its ring of min(tpw, 2)); 1, 2, 4: the FP8 kernel at that ring depth
+    auto go = [&](int variant, int l, unsigned long long* stamps) {
+        if (variant == 0)
+            launch_mfma<HD, G>(a16(l, stamps), blocks, tpw > 1 ? 2 : 1, s);
+        else
+            launch_f8<HD, G>(a8(l, stamps), blocks, variant, s);
+    };
+    double bytes16 = 0;
+    for (int b = 0; b < nseq; ++b) bytes16 += 2.0 * seq_heads * (hp[b * 16] + 1.0) * HD * 2;
+    std::vector<float> h16((size_t)H * HD), h8((size_t)H * HD);
+    go(0, 0, nullptr);
+    CK(hipStreamSynchronize(s));
+    CK(hipMemcpy(h16.data(), out16, h16.size() * 4, hipMemcpyDeviceToHost));
+    for (int variant : {0, 1, 2, 4}) {
+        if (variant > tpw) continue;
+        double md = 0, mo = 0;
+        if (variant) {
+            go(variant, 0, nullptr);
+            CK(hipStreamSynchronize(s));
+            CK(hipMemcpy(h8.data(), out8, h8.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < h8.size(); ++i) {
+                md = std::max(md, (double)std::fabs(h16[i] - h8[i]));
+                mo = std::max(mo, (double)std::fabs(h16[i]));
+            }
+        }
+        double us[3];
+        for (int rep = 0; rep < 3; ++rep) {  // three graphs of NL layers, 20 replays each
+            hipGraph_t g;
+            hipGraphExec_t ge;
+            CK(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+            for (int l = 0; l < NL; ++l) go(variant, l, nullptr);
+            CK(hipStreamEndCapture(s, &g));
+            CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+            CK(hipGraphLaunch(ge, s));
+            CK(hipStreamSynchronize(s));
+            hipEvent_t e0, e1;
+            CK(hipEventCreate(&e0));
+            CK(hipEventCreate(&e1));
+            const int reps = 20;
+            CK(hipEventRecord(e0, s));
+            for (int r = 0; r < reps; ++r) CK(hipGraphLaunch(ge, s));
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            CK(hipGraphExecDestroy(ge));
+            CK(hipGraphDestroy(g));
+            us[rep] = 1000.0 * ms / (reps * NL);
+        }
+        std::sort(us, us + 3);
+        CK(hipMemset(st, 0, sizeof(unsigned long long) * 4 * blocks));
+        go(variant, NL > 1 ? 1 : 0, st);
+        CK(hipStreamSynchronize(s));
+        std::vector<unsigned long long> h(4 * blocks);
+        CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, tend = 0;
+        double ent = 0, q_sum = 0, loop_sum = 0, m_sum = 0;
+        int n = 0, nm = 0;
+        for (int i = 0; i < blocks; ++i)
+            if (h[4 * i]) t0 = std::min(t0, h[4 * i]);
+        for (int i = 0; i < blocks; ++i) {
+            if (!h[4 * i] || !h[4 * i + 2]) continue;
+            ++n;
+            ent = std::max(ent, (double)(h[4 * i] - t0));
+            q_sum += h[4 * i + 1] - h[4 * i];
+            loop_sum += h[4 * i + 2] - h[4 * i + 1];
+            if (h[4 * i + 3]) {
+                m_sum += h[4 * i + 3] - h[4 * i + 2];
+                ++nm;
+            }
+            tend = std::max(tend, std::max(h[4 * i + 2], h[4 * i + 3]));
+        }
+        const double bytes = variant ? bytes16 / 2 : bytes16;
+        printf("%-8s G=%d HD=%d nkv=%3d T=%5d pos0=%5d tpw %2d (%d wg) | %s ring %d | max|d| vs fp16 %.2e (max|o| %.2e) | "
+               "%7.2f us (min %.2f max %.2f) %6.0f GB/s | stamps: entry spread %.2f, q staged %.2f, loop %.2f, last merge "
+               "%.2f (%d), span %.2f us\n",
+               name, G, HD, nkv, T, pos[0], tpw, blocks, variant ? "f8  " : "fp16", variant ? variant : (tpw > 1 ? 2 : 1), md,
+               mo, us[1], us[0], us[2], bytes / (us[1] * 1e3), ent / 100, n ? q_sum / n / 100 : 0.0,
+               n ? loop_sum / n / 100 : 0.0, nm ? m_sum / nm / 100 : 0.0, nm, (tend - t0) / 100.0);
+        fflush(stdout);
+        if (variant && !(md <= 2e-5 * std::max(1.0, mo))) printf("MISMATCH %s ring %d\n", name, variant);
+    }
+    CK(hipStreamDestroy(s));
+    for (int l = 0; l < NL; ++l) {
+        CK(hipFree(K8[l]));
+        CK(hipFree(V8[l]));
+        CK(hipFree(K[l]));
+        CK(hipFree(V[l]));
+    }
+    CK(hipFree(q));
+    CK(hipFree(out16));
+    CK(hipFree(out8));
+    CK(hipFree(part));
+    CK(hipFree(cnt));
+    CK(hipFree(posd));
+    CK(hipFree(st));
+}
+static void f8_mode() {
+    for (int p : {0, 33, 1000, 4095}) run8<128, 4>("C4-pos", 64, 8, 4096, {p}, 1);
+    run8<128, 4>("C4-rag", 64, 8, 4096, {1, 4095, 77, 2048, 3000, 5, 1024, 4000}, 1);
+    run8<64, 4>("hd64g4", 2, 2, 512, {511}, 1);
+    run8<128, 4>("C4", 64, 8, 4096, {4095}, 3);      // Llama-3-8B batch 8 ctx 4096
+    run8<128, 1>("C1", 32, 32, 2048, {2047}, 8);     // Llama-2-7B batch 1 ctx 2048
+    run8<128, 4>("B1-8B", 8, 8, 4096, {4095}, 16);   // Llama-3-8B batch 1 ctx 4096
+    run8<128, 4>("C4-tp8", 8, 1, 4096, {4095}, 16);
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "f8") {
+        f8_mode();
+        return 0;
+    }
     const int only_tpw = argc > 1 ? atoi(argv[1]) : 0;
     if (only_tpw < 0) {  // tools/attn_mfma_lab -1: the Infinity-Cache warm-up test only
         prefetch_test();
