@@ -25,8 +25,14 @@
 // with HBM idle between the bursts; its VALU work (fp16 -> fp32 unpack, 4 heads x 256 FMAs per key, row
 // reductions) is ~9 us per CU at C4. Here the matrix cores do that work in ~1 us per CU and the in-flight
 // bytes live in LDS, so one resident round streams the whole context.
+//
+// One body serves both cache formats (am_attn). A format struct supplies what a cache row's bytes change and nothing
+// else: the element type and size, the largest ring depth, the K / V chunk swizzles, which key of the tile A row i
+// of S MFMA kt is (and so which key a lane's S accumulator (g, kt, r) holds), the K fragment read, and the Vᵀ
+// operand's transposed reads. AmF16 is below; AmF8 (an FP8 E4M3 cache) in attn_mfma_f8.h.
 #pragma once
 #include "attention.h"
+#include "lds_mfma.h"
 
 namespace sli {
 
@@ -34,9 +40,9 @@ constexpr int kAmWaves = 4;   // waves per workgroup (one per SIMD)
 constexpr int kAmKeys = 32;   // keys per tile
 constexpr int kAmWgKeys = kAmWaves * kAmKeys;  // keys per workgroup per tile round: ppwg = kAmWgKeys * tpw
 
-template <int HD, int G>
+template <class F, int HD, int G>
 struct AmGeo {
-    static constexpr int ROWB = HD * 2;              // bytes per cache row
+    static constexpr int ROWB = HD * F::EB;          // bytes per cache row
     static constexpr int IMG = kAmKeys * ROWB;       // one 32-key K (or V) image
     static constexpr int TILE = 2 * IMG;             // K + V
     static constexpr int PIECES = TILE / 1024;       // 1-KiB DMA pieces per tile
@@ -44,69 +50,46 @@ struct AmGeo {
     static constexpr int QB = ((G * HD * 4 + 1023) / 1024) * 1024;  // the q image (fp32), whole pieces
     static constexpr int QP = QB / 1024;
     static constexpr int ND = HD / 32, NT = HD / 16;  // 32-d blocks (S), 16-d tiles (O)
+    static constexpr int MERGE = (NT * 64 * 4 + 128) * 4;  // the wave's (o, mx, l) image of the in-LDS merge
     template <int NBUF>
     static constexpr int wave_bytes() { return QB + NBUF * TILE; }
     static_assert(HD == 64 || HD == 128, "head_dim");
     static_assert(G >= 1 && G <= 16, "query heads per kv head: one MFMA column each");
+    static_assert(QB + TILE >= MERGE, "the merge image fits the smallest wave image");
 };
-// chunk swizzles of the K and V images (as prefill.h pf_attn_mfma_kernel): conflict-free ds_read_b128 row
-// reads of K and ds_read_b64_tr_b16 transposed reads of V
-__device__ __forceinline__ int am_swz_k(int r, int rowb) { return rowb == 256 ? r & 15 : (r >> 1) & 7; }
-__device__ __forceinline__ int am_swz_v(int r, int rowb) { return rowb == 256 ? (r & 7) << 1 : ((r >> 1) & 3) << 1; }
 
-// LDS-DMA of one 1-KiB piece (NT: non-temporal, aux 2, for the once-read K/V rows: MI355X_MICROARCH.md
-// nt-weights; q, read by every split of its head, keeps the default policy): lane i's 16 bytes at gsrc
-// land at LDS byte lds + 16 i. Inline asm, so the compiler neither counts nor drains it: the kernel waits with
-// counted vmcnt, and issues no other vector-memory load while a piece is in flight.
-template <bool NT>
-__device__ __forceinline__ void am_dma(const void* gsrc, unsigned lds) {
-    unsigned keep;
-    if constexpr (NT)
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off nt\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds)
-            : "memory");
-    else
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %2\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "v"(gsrc), "s"(lds)
-            : "memory");
-}
-template <int N>
-__device__ __forceinline__ void am_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ uint2 am_tr_read(unsigned lds_addr) {
-    uint2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
-typedef _Float16 am_half8 __attribute__((ext_vector_type(8)));
-typedef float am_float4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ am_float4 am_mfma(const u32x4& a, const u32x4& b, am_float4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(am_half8, a), __builtin_bit_cast(am_half8, b), c,
-                                                  0, 0, 0);
-}
-// fp32 -> fp16 hi + mid + lo: v - hi - mid - lo is below 2^-33 |v| (or the fp16 subnormal step 2^-24 for |v| <
-// 2^-9), so the three exact fp16 products of an MFMA carry the fp32 operand in full (a hi + lo pair carries 22
-// bits: measured at C4 position 1, where 32 layers amplify every rounding of the new K/V rows, the pair put the
-// logits 1.51e-3 from a float64 restatement against 1.04 - 1.34e-3 for fp32 summation orders)
-__device__ __forceinline__ void am_split3(float v, __half& hi, __half& mid, __half& lo) {
-    hi = __float2half_rn(v);
-    const float r = v - __half2float(hi);  // exact
-    mid = __float2half_rn(r);
-    lo = __float2half_rn(r - __half2float(mid));
-}
+// The fp16 cache. A row of S MFMA kt is key 16 kt + i; K fragment = the row's 16 bytes at d = 32 db + 8 g; Vᵀ 16-d
+// tile t = two ds_read_b64_tr_b16, whose 4-row blocks are keys 4 g .. +3 and 16 + 4 g .. +3: lane 16 g + 4 q + p
+// addresses row 4 g + q [+ 16], d 16 t + 4 p .. +3.
+struct AmF16 {
+    using KT = __half;
+    static constexpr int EB = 2;       // bytes per element
+    static constexpr int MAXBUF = 2;   // ring slots per wave: 2 tiles of 16 KiB (hd 128) in flight
+    static constexpr int VR = 2;       // transposed reads per 16-d tile
+    __device__ __forceinline__ static int swz_k(int r, int rowb) { return lm_swz_k16(r, rowb); }
+    __device__ __forceinline__ static int swz_v(int r, int rowb) { return lm_swz_v16(r, rowb); }
+    __device__ __forceinline__ static int a_row(int kt, int i16) { return kt * 16 + i16; }
+    __device__ __forceinline__ static int acc_key(int t0, int g, int kt, int r) { return t0 + kt * 16 + 4 * g + r; }
+    __device__ __forceinline__ static u32x4 k_frag(const char* krow, int sw, int db, int g) {
+        return *reinterpret_cast<const u32x4*>(krow + ((4 * db + g) ^ sw) * 16);
+    }
+    template <int NT, int ROWB>
+    __device__ __forceinline__ static void v_read(unsigned vbase, int lane, uint2 (&x)[NT * VR]) {
+        const int g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+        const int r1 = 4 * g + q4, r2 = 16 + 4 * g + q4;
+        const unsigned a1 = vbase + r1 * ROWB + 8 * (p4 & 1), a2 = vbase + r2 * ROWB + 8 * (p4 & 1);
+        const int sw1 = swz_v(r1, ROWB), sw2 = swz_v(r2, ROWB);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int c = 2 * t + (p4 >> 1);
+            x[2 * t] = lm_tr16_read(a1 + ((c ^ sw1) * 16));
+            x[2 * t + 1] = lm_tr16_read(a2 + ((c ^ sw2) * 16));
+        }
+    }
+    __device__ __forceinline__ static u32x4 v_frag(const uint2* x, int t) {
+        return u32x4{x[2 * t].x, x[2 * t].y, x[2 * t + 1].x, x[2 * t + 1].y};
+    }
+};
 
 // The head's last-arriving workgroup merges its ns live split partials into out (attention.h attn_merge's
 // arithmetic: M = max m_i, w_i = e^{m_i - M}, out = sum w_i o_i / sum w_i l_i). A thread pair owns 4 consecutive
@@ -173,14 +156,15 @@ __device__ __forceinline__ void am_merge(const float* part, float* out, int kvh,
     }
 }
 
-// grid: n_kv_heads (every sequence's) * max_splits workgroups of 256 threads; a.ppwg = kAmWgKeys * tpw (the
-// split length), NBUF = min(tpw, 2) ring slots per wave. The K/V rows of a split are read once (clamped to pos:
-// rows past the live context re-read row pos, an L2 hit, and are masked).
-template <int HD, int G, int NBUF>
-__global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__half> a) {
-    using Geo = AmGeo<HD, G>;
+// The kernel body. grid: n_kv_heads (every sequence's) * max_splits workgroups of 256 threads; a.ppwg = kAmWgKeys *
+// tpw (the split length), NBUF <= min(tpw, F::MAXBUF) ring slots per wave. The K/V rows of a split are read once
+// (clamped to pos: rows past the live context re-read row pos, an L2 hit, and are masked).
+template <class F, int HD, int G, int NBUF>
+__device__ __forceinline__ void am_attn(AttnArgs<typename F::KT> a) {
+    using Geo = AmGeo<F, HD, G>;
     constexpr int ND = Geo::ND, NT = Geo::NT, P = Geo::PIECES;
     constexpr int WB = Geo::template wave_bytes<NBUF>();
+    static_assert(NBUF >= 1 && NBUF <= F::MAXBUF && NBUF * P + Geo::QP <= 63, "vmcnt is 6 bits");
     __shared__ __attribute__((aligned(1024))) char sm[kAmWaves * WB];
     __shared__ int last;
     if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 4] = __builtin_amdgcn_s_memrealtime();
@@ -201,8 +185,8 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
     const unsigned wbase = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)wimg;
     const unsigned qbase = wbase, tbase = wbase + Geo::QB;
     const int ch = a.cache_heads > 0 ? kvh % a.cache_heads : kvh / a.kv_group;
-    const __half* kc = a.k + (long long)ch * a.head_stride;
-    const __half* vc = a.v + (long long)ch * a.head_stride;
+    const typename F::KT* kc = a.k + (long long)ch * a.head_stride;
+    const typename F::KT* vc = a.v + (long long)ch * a.head_stride;
 
     // tile j of this wave into ring slot j % NBUF: K pieces 0 .. P/2-1, V pieces P/2 .. P-1; lane i of a piece:
     // row (piece rows) + i / CPR, physical chunk i % CPR <- logical chunk (i % CPR) ^ swizzle(row)
@@ -214,28 +198,27 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
             const bool isv = p >= P / 2;
             const int jj = isv ? p - P / 2 : p;
             const int r = jj * (1024 / Geo::ROWB) + lane / Geo::CPR;
-            const int c = (lane % Geo::CPR) ^ (isv ? am_swz_v(r, Geo::ROWB) : am_swz_k(r, Geo::ROWB));
-            const __half* src = (isv ? vc : kc) + (long long)min(t0 + r, pos) * a.pos_stride + c * 8;
-            am_dma<true>(src, base + (isv ? Geo::IMG : 0) + (unsigned)(jj * 1024));
+            const int c = (lane % Geo::CPR) ^ (isv ? F::swz_v(r, Geo::ROWB) : F::swz_k(r, Geo::ROWB));
+            const typename F::KT* src = (isv ? vc : kc) + (long long)min(t0 + r, pos) * a.pos_stride + c * (16 / F::EB);
+            lm_dma<true>(src, base + (isv ? Geo::IMG : 0) + (unsigned)(jj * 1024));
         }
     };
-    // q of the kv head's G query heads (fp32, contiguous): QP pieces, clamped inside the vector
+    // q of the kv head's G query heads (fp32, contiguous): QP pieces, clamped inside the vector; read by every
+    // split of its head, so the default cache policy
     {
         const float* qs = a.q + (size_t)kvh * G * HD;
 #pragma unroll
         for (int p = 0; p < Geo::QP; ++p)
-            am_dma<false>(qs + min(p * 256 + lane * 4, G * HD - 4), qbase + (unsigned)(p * 1024));
+            lm_dma<false>(qs + min(p * 256 + lane * 4, G * HD - 4), qbase + (unsigned)(p * 1024));
     }
-    if (nl > 0) issue(0);
-    if (NBUF > 1 && nl > 1) issue(1);
-    if (NBUF > 1 && nl > 1)  // q landed (the tiles may still be in flight)
-        am_wait_vm<2 * P>();
-    else if (nl > 0)
-        am_wait_vm<P>();
-    else
-        am_wait_vm<0>();
+    static_assert(F::MAXBUF <= 4, "the ring's first fill below names each slot");
+    if (nl > 0) issue(0);  // (one statement per slot: as a loop over the slots hipcc schedules the whole kernel
+    if (NBUF > 1 && nl > 1) issue(1);  //  differently: 228 VGPRs for 224 at fp16 hd 128, and a slower launch at C4)
+    if (NBUF > 2 && nl > 2) issue(2);
+    if (NBUF > 3 && nl > 3) issue(3);
+    lm_wait_groups<P, NBUF>(0, nl);  // q landed (the tiles may still be in flight)
     // Qᵀ as the B operand: lane l = query column l & 15 (q head kvh * G + col for col < G, else zero), d = 32 db +
-    // 8 g .. +7, fp32 -> hi + lo
+    // 8 g .. +7, fp32 -> hi + mid + lo
     u32x4 qh[ND], qm[ND], ql[ND];
 #pragma unroll
     for (int db = 0; db < ND; ++db) {
@@ -255,57 +238,45 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
         qm[db] = *reinterpret_cast<const u32x4*>(hm);
         ql[db] = *reinterpret_cast<const u32x4*>(hl);
     }
-    am_float4 o[NT];
+    lm_float4 o[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) o[t] = am_float4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int t = 0; t < NT; ++t) o[t] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
     float mx = -INFINITY, l = 0.0f;
     if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
 
     for (int j = 0; j < nl; ++j) {
-        // tile j landed (tile j + 1 may still be in flight)
-        if (NBUF > 1 && j + 1 < nl)
-            am_wait_vm<P>();
-        else
-            am_wait_vm<0>();
+        // tile j landed (up to NBUF - 1 later tiles may still be in flight)
+        lm_wait_groups<P, NBUF - 1>(j + 1, nl);
         const int t0 = s0 + (kAmWaves * j + wave) * kAmKeys;
         const char* kimg = wimg + Geo::QB + (j % NBUF) * Geo::TILE;
         const unsigned vbase = tbase + (unsigned)((j % NBUF) * Geo::TILE) + Geo::IMG;
-        // Sᵀ[key][query] for keys t0 + 16 kt + (0..15)
-        am_float4 sacc[2];
+        // Sᵀ[key][query]: A row i16 of MFMA kt is key F::a_row(kt, i16) of the tile
+        lm_float4 sacc[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-            sacc[kt] = am_float4{0.0f, 0.0f, 0.0f, 0.0f};
-            const int r = kt * 16 + i16;
+            sacc[kt] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
+            const int r = F::a_row(kt, i16);
             const char* krow = kimg + r * Geo::ROWB;
+            const int sw = F::swz_k(r, Geo::ROWB);
 #pragma unroll
             for (int db = 0; db < ND; ++db) {
-                const u32x4 kf = *reinterpret_cast<const u32x4*>(krow + ((4 * db + g) ^ am_swz_k(r, Geo::ROWB)) * 16);
-                sacc[kt] = am_mfma(kf, qh[db], sacc[kt]);
-                sacc[kt] = am_mfma(kf, qm[db], sacc[kt]);
-                sacc[kt] = am_mfma(kf, ql[db], sacc[kt]);
+                const u32x4 kf = F::k_frag(krow, sw, db, g);
+                sacc[kt] = lm_mfma(kf, qh[db], sacc[kt]);
+                sacc[kt] = lm_mfma(kf, qm[db], sacc[kt]);
+                sacc[kt] = lm_mfma(kf, ql[db], sacc[kt]);
             }
         }
-        // Vᵀ 16-d tile dt: lane 16 g + 4 q + p addresses row (4 g + q) [+16], d 16 dt + 4 p .. +3 (issued before the
-        // softmax so the LDS reads overlap it)
-        const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-        const int r1 = 4 * g + q4, r2 = 16 + 4 * g + q4;
-        const unsigned a1 = vbase + r1 * Geo::ROWB + 8 * (p4 & 1), a2 = vbase + r2 * Geo::ROWB + 8 * (p4 & 1);
-        const int sw1 = am_swz_v(r1, Geo::ROWB), sw2 = am_swz_v(r2, Geo::ROWB);
-        uint2 x1[NT], x2[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int c = 2 * t + (p4 >> 1);
-            x1[t] = am_tr_read(a1 + ((c ^ sw1) * 16));
-            x2[t] = am_tr_read(a2 + ((c ^ sw2) * 16));
-        }
-        // lane holds keys t0 + 16 kt + 4 g + r of its query column (mha_kernel.cpp:51-60: s = (q . k) * scale)
+        // the Vᵀ operand's transposed reads (issued before the softmax so the LDS reads overlap it)
+        uint2 x[NT * F::VR];
+        F::template v_read<NT, Geo::ROWB>(vbase, lane, x);
+        // lane holds keys F::acc_key(t0, g, kt, r) of its query column (mha_kernel.cpp:51-60: s = (q . k) * scale)
         float sv[8];
         float cmax = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int key = t0 + kt * 16 + 4 * g + r;
+                const int key = F::acc_key(t0, g, kt, r);
                 const float v = key <= pos ? sacc[kt][r] * a.scale : -INFINITY;
                 sv[kt * 4 + r] = v;
                 cmax = fmaxf(cmax, v);
@@ -330,31 +301,16 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
         const u32x4 pfh = *reinterpret_cast<const u32x4*>(ph);
         const u32x4 pfm = *reinterpret_cast<const u32x4*>(pm);
         const u32x4 pfl = *reinterpret_cast<const u32x4*>(pl);
-        // the transposed reads landed. Their registers are named in the wait, so the compiler neither reads nor copies
-        // them above it (an asm load's outputs count as written at its end: cdna_hip_programming.md "What hipcc does
-        // not do" 1(ii); without this, copies into the MFMA operand raced the LDS returns under DMA load)
-        if constexpr (NT == 8)
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(x1[0]), "+v"(x1[1]), "+v"(x1[2]), "+v"(x1[3]), "+v"(x1[4]), "+v"(x1[5]), "+v"(x1[6]),
-                           "+v"(x1[7]), "+v"(x2[0]), "+v"(x2[1]), "+v"(x2[2]), "+v"(x2[3]), "+v"(x2[4]), "+v"(x2[5]),
-                           "+v"(x2[6]), "+v"(x2[7])
-                         :
-                         : "memory");
-        else
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(x1[0]), "+v"(x1[1]), "+v"(x1[2]), "+v"(x1[3]), "+v"(x2[0]), "+v"(x2[1]), "+v"(x2[2]),
-                           "+v"(x2[3])
-                         :
-                         : "memory");
+        lm_tr_landed(x);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             o[t] *= corr;
-            const u32x4 vf = u32x4{x1[t].x, x1[t].y, x2[t].x, x2[t].y};
-            o[t] = am_mfma(vf, pfh, o[t]);
-            o[t] = am_mfma(vf, pfm, o[t]);
-            o[t] = am_mfma(vf, pfl, o[t]);
+            const u32x4 vf = F::v_frag(x, t);
+            o[t] = lm_mfma(vf, pfh, o[t]);
+            o[t] = lm_mfma(vf, pfm, o[t]);
+            o[t] = lm_mfma(vf, pfl, o[t]);
         }
-        // the slot's LDS reads are done (lgkmcnt(0) above): refill it with tile j + NBUF
+        // the slot's LDS reads are done (lgkmcnt(0) in lm_tr_landed): refill it with tile j + NBUF
         if (j + NBUF < nl) issue(j + NBUF);
     }
     if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
@@ -364,7 +320,7 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
     float* fo = reinterpret_cast<float*>(wimg);  // [NT][64 lanes][4]
     float* fml = fo + NT * 64 * 4;               // [64] mx, then [64] l
 #pragma unroll
-    for (int t = 0; t < NT; ++t) *reinterpret_cast<am_float4*>(fo + (t * 64 + lane) * 4) = o[t];
+    for (int t = 0; t < NT; ++t) *reinterpret_cast<lm_float4*>(fo + (t * 64 + lane) * 4) = o[t];
     fml[lane] = mx;
     fml[64 + lane] = l;
     __syncthreads();
@@ -382,10 +338,10 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
     }
     const bool publish = a.defer_merge == 0;
     for (int t = wave; t < NT; t += kAmWaves) {
-        am_float4 acc = am_float4{0.0f, 0.0f, 0.0f, 0.0f};
+        lm_float4 acc = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int w = 0; w < kAmWaves; ++w)
-            acc += *reinterpret_cast<const am_float4*>(reinterpret_cast<const float*>(sm + w * WB) + (t * 64 + lane) * 4) *
+            acc += *reinterpret_cast<const lm_float4*>(reinterpret_cast<const float*>(sm + w * WB) + (t * 64 + lane) * 4) *
                    w4[w];
         if (i16 < G) {  // lane holds d = 16 t + 4 g + r of q head kvh * G + i16
             const size_t row = ((size_t)(kvh * G + i16) * a.max_splits + wgs) * (HD + kAttnPartPad);
@@ -427,6 +383,11 @@ __global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__hal
             am_merge<HD, G, 16>(a.part, a.out, kvh, a.max_splits, ns);
         if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime();
     }
+}
+
+template <int HD, int G, int NBUF>
+__global__ void __launch_bounds__(64 * kAmWaves) attn_mfma_kernel(AttnArgs<__half> a) {
+    am_attn<AmF16, HD, G, NBUF>(a);
 }
 
 // Tiles per wave for a launch over n_kv kv heads (every sequence's) of a T-position cache: one workgroup per CU

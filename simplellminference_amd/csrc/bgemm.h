@@ -35,11 +35,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_mfma.h"
 
 namespace sli {
-
-typedef _Float16 bg_half8 __attribute__((ext_vector_type(8)));
-typedef float bg_float4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBgThreads = 1024;
 constexpr int kBgWaves = kBgThreads / 64;
@@ -147,11 +145,6 @@ inline size_t bg_part_bytes(const BgPlan& p) {
 inline size_t bg_ws_bytes(const BgPlan& p) { return bg_part_bytes(p) + sizeof(unsigned) * (size_t)p.groups + 256; }
 
 // ---------------------------------------------------------------- device side
-__device__ __forceinline__ bg_float4 bg_mfma(const u32x4& a, const u32x4& b, bg_float4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(bg_half8, a), __builtin_bit_cast(bg_half8, b), c,
-                                                  0, 0, 0);
-}
-
 __device__ __forceinline__ float bg_load_sc1(const float* base, unsigned bytes, unsigned off) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 16 /* sc1 */));
@@ -322,7 +315,7 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
 
     const unsigned long long t_staged = in.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     // ---- 5. stream the tiles
-    bg_float4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    lm_float4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const u32x4* wimg = img + (size_t)(wb0 - kb0) * 64 + lane;
     auto mfma_step = [&](int k, const WV(&w)[kBgU]) {
         const int c = k - (k / cpt) * cpt;
@@ -330,9 +323,9 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
         for (int u = 0; u < kBgU; ++u) {
             const int r = c * kBgU + u;
             if constexpr (I8) {
-                if (r < wnb) acc = bg_mfma(i8x8_to_f16(w[u].x, w[u].y), wimg[(size_t)r * 64], acc);
+                if (r < wnb) acc = lm_mfma(i8x8_to_f16(w[u].x, w[u].y), wimg[(size_t)r * 64], acc);
             } else {
-                if (r < wnb) acc = bg_mfma(w[u], wimg[(size_t)r * 64], acc);
+                if (r < wnb) acc = lm_mfma(w[u], wimg[(size_t)r * 64], acc);
             }
         }
     };
@@ -346,7 +339,7 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Pb[wave * 128 + ((lane >> 4) * 4 + r) * 8 + (lane & 7)] = acc[r];
             }
-            acc = bg_float4{0.0f, 0.0f, 0.0f, 0.0f};
+            acc = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
             __syncthreads();
             if (wave == (j & (kBgWaves - 1))) {  // tile j's 16 wave partials, summed in wave order
                 const int i = lane >> 3, b = lane & 7;

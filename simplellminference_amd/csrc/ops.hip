@@ -189,40 +189,59 @@ static int matmul_dispatch(const float* x, const WT* w, const float* rscale, flo
 }
 
 int attn_wg_positions(int kv_dtype, int head_dim) {
-    // an FP8 cache runs attn_mfma_f8_launch only, whose split is never shorter than the fp32 kernel's (the partial
+    // an FP8 cache runs attn_mfma_launch only, whose split is never shorter than the fp32 kernel's (the partial
     // buffer's own split): that length, stated explicitly
     if (kv_dtype == SLI_DT_F8E4M3) return kAttnSlots * (64 / (head_dim / 4));
     const int epv = kv_dtype == SLI_DT_F16 ? 8 : 4;
     return kAttnSlots * (64 / (head_dim / epv));
 }
 
-// The MFMA decode attention (attn_mfma.h) for an fp16 cache. SLI_ATTN_MFMA=0 at build time keeps the
-// register-staged kernel (attention.h) everywhere, for an A/B variant build.
+// The MFMA decode attention (attn_mfma.h am_attn; the cache formats: AmF16 there, AmF8 in attn_mfma_f8.h).
+// SLI_ATTN_MFMA=0 at build time keeps the register-staged kernel (attention.h) everywhere for an fp16 cache, for an
+// A/B variant build. SLI_ATTN_F8_RING: the FP8 cache's largest ring depth (the A/B of depth 2 and 4).
 #ifndef SLI_ATTN_MFMA
 #define SLI_ATTN_MFMA 1
 #endif
+#ifndef SLI_ATTN_F8_RING
+#define SLI_ATTN_F8_RING 2
+#endif
+// every 16-byte DMA piece aligned: cache bases, row and head strides (in bytes), q
+template <typename KT>
+static bool attn_mfma_aligned(const AttnArgs<KT>& a) {
+    return (uintptr_t)a.k % 16 == 0 && (uintptr_t)a.v % 16 == 0 && (uintptr_t)a.q % 16 == 0 &&
+           a.pos_stride * (long long)sizeof(KT) % 16 == 0 && a.head_stride * (long long)sizeof(KT) % 16 == 0;
+}
 static bool attn_mfma_ok(const AttnArgs<__half>& a, int g) {
     // the batch-1 MHA step (C1 / C3) merges its splits in the wo GEMV's input staging (defer_merge 1), where the
     // register-staged kernel's 8.5 us stays ahead (tools/attn_mfma_lab: 9.1 vs 10.6 us at C1, both ramp-bound: 131 KB
     // per CU); every other fp16 attention (GQA batches and shards, op level) runs on the matrix cores
     if (!SLI_ATTN_MFMA || a.cache_heads != 0 || !(g == 1 || g == 2 || g == 4 || g == 8) || a.defer_merge == 1)
         return false;
-    // every 16-byte DMA piece aligned: cache bases, row and head strides, q
-    return (uintptr_t)a.k % 16 == 0 && (uintptr_t)a.v % 16 == 0 && (uintptr_t)a.q % 16 == 0 && a.pos_stride % 8 == 0 &&
-           a.head_stride % 8 == 0;
+    return attn_mfma_aligned(a);
 }
-template <int HD, int G>
-static void attn_mfma_go(const AttnArgs<__half>& a, int blocks, int nbuf, hipStream_t s) {
-    if (nbuf == 1)
-        hipLaunchKernelGGL((attn_mfma_kernel<HD, G, 1>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
-    else
-        hipLaunchKernelGGL((attn_mfma_kernel<HD, G, 2>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
+// the launch ladder of each kernel name (two names, so two ladders); ring depth nbuf rounded down to an instantiated
+// one: 1, 2, or (FP8 cache only) 4
+template <typename KT, int HD, int G>
+static void attn_mfma_go(const AttnArgs<KT>& a, int blocks, int nbuf, hipStream_t s) {
+    const dim3 grid(blocks), wg(64 * kAmWaves);
+    if constexpr (std::is_same<KT, __half>::value) {
+        if (nbuf == 1)
+            hipLaunchKernelGGL((attn_mfma_kernel<HD, G, 1>), grid, wg, 0, s, a);
+        else
+            hipLaunchKernelGGL((attn_mfma_kernel<HD, G, 2>), grid, wg, 0, s, a);
+    } else {
+        if (nbuf == 1)
+            hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 1>), grid, wg, 0, s, a);
+        else if (nbuf < 4)
+            hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 2>), grid, wg, 0, s, a);
+        else
+            hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 4>), grid, wg, 0, s, a);
+    }
 }
 // Split geometry: one workgroup per CU over the whole context (attn_mfma_tpw), its splits merged by the head's
-// last-arriving workgroup inside the launch (a requested merge launch, defer_merge 2, becomes that in-launch
-// merge: the same result in out).
-template <int HD>
-static int attn_mfma_launch(AttnArgs<__half> a, int g, int T, hipStream_t s) {
+// last-arriving workgroup inside the launch (a.defer_merge 0). ring: the most tiles a wave keeps in flight.
+template <typename KT, int HD>
+static int attn_mfma_launch(AttnArgs<KT> a, int g, int T, int ring, hipStream_t s) {
     // the partial buffer (mha_part_bytes) holds ceil(T / pf) splits per head, pf = the fp32 kernel's positions per
     // workgroup; at head_dim 64 that is 256 keys, so one tile per wave (128 keys) over a longer context would store
     // past it (the round-5 fault record): the split is never shorter than pf
@@ -232,55 +251,12 @@ static int attn_mfma_launch(AttnArgs<__half> a, int g, int T, hipStream_t s) {
     a.max_splits = (T + a.ppwg - 1) / a.ppwg;
     if (a.max_splits > kAttnMaxWgSplits) return fail(SLI_ERR_SHAPE, "mha: context too long for the split merge");
     if (a.max_splits > (T + pf - 1) / pf) return fail(SLI_ERR_SHAPE, "mha: more splits than the partial buffer holds");
-    if (a.defer_merge == 2) a.defer_merge = 0;
-    const int blocks = a.n_kv_heads * a.max_splits, nbuf = tpw > 1 ? 2 : 1;
+    const int blocks = a.n_kv_heads * a.max_splits, nbuf = std::min(tpw, ring);
     switch (g) {
-        case 1: attn_mfma_go<HD, 1>(a, blocks, nbuf, s); break;
-        case 2: attn_mfma_go<HD, 2>(a, blocks, nbuf, s); break;
-        case 4: attn_mfma_go<HD, 4>(a, blocks, nbuf, s); break;
-        default: attn_mfma_go<HD, 8>(a, blocks, nbuf, s); break;
-    }
-    SLI_HIP(hipGetLastError());
-    return SLI_OK;
-}
-
-// The FP8 cache's attention (attn_mfma_f8.h): the same split geometry and the same two host checks as
-// attn_mfma_launch; nothing else runs an FP8 cache, so what that kernel cannot take is an error here. The ring depth
-// is min(tiles per wave, SLI_ATTN_F8_RING) rounded down to 1, 2 or 4 (the A/B of depth 2 and 4).
-#ifndef SLI_ATTN_F8_RING
-#define SLI_ATTN_F8_RING 2
-#endif
-template <int HD, int G>
-static void attn_mfma_f8_go(const AttnArgs<f8e4m3>& a, int blocks, int nbuf, hipStream_t s) {
-    if (nbuf == 1)
-        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 1>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
-    else if (nbuf < 4)
-        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 2>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
-    else
-        hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 4>), dim3(blocks), dim3(64 * kAmWaves), 0, s, a);
-}
-template <int HD>
-static int attn_mfma_f8_launch(AttnArgs<f8e4m3> a, int g, int T, hipStream_t s) {
-    if (!(g == 1 || g == 2 || g == 4 || g == 8))
-        return fail(SLI_ERR_SHAPE, "mha: heads per kv head must be 1, 2, 4 or 8");
-    if (a.cache_heads != 0 || a.defer_merge == 1)
-        return fail(SLI_ERR_ARG, "mha: an FP8 cache takes neither shared cache heads nor a merge in the consumer");
-    // every 16-byte DMA piece aligned: cache bases, row and head strides (in bytes), q
-    if ((uintptr_t)a.k % 16 || (uintptr_t)a.v % 16 || (uintptr_t)a.q % 16 || a.pos_stride % 16 || a.head_stride % 16)
-        return fail(SLI_ERR_ARG, "mha: an FP8 cache needs 16-byte aligned bases, row stride and head stride");
-    const int pf = attn_wg_positions(SLI_DT_F32, HD);  // the partial buffer's split (attn_mfma_launch)
-    const int tpw = std::max(attn_mfma_tpw(a.n_kv_heads, T, device_cus()), (pf + kAmWgKeys - 1) / kAmWgKeys);
-    a.ppwg = kAmWgKeys * tpw;
-    a.max_splits = (T + a.ppwg - 1) / a.ppwg;
-    if (a.max_splits > kAttnMaxWgSplits) return fail(SLI_ERR_SHAPE, "mha: context too long for the split merge");
-    if (a.max_splits > (T + pf - 1) / pf) return fail(SLI_ERR_SHAPE, "mha: more splits than the partial buffer holds");
-    a.defer_merge = 0;  // the head's last-arriving workgroup merges (a requested merge launch becomes that)
-    const int blocks = a.n_kv_heads * a.max_splits, nbuf = std::min(tpw, SLI_ATTN_F8_RING);
-    switch (g) {
-        case 1: attn_mfma_f8_go<HD, 1>(a, blocks, nbuf, s); break;
-        case 2: attn_mfma_f8_go<HD, 2>(a, blocks, nbuf, s); break;
-        case 4: attn_mfma_f8_go<HD, 4>(a, blocks, nbuf, s); break;
-        default: attn_mfma_f8_go<HD, 8>(a, blocks, nbuf, s); break;
+        case 1: attn_mfma_go<KT, HD, 1>(a, blocks, nbuf, s); break;
+        case 2: attn_mfma_go<KT, HD, 2>(a, blocks, nbuf, s); break;
+        case 4: attn_mfma_go<KT, HD, 4>(a, blocks, nbuf, s); break;
+        default: attn_mfma_go<KT, HD, 8>(a, blocks, nbuf, s); break;
     }
     SLI_HIP(hipGetLastError());
     return SLI_OK;
@@ -296,8 +272,16 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
                        head_stride, part, out, counters, pos_dev, pos, Hkv, 0, 1.0f / sqrtf((float)HD),
                        seq_heads > 0 ? seq_heads : Hkv, pos_seq_stride};
         a.cache_heads = cache_heads;
-        a.defer_merge = defer_merge;
-        return attn_mfma_f8_launch<HD>(a, H / Hkv, T, s);
+        const int g = H / Hkv;
+        // nothing else runs an FP8 cache, so what the MFMA kernel cannot take is an error here
+        if (!(g == 1 || g == 2 || g == 4 || g == 8))
+            return fail(SLI_ERR_SHAPE, "mha: heads per kv head must be 1, 2, 4 or 8");
+        if (cache_heads != 0 || defer_merge == 1)
+            return fail(SLI_ERR_ARG, "mha: an FP8 cache takes neither shared cache heads nor a merge in the consumer");
+        if (!attn_mfma_aligned(a))
+            return fail(SLI_ERR_ARG, "mha: an FP8 cache needs 16-byte aligned bases, row stride and head stride");
+        a.defer_merge = 0;  // the head's last-arriving workgroup merges (a requested merge launch becomes that)
+        return attn_mfma_launch<KT, HD>(a, g, T, SLI_ATTN_F8_RING, s);
     } else {
     using Geo = AttnGeom<KT, HD>;
     constexpr int ppw_wg = Geo::PPWG;
@@ -310,7 +294,10 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
     a.defer_merge = defer_merge;
     int g = H / Hkv;
     if constexpr (std::is_same<KT, __half>::value) {
-        if (attn_mfma_ok(a, g)) return attn_mfma_launch<HD>(a, g, T, s);
+        if (attn_mfma_ok(a, g)) {
+            if (a.defer_merge == 2) a.defer_merge = 0;  // a requested merge launch becomes the in-launch merge
+            return attn_mfma_launch<KT, HD>(a, g, T, 2, s);
+        }
     }
     // GQA-4 as two GQA-2 groups per kv head: the 59-VGPR GQA-2 kernel at 8 waves/SIMD instead of the 128-VGPR GQA-4
     // one at 4; the two groups of a kv head are wg_splits blocks apart and read the same K/V rows. Deferred merges

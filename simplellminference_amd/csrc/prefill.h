@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "lds_mfma.h"
 #include "mxfp4.h"
 
 namespace sli {
@@ -40,25 +41,6 @@ struct PfState {
     int32_t p0;  // position of chunk row 0
     int32_t nv;  // valid chunk rows (the rest is padding: computed, never written to the cache)
 };
-
-typedef _Float16 pf_half8 __attribute__((ext_vector_type(8)));
-typedef float pf_float4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ pf_float4 pf_mfma(const u32x4& a, const u32x4& b, pf_float4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pf_half8, a), __builtin_bit_cast(pf_half8, b), c,
-                                                  0, 0, 0);
-}
-
-// fp32 -> fp16 hi + fp16 lo. v is pinned in a register first. Without that the split fuses into the expression that
-// produced v: a product a * b contracts into v_fma_mixlo_f16, once for the hi that is stored (the rounded product
-// converted) and once more inside the subtraction (the unrounded product). The two hi differ when the product sits
-// next to an fp16 tie, lo then has the wrong sign, and hi + lo is one fp16 ulp of hi (2^-11 relative) off: about
-// one SwiGLU or attention output in 10^4 (tests/test_gpu_prefill_kernels.py found it).
-__device__ __forceinline__ void pf_split(float v, __half& hi, __half& lo) {
-    asm("" : "+v"(v));
-    hi = __float2half_rn(v);
-    lo = __float2half_rn(v - __half2float(hi));
-}
 
 // ---------------------------------------------------------------- 1. embedding + RMSNorm / split
 // x[m] = emb[prompt[p0 + m]] (emb_kernel.cpp:4-21; padding rows repeat the last valid token)
@@ -129,25 +111,7 @@ __global__ void __launch_bounds__(256) pf_norm_split_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- 2. the GEMM
-// LDS-DMA of one 1-KiB fragment image: lane i's 16 bytes at gsrc land at LDS byte lds + 16 i (inline asm: the
-// compiler neither counts nor drains it; the kernel counts its own vmcnt).
-__device__ __forceinline__ void pf_dma(const void* gsrc, unsigned lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds)
-        : "memory");
-}
-template <int N>
-__device__ __forceinline__ void pf_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
+// The operand images travel by LDS-DMA (lds_mfma.h lm_dma: 1-KiB pieces, counted by the kernel's own vmcnt waits).
 template <typename WT>
 struct PgIn {
     const WT* W;        // [N][K] fp16 or int8 (row-major, PyTorch [out][in]; int8 row scales in the epilogue)
@@ -219,13 +183,13 @@ __device__ __forceinline__ u32x4 pg_i8_to_f16(uint2 w) { return i8x8_to_f16(w.x,
 template <int DPW>
 __device__ __forceinline__ void pg_wait_stages(int later) {
     switch (later) {
-        case 0: pf_wait_vm<0>(); break;
-        case 1: pf_wait_vm<1 * DPW>(); break;
-        case 2: pf_wait_vm<(2 * DPW > 63 ? 63 : 2 * DPW)>(); break;
-        case 3: pf_wait_vm<(3 * DPW > 63 ? 63 : 3 * DPW)>(); break;
-        case 4: pf_wait_vm<(4 * DPW > 63 ? 63 : 4 * DPW)>(); break;
-        case 5: pf_wait_vm<(5 * DPW > 63 ? 63 : 5 * DPW)>(); break;
-        default: pf_wait_vm<(6 * DPW > 63 ? 63 : 6 * DPW)>(); break;
+        case 0: lm_wait_vm<0>(); break;
+        case 1: lm_wait_vm<1 * DPW>(); break;
+        case 2: lm_wait_vm<(2 * DPW > 63 ? 63 : 2 * DPW)>(); break;
+        case 3: lm_wait_vm<(3 * DPW > 63 ? 63 : 3 * DPW)>(); break;
+        case 4: lm_wait_vm<(4 * DPW > 63 ? 63 : 4 * DPW)>(); break;
+        case 5: lm_wait_vm<(5 * DPW > 63 ? 63 : 5 * DPW)>(); break;
+        default: lm_wait_vm<(6 * DPW > 63 ? 63 : 6 * DPW)>(); break;
     }
 }
 
@@ -294,7 +258,7 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
             const bool isa = (wave * Geo::DPW + j) * 1024 < Geo::A_BYTES;
             if (((PG_LAB_SKIP & 1) && isa) || ((PG_LAB_SKIP & 2) && !isa)) continue;
 #endif
-            pf_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPW + j) * 1024));
+            lm_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPW + j) * 1024));
         }
     };
 
@@ -305,22 +269,22 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
         const bool tail = half_tail && s == ns - 1;
 #pragma unroll
         for (int j = 0; j < Geo::DPA; ++j)
-            pf_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPA + j) * 1024));
+            lm_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPA + j) * 1024));
     };
     auto issue_b = [&](int s) {
         const unsigned dst = ring_b + (unsigned)((s & 1) * Geo::B_BYTES);
         const bool tail = half_tail && s == ns - 1;
 #pragma unroll
         for (int j = 0; j < Geo::DPB; ++j)
-            pf_dma(src[Geo::DPA + j] + (size_t)s * adv[Geo::DPA + j] - (tail ? back[Geo::DPA + j] : 0),
+            lm_dma(src[Geo::DPA + j] + (size_t)s * adv[Geo::DPA + j] - (tail ? back[Geo::DPA + j] : 0),
                    dst + (unsigned)((wave * Geo::DPB + j) * 1024));
     };
     constexpr int AT = Geo::AT;
-    pf_float4 acc[AT][Geo::WPT];
+    lm_float4 acc[AT][Geo::WPT];
 #pragma unroll
     for (int a = 0; a < AT; ++a)
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
 
     // fragment read offsets: lane l reads row / column r = l & 15, k group kg = l >> 4 of each 32-k block
     const int kg = lane >> 4, r16 = lane & 15;
@@ -358,11 +322,11 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
 #pragma unroll
         for (int b = 0; b < Geo::WPT; ++b)
 #pragma unroll
-            for (int a = 0; a < AT; ++a) acc[a][b] = pf_mfma(af[a], bh[b], acc[a][b]);
+            for (int a = 0; a < AT; ++a) acc[a][b] = lm_mfma(af[a], bh[b], acc[a][b]);
 #pragma unroll
         for (int b = 0; b < Geo::WPT; ++b)
 #pragma unroll
-            for (int a = 0; a < AT; ++a) acc[a][b] = pf_mfma(af[a], bl[b], acc[a][b]);
+            for (int a = 0; a < AT; ++a) acc[a][b] = lm_mfma(af[a], bl[b], acc[a][b]);
     };
     if constexpr (Cfg::PIPE) {
         // set X holds even k-blocks, set Y odd ones (KBS is even; an int8 half stage has KBS / 2 = 2): per stage
@@ -384,9 +348,9 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
                 // B(s) was the first load of iteration s - 1; only that iteration's A pieces (if it issued any) were
                 // issued after it, and A(s) before it
                 if (s + Geo::SA - 2 < ns)
-                    pf_wait_vm<Geo::DPA>();
+                    lm_wait_vm<Geo::DPA>();
                 else
-                    pf_wait_vm<0>();
+                    lm_wait_vm<0>();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 if (s + 1 < ns) issue_b(s + 1);
@@ -442,9 +406,9 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
 #if defined(PG_LAB_MFMA) && PG_LAB_MFMA == 0  // tools/pgemm_lab only: no MFMA (data movement alone)
                     acc[a][b][0] += __uint_as_float(af[a][0] ^ bh[b][0] ^ bl[b][0]);
 #else
-                    acc[a][b] = pf_mfma(af[a], bh[b], acc[a][b]);
+                    acc[a][b] = lm_mfma(af[a], bh[b], acc[a][b]);
 #if !(defined(PG_LAB_MFMA) && PG_LAB_MFMA == 1)  // PG_LAB_MFMA 1: the hi MFMA only
-                    acc[a][b] = pf_mfma(af[a], bl[b], acc[a][b]);
+                    acc[a][b] = lm_mfma(af[a], bl[b], acc[a][b]);
 #endif
 #endif
                 }
@@ -502,20 +466,6 @@ struct PgGeoMx {
 
 // chunk swizzle of a weight image row (64 or 128 B): a k-block's fragment read is 16 rows x 16 B, 4 B per lane
 __device__ __forceinline__ int pg_mx_swz(int row, int row_bytes) { return row_bytes == 64 ? (row >> 2) & 3 : (row >> 1) & 7; }
-
-// LDS-DMA of 64 single bytes: lane i's byte at gsrc lands, zero-extended, in the dword at LDS byte lds + 4 i
-__device__ __forceinline__ void pf_dma_u8(const void* gsrc, unsigned lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_ubyte %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds)
-        : "memory");
-}
 
 // 8 e2m1 codes (element 2i in bits 3:0 of byte i) -> 8 fp16, exact and unscaled, in element order. The high byte
 // of the fp16 of magnitude code c is {00, 38, 3C, 3E, 40, 42, 44, 46}[c] (0, .5, 1, 1.5, 2, 3, 4, 6), the low byte 0.
@@ -614,16 +564,16 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_mx_kernel(PgInMx in, Epi 
         for (int j = 0; j < Geo::NPW; ++j) {
             const char* g = src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0);
             if (j < Geo::DPA + Geo::DPB)
-                pf_dma(g, dst + dsto[j]);
+                lm_dma(g, dst + dsto[j]);
             else
-                pf_dma_u8(g, dst + dsto[j]);
+                lm_dma_u8(g, dst + dsto[j]);
         }
     };
-    pf_float4 acc[AT][Geo::WPT];
+    lm_float4 acc[AT][Geo::WPT];
 #pragma unroll
     for (int a = 0; a < AT; ++a)
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
 
     const int kg = lane >> 4, r16 = lane & 15;
     const int sa = pg_mx_swz(r16, Geo::A_ROW), sb = pg_swz(r16, Geo::B_ROW);
@@ -660,15 +610,15 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_mx_kernel(PgInMx in, Epi 
                 bh[b] = *reinterpret_cast<const u32x4*>(img);
                 bl[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
             }
-            pf_float4 tmp[AT][Geo::WPT];
+            lm_float4 tmp[AT][Geo::WPT];
 #pragma unroll
             for (int b = 0; b < Geo::WPT; ++b)
 #pragma unroll
-                for (int a = 0; a < AT; ++a) tmp[a][b] = pf_mfma(af[a], bh[b], pf_float4{0.0f, 0.0f, 0.0f, 0.0f});
+                for (int a = 0; a < AT; ++a) tmp[a][b] = lm_mfma(af[a], bh[b], lm_float4{0.0f, 0.0f, 0.0f, 0.0f});
 #pragma unroll
             for (int b = 0; b < Geo::WPT; ++b)
 #pragma unroll
-                for (int a = 0; a < AT; ++a) tmp[a][b] = pf_mfma(af[a], bl[b], tmp[a][b]);
+                for (int a = 0; a < AT; ++a) tmp[a][b] = lm_mfma(af[a], bl[b], tmp[a][b]);
 #pragma unroll
             for (int a = 0; a < AT; ++a) {
                 float f[4];
@@ -991,14 +941,6 @@ struct PaGeo {
     static constexpr int PIECES = WAVE / 1024;   // DMA instructions per tile
     static constexpr int CPR = ROWB / 16;        // 16-B chunks per row
 };
-__device__ __forceinline__ int pa_swz_k(int r, int rowb) { return rowb == 256 ? r & 15 : (r >> 1) & 7; }
-__device__ __forceinline__ int pa_swz_v(int r, int rowb) { return rowb == 256 ? (r & 7) << 1 : ((r >> 1) & 3) << 1; }
-
-__device__ __forceinline__ uint2 pa_tr_read(unsigned lds_addr) {
-    uint2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-    return v;
-}
 
 template <int HD>
 __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a, const PfState* __restrict__ ps) {
@@ -1028,9 +970,9 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
         qh[db] = *reinterpret_cast<const u32x4*>(hh);
         ql[db] = *reinterpret_cast<const u32x4*>(hl);
     }
-    pf_float4 o[NT];
+    lm_float4 o[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) o[t] = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int t = 0; t < NT; ++t) o[t] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
     float mx = -INFINITY, l = 0.0f;
     char* kimg = sm + wave * G::WAVE;
     const unsigned kbase = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)kimg;
@@ -1046,23 +988,23 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
             const bool isv = j >= G::PIECES / 2;
             const int jj = isv ? j - G::PIECES / 2 : j;
             const int r = jj * (1024 / G::ROWB) + lane / G::CPR;
-            const int c = (lane % G::CPR) ^ (isv ? pa_swz_v(r, G::ROWB) : pa_swz_k(r, G::ROWB));
+            const int c = (lane % G::CPR) ^ (isv ? lm_swz_v16(r, G::ROWB) : lm_swz_k16(r, G::ROWB));
             const __half* src = (isv ? vc : kc) + (size_t)min(t0 + r, a.T - 1) * HD + c * 8;
-            pf_dma(src, (isv ? vbase : kbase) + (unsigned)(jj * 1024));
+            lm_dma(src, (isv ? vbase : kbase) + (unsigned)(jj * 1024));
         }
-        pf_wait_vm<0>();
+        lm_wait_vm<0>();
         // Sᵀ[key][query] for keys t0 + 16 kt + (0..15)
-        pf_float4 sacc[2];
+        lm_float4 sacc[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-            sacc[kt] = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+            sacc[kt] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
             const int r = kt * 16 + i16;
             const char* krow = kimg + r * G::ROWB;
 #pragma unroll
             for (int db = 0; db < ND; ++db) {
-                const u32x4 kf = *reinterpret_cast<const u32x4*>(krow + ((4 * db + g) ^ pa_swz_k(r, G::ROWB)) * 16);
-                sacc[kt] = pf_mfma(kf, qh[db], sacc[kt]);
-                sacc[kt] = pf_mfma(kf, ql[db], sacc[kt]);
+                const u32x4 kf = *reinterpret_cast<const u32x4*>(krow + ((4 * db + g) ^ lm_swz_k16(r, G::ROWB)) * 16);
+                sacc[kt] = lm_mfma(kf, qh[db], sacc[kt]);
+                sacc[kt] = lm_mfma(kf, ql[db], sacc[kt]);
             }
         }
         // lane holds keys t0 + 16 kt + 4 g + r of query mq
@@ -1100,21 +1042,21 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
         const int q4 = (lane & 15) >> 2, p4 = lane & 3;
         const int r1 = 4 * g + q4, r2 = 16 + 4 * g + q4;
         const unsigned a1 = vbase + r1 * G::ROWB + 8 * (p4 & 1), a2 = vbase + r2 * G::ROWB + 8 * (p4 & 1);
-        const int s1 = pa_swz_v(r1, G::ROWB), s2 = pa_swz_v(r2, G::ROWB);
-        uint2 x1[NT], x2[NT];
+        const int s1 = lm_swz_v16(r1, G::ROWB), s2 = lm_swz_v16(r2, G::ROWB);
+        uint2 x[2 * NT];  // tile t: rows r1 in x[2 t], rows r2 in x[2 t + 1]
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int c = 2 * t + (p4 >> 1);
-            x1[t] = pa_tr_read(a1 + ((c ^ s1) * 16));
-            x2[t] = pa_tr_read(a2 + ((c ^ s2) * 16));
+            x[2 * t] = lm_tr16_read(a1 + ((c ^ s1) * 16));
+            x[2 * t + 1] = lm_tr16_read(a2 + ((c ^ s2) * 16));
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lm_tr_landed(x);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             o[t] *= corr;
-            const u32x4 vf = u32x4{x1[t].x, x1[t].y, x2[t].x, x2[t].y};
-            o[t] = pf_mfma(vf, pfh, o[t]);
-            o[t] = pf_mfma(vf, pfl, o[t]);
+            const u32x4 vf = u32x4{x[2 * t].x, x[2 * t].y, x[2 * t + 1].x, x[2 * t + 1].y};
+            o[t] = lm_mfma(vf, pfh, o[t]);
+            o[t] = lm_mfma(vf, pfl, o[t]);
         }
     }
     // merge the 4 key splits: wave w publishes (mx, l, o) and merges 16-d tiles t = w, w + 4, ...
@@ -1124,7 +1066,7 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
     float* fl = fm + 4 * 64;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
-        *reinterpret_cast<pf_float4*>(fo + ((wave * NT + t) * 64 + lane) * 4) = o[t];
+        *reinterpret_cast<lm_float4*>(fo + ((wave * NT + t) * 64 + lane) * 4) = o[t];
     fm[wave * 64 + lane] = mx;
     fl[wave * 64 + lane] = l;
     __syncthreads();
@@ -1142,9 +1084,9 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
     }
     const float inv = 1.0f / L;
     for (int t = wave; t < NT; t += 4) {
-        pf_float4 acc = pf_float4{0.0f, 0.0f, 0.0f, 0.0f};
+        lm_float4 acc = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int w = 0; w < 4; ++w) acc += *reinterpret_cast<const pf_float4*>(fo + ((w * NT + t) * 64 + lane) * 4) * w4[w];
+        for (int w = 0; w < 4; ++w) acc += *reinterpret_cast<const lm_float4*>(fo + ((w * NT + t) * 64 + lane) * 4) * w4[w];
         // lane holds d = 16 t + 4 g + r of query mq
         const size_t idx = (size_t)mq * qs + (size_t)h * HD + t * 16 + 4 * g;
         __half hh[4], hl[4];
