@@ -467,6 +467,89 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
                      int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
                      sli_stream_t stream);
 
+/* ---------------------------------------------------------------- batched decode stages, for tests and labs
+ * One projection launch of the batched decode step (csrc/bgemm.h bgemm_kernel, 2 .. 8 sequences in lockstep; B = 1
+ * is taken too), without a model: device pointers and a stream. The entry is compiled into the engine's translation
+ * unit over the engine's own template arguments, so it launches the very code objects a model step launches: every
+ * (role, weight type, cache type, layout) here is one the engine runs, and nothing else can be asked for. Role and
+ * RMSNorm are paired as the engine pairs them: q/k/v, gate/up and logits take norm_w, store refuses it.
+ *
+ * The launch: sums[b][r] = sum_k W[r][k] * h[b][k] on MFMA with fp32 accumulation, h = x (store) or x * norm_w, the
+ * fp32 h carried as fp16 hi + lo. With a norm the per-sequence 1 / sqrt(mean(x^2) + eps) multiplies the finished sum
+ * (it commutes with the k-sum); then the row scale (w_row_scale[r], NULL: none), then the epilogue:
+ * SLI_BG_QKV      rows [q heads; k heads; v heads] of hd (64 or 128) each, hq % hkv == 0, (hq + 2 hkv) hd % 16 == 0.
+ *                 Rotate-half RoPE of the q and k rows at sequence b's position pos[b] with sin_t / cos_t
+ *                 [T][hd / 2]; q [B][hq hd] fp32; the k and v rows go to kc / vc, one layer's cache [B][hkv][T][hd]
+ *                 in kv_dtype (SLI_DT_F32 / F16 / F8E4M3), at row pos[b] of sequence b. pos is int32 [B] ON THE
+ *                 DEVICE; 0 <= pos[b] < T is the caller's contract (the host cannot check it).
+ * SLI_BG_GATE_UP  rows [gate (inter); up (inter)], inter % 8 == 0: act [B][inter] fp32 = sigmoid(g) * u (act_mode
+ *                 0) or SiLU(g) * u (1).
+ * SLI_BG_STORE    y[b][r] = (resid ? resid[b][r] : 0) + sum * scale for r < nrows; y and resid [B][ld] fp32,
+ *                 ld >= nrows; resid may be y (the engine's residual stream is updated in place).
+ * SLI_BG_LOGITS   logits[b][r] = sum for r < nrows, [B][ld]; keys_out [B][key_ld] uint64 receives, per sequence
+ *                 and workgroup group g < plan.groups, the largest key of the group's rows: (orderable image of
+ *                 the fp32 logit) << 32 | (0xFFFFFFFF - (vocab_off + r)), so the maximum over the groups names
+ *                 the largest logit and, among equals, the lowest row (-0 counts as +0). key_ld >= groups.
+ * Columns [nrows, ld) of y / logits, entries [groups, key_ld) of keys_out and every cache row but pos[b] are not
+ * written. The fields of the other roles are ignored. */
+enum { SLI_BG_QKV = 0, SLI_BG_GATE_UP = 1, SLI_BG_STORE = 2, SLI_BG_LOGITS = 3 };
+typedef struct {
+    int32_t role;
+    /* SLI_BG_QKV */
+    float* q;
+    void* kc;
+    void* vc;
+    int32_t kv_dtype;
+    const int32_t* pos;
+    const float* sin_t;
+    const float* cos_t;
+    int32_t hq, hkv, hd, T;
+    /* SLI_BG_GATE_UP */
+    float* act;
+    int32_t inter, act_mode;
+    /* SLI_BG_STORE */
+    float* y;
+    const float* resid;
+    float scale;
+    /* SLI_BG_STORE and SLI_BG_LOGITS */
+    int32_t nrows, ld;
+    /* SLI_BG_LOGITS */
+    float* logits;
+    uint64_t* keys_out;
+    int32_t vocab_off, key_ld;
+} sli_bgemm_epilogue;
+
+/* The plan of a launch, in / out. A workgroup owns tpw consecutive 16-row tiles and one of `splits` k-ranges;
+ * groups = ceil(tiles / tpw) and the grid is groups * splits workgroups. On entry tpw == 0 asks the engine's planner
+ * (bgemm.h bg_plan with the device's CU count: what a model of this shape runs); tpw != 0 forces (tpw, splits). A
+ * forced plan must satisfy what the kernel assumes, or the call is SLI_ERR_ARG and nothing is launched: tpw >= 1,
+ * splits >= 1; splits == 1 with a norm; splits > 1 only while (K / 32) / splits >= 16; ceil(K / 32 / splits) * 32 <=
+ * 4096 (the staging registers); the LDS image 1 KiB + ceil(K / 32 / splits) KiB + 16 KiB + tpw / 2 KiB within 160 KiB.
+ * On return every field holds what ran: step_width is the number of k-blocks a wave loads per step (2, 4 or 7: the
+ * kernel instantiation), lds_bytes the dynamic LDS, counter_off the byte offset of the groups' arrival counters
+ * (uint32 [groups]) inside the workspace. */
+typedef struct {
+    int32_t tpw, splits, groups, step_width, lds_bytes;
+    int64_t counter_off;
+} sli_bgemm_plan;
+
+/* Bytes of workspace a sli_batch_gemm call needs for a [rows][K] matrix (rows: (hq + 2 hkv) hd, 2 inter or nrows),
+ * and *plan resolved as the call would resolve it (no device needed): the split partials and arrival counters, plus
+ * for tiled != 0 the fragment-layout image of W. 0 when the shape or the forced plan is refused. */
+size_t sli_batch_gemm_workspace_bytes(int32_t rows, int32_t K, int32_t B, int32_t norm, int32_t w_dtype, int32_t tiled,
+                                      sli_bgemm_plan* plan);
+
+/* One bgemm_kernel launch. x [B][K] fp32, norm_w [K] fp32 or NULL (see the roles), W [rows][K] row-major in w_dtype
+ * (SLI_DT_F16 / SLI_DT_I8), K % 32 == 0, 1 <= B <= 8. tiled != 0: the call first re-lays W into the fragment layout
+ * inside the workspace with bg_tile_kernel and the epilogue's row map (RoPE pairs, gate/up pairs, the clamped last
+ * tile), as a model does when weights are placed, and streams that image. Every device pointer is 16-byte aligned.
+ * The arrival counters must be zero before the first call on a workspace (zero it once); a launch leaves them zero,
+ * so later calls with the same plan reuse the workspace as it is. Anything the kernel cannot take is SLI_ERR_ARG,
+ * decided before the device is touched. */
+int sli_batch_gemm(const float* x, const float* norm_w, float eps, const void* w, int w_dtype, const float* w_row_scale,
+                   int32_t tiled, int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan,
+                   void* workspace, size_t workspace_bytes, sli_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

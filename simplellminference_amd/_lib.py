@@ -54,6 +54,20 @@ class PgemmEpilogue(ctypes.Structure):  # sli_pgemm_epilogue
                 ("y", c_vp), ("resid", c_vp), ("ld", c_i32)]
 
 
+class BgemmEpilogue(ctypes.Structure):  # sli_bgemm_epilogue
+    _fields_ = [("role", c_i32),
+                ("q", c_vp), ("kc", c_vp), ("vc", c_vp), ("kv_dtype", c_i32), ("pos", c_vp), ("sin_t", c_vp),
+                ("cos_t", c_vp), ("hq", c_i32), ("hkv", c_i32), ("hd", c_i32), ("T", c_i32),
+                ("act", c_vp), ("inter", c_i32), ("act_mode", c_i32),
+                ("y", c_vp), ("resid", c_vp), ("scale", c_f),
+                ("nrows", c_i32), ("ld", c_i32),
+                ("logits", c_vp), ("keys_out", c_vp), ("vocab_off", c_i32), ("key_ld", c_i32)]
+
+
+class BgemmPlan(ctypes.Structure):  # sli_bgemm_plan
+    _fields_ = [(n, c_i32) for n in ("tpw", "splits", "groups", "step_width", "lds_bytes")] + [("counter_off", c_i64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "sli_version": (c_int, []),
@@ -145,6 +159,9 @@ _SIGS = {
     "sli_tp_group_set_prefill": (c_int, [c_vp, c_i32]),
     "sli_prefill_attn": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                  c_vp, c_vp]),
+    "sli_batch_gemm_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmPlan)]),
+    "sli_batch_gemm": (c_int, [c_vp, c_vp, c_f, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
+                               ctypes.POINTER(BgemmPlan), c_vp, c_sz, c_vp]),
     "sli_tp_group_create": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(c_vp)]),
     "sli_tp_group_destroy": (c_int, [c_vp]),
     "sli_tp_group_rank": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
@@ -189,6 +206,7 @@ def call(name: str, *args) -> int:
     if isinstance(rc, int) and name not in ("sli_version", "sli_mha_workspace_bytes", "sli_comm_id_bytes",
                                                  "sli_model_comm_handle_bytes",
                                                  "sli_matmul_batch_workspace_bytes",
-                                                 "sli_matmul_batch_i8_workspace_bytes"):
+                                                 "sli_matmul_batch_i8_workspace_bytes",
+                                                 "sli_batch_gemm_workspace_bytes"):
         check(rc, name)
     return rc

@@ -63,6 +63,11 @@ inline bool bg_seven_blocks(int splits, int K) {
     const int bpw = ((((K >> 5) + splits - 1) / splits) + kBgWaves - 1) / kBgWaves;
     return bpw >= SLI_BG_U7_FROM && bpw <= 7;
 }
+// The step width (the kBgU instantiation) launch_bgemm runs for a plan: the one place that decides it.
+inline int bg_launch_width(bool norm, int tpw, int splits, int K) {
+    if (bg_step_width(tpw) == 2) return 2;
+    return !norm && bg_seven_blocks(splits, K) ? 7 : 4;
+}
 
 struct BgIn {
     const float* x;       // [B][K] fp32 activations
@@ -641,14 +646,14 @@ hipError_t launch_bgemm(const WT* W, const BgIn& in_, const Epi& epi, const BgPl
     in.splits = p.splits;
     const dim3 grid(p.groups * p.splits);
     if (in.norm_w && p.splits != 1) return hipErrorInvalidValue;  // the fused RMS runs on one split only
-    const bool u2 = bg_step_width(p.tpw) == 2;
-    if (in.norm_w && u2)
+    const int width = bg_launch_width(in.norm_w != nullptr, p.tpw, p.splits, in.K);
+    if (in.norm_w && width == 2)
         hipLaunchKernelGGL((bgemm_kernel<Epi, true, 2, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else if (in.norm_w)
         hipLaunchKernelGGL((bgemm_kernel<Epi, true, 4, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
-    else if (u2)
+    else if (width == 2)
         hipLaunchKernelGGL((bgemm_kernel<Epi, false, 2, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
-    else if (bg_seven_blocks(p.splits, in.K))
+    else if (width == 7)
         hipLaunchKernelGGL((bgemm_kernel<Epi, false, 7, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);
     else
         hipLaunchKernelGGL((bgemm_kernel<Epi, false, 4, WT>), grid, dim3(kBgThreads), p.lds, s, W, in, epi);

@@ -2708,3 +2708,6 @@ int sli_tp_group_predict_batch(sli_tp_group* g, const int32_t* prompts, const in
 // the prefill stages as kernel-level entry points (sli.h "prefill stages, for tests and labs"), compiled here so
 // that they launch this translation unit's copies of the prefill kernels
 #include "prefill_ops.h"
+// likewise one batched decode projection (sli.h "batched decode stages, for tests and labs"): this translation
+// unit's copies of bgemm_kernel and bg_tile_kernel, the ones StepRecorder launches
+#include "bgemm_ops.h"

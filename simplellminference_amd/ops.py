@@ -348,6 +348,100 @@ def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int):
     return ohi, olo
 
 
+BG_ROLE_QKV, BG_ROLE_GATE_UP, BG_ROLE_STORE, BG_ROLE_LOGITS = 0, 1, 2, 3
+
+
+def batch_gemm_plan(rows: int, K: int, B: int, norm: bool, w_dtype=DT_F16, tiled: bool = False, plan=None):
+    """The plan sli_batch_gemm would run for a [rows, K] matrix and the workspace bytes it needs, without a device:
+    plan None asks the engine's planner, (tpw, splits) forces one. Returns (plan dict, bytes); bytes 0: refused."""
+    p = _lib.BgemmPlan(tpw=plan[0], splits=plan[1]) if plan else _lib.BgemmPlan()
+    nbytes = call("sli_batch_gemm_workspace_bytes", rows, K, B, int(norm), w_dtype, int(tiled), ctypes.byref(p))
+    return {n: getattr(p, n) for n, _ in p._fields_}, nbytes
+
+
+def _batch_gemm(x, norm_w, eps, w, row_scale, tiled, epi, rows, plan, ws):
+    """sli_batch_gemm. plan None: the engine's planner; (tpw, splits): forced. ws: a workspace of an earlier call
+    with the same plan, reused as it is (its arrival counters are zero again), or None for a fresh zeroed one.
+    Returns the plan that ran as a dict, with the workspace (a uint8 tensor) under "ws"."""
+    B, K = x.shape
+    if w.shape != (rows, K) or w.dtype not in (torch.float16, torch.int8) or x.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if (norm_w is not None and norm_w.numel() != K) or (row_scale is not None and row_scale.numel() != rows):
+        raise ValueError("Tensor with Wrong Dim!")
+    p = _lib.BgemmPlan(tpw=plan[0], splits=plan[1]) if plan else _lib.BgemmPlan()
+    q = _lib.BgemmPlan(tpw=p.tpw, splits=p.splits)
+    nbytes = call("sli_batch_gemm_workspace_bytes", rows, K, B, int(norm_w is not None), _DT[w.dtype], int(tiled),
+                  ctypes.byref(q))
+    if nbytes == 0:
+        raise _lib.SliError(1, "sli_batch_gemm_workspace_bytes", (_lib.load().sli_last_error() or b"").decode())
+    if ws is None:
+        ws = torch.zeros(nbytes, device=x.device, dtype=torch.uint8)
+    _dev(x, norm_w, w, row_scale, ws)
+    call("sli_batch_gemm", _p(x), _p(norm_w), eps, _p(w), _DT[w.dtype], _p(row_scale), int(tiled), K, B,
+         ctypes.byref(epi), ctypes.byref(p), _p(ws), ws.numel(), _s())
+    out = {n: getattr(p, n) for n, _ in p._fields_}
+    out["ws"] = ws
+    return out
+
+
+def batch_gemm_qkv(x, norm_w, eps: float, w, q, kc, vc, pos, sin_t, cos_t, hq: int, hkv: int, hd: int, row_scale=None,
+                   tiled: bool = False, plan=None, kv_dtype=None, ws=None):
+    """One bgemm_kernel launch with the q/k/v epilogue (fused RMSNorm, row scale, RoPE, K/V cache write): x [B, K]
+    fp32, W [(hq + 2 hkv) hd, K] fp16 or int8; q [>= B, hq hd] fp32; kc / vc one layer's cache [B, hkv, T, hd] (f32, f16,
+    or E4M3 codes with kv_dtype="f8"); pos int32 [B] on the device, 0 <= pos[b] < T. Returns the plan that ran."""
+    B = x.shape[0]
+    if kc.shape != vc.shape or kc.dtype != vc.dtype or kc.dim() != 4 or tuple(kc.shape[:2]) != (B, hkv) or kc.shape[3] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[2]
+    if q.dim() != 2 or q.shape[0] < B or q.shape[1] != hq * hd or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    if pos.dtype != torch.int32 or pos.numel() != B:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, pos, sin_t, cos_t)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_kv_dt(kc, kv_dtype), pos=pos.data_ptr(), sin_t=sin_t.data_ptr(),
+                           cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv, hd=hd, T=T)
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, (hq + 2 * hkv) * hd, plan, ws)
+
+
+def batch_gemm_gate_up(x, norm_w, eps: float, w, act, act_mode: int = 0, row_scale=None, tiled: bool = False,
+                       plan=None, ws=None):
+    """One bgemm_kernel launch with the gate/up epilogue: W [2 inter, K] = [gate; up]; act [>= B, inter] fp32 gets
+    sigmoid(g) * u (act_mode 0) or SiLU(g) * u (1) of the RMS-normalised x. Returns the plan that ran."""
+    inter = w.shape[0] // 2
+    if act.dim() != 2 or act.shape[0] < x.shape[0] or act.shape[1] != inter or act.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(act)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_GATE_UP, act=act.data_ptr(), inter=inter, act_mode=act_mode)
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, 2 * inter, plan, ws)
+
+
+def batch_gemm_store(x, w, y, resid=None, scale: float = 1.0, row_scale=None, tiled: bool = False, plan=None, ws=None):
+    """One bgemm_kernel launch with the wo / down epilogue: y [>= B, ld] = (resid or 0) + (W x) * row scale * scale for
+    the W.shape[0] rows; resid [B, ld] may be y itself. Returns the plan that ran."""
+    if y.dim() != 2 or y.shape[0] < x.shape[0] or y.dtype != torch.float32 or (resid is not None and resid.shape != y.shape):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_STORE, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                           scale=scale, nrows=w.shape[0], ld=y.shape[1])
+    return _batch_gemm(x, None, 0.0, w, row_scale, tiled, e, w.shape[0], plan, ws)
+
+
+def batch_gemm_logits(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int = 0, row_scale=None,
+                      tiled: bool = False, plan=None, ws=None):
+    """One bgemm_kernel launch with the LM-head epilogue: logits [>= B, ld] fp32 of the RMS-normalised x and, in keys_out
+    [>= B, key_ld] (int64 holding the uint64 keys), each workgroup group's largest argmax key per sequence. Returns
+    the plan that ran."""
+    if logits.dim() != 2 or logits.shape[0] < x.shape[0] or logits.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if keys_out.dim() != 2 or keys_out.shape[0] < x.shape[0] or keys_out.dtype != torch.int64:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(logits, keys_out)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_LOGITS, logits=logits.data_ptr(), keys_out=keys_out.data_ptr(),
+                           nrows=w.shape[0], ld=logits.shape[1], vocab_off=vocab_off, key_ld=keys_out.shape[1])
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, w.shape[0], plan, ws)
+
+
 def argmax(logits, out=None):
     """argmaxLayer::forward (argmax.cpp:7-17) on device: first index of the maximum."""
     out = torch.empty(1, device=logits.device, dtype=torch.int32) if out is None else out
