@@ -192,7 +192,8 @@ typedef struct {
                          SLI_ERR_SHAPE) */
     int32_t kv_dtype; /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_F8E4M3 (one byte per element, the rule at sli_quant_f8; with
                          fp16 and int8 weights at any batch, MXFP4 at batch 1, not fp32 weights: SLI_ERR_ARG; the launch
-                         graph only, prompts through the decode step, sli_model_get_kv returns the decoded fp32) */
+                         graph only; prompts through the decode step, or through the GEMM prefill after
+                         sli_model_set_prefill(SLI_PREFILL_GEMM_KV8); sli_model_get_kv returns the decoded fp32) */
     int32_t act_mode; /* 0: reference sigmoid(gate)*up (swiglu_kernel.cpp:12-13); 1: SiLU(gate)*up */
     int32_t tp_rank, tp_size;
     int32_t device;
@@ -265,7 +266,8 @@ int sli_model_get_state_seq(sli_model* m, int32_t seq, int32_t* pos, int32_t* to
                             int32_t* error);
 /* Prompt prefill (batch-1 models): positions 0 .. n-2 of the prompt run through the layers in chunks of up
  * to 256 positions, every projection one MFMA GEMM over the chunk and attention block-causal over the
- * cache (fp16 / int8 weights, MXFP4 after sli_model_set_prefill(SLI_PREFILL_GEMM), head_dim 64 / 128; otherwise
+ * cache (fp16 / int8 weights, MXFP4 after sli_model_set_prefill(SLI_PREFILL_GEMM), an FP8 K/V cache after
+ * sli_model_set_prefill(SLI_PREFILL_GEMM_KV8), head_dim 64 / 128; otherwise
  * through the decode step, teacher-forced; under
  * multi-process tensor parallelism every rank calls it, the chunk's residual rows all-reduced over RCCL
  * twice per layer), filling the K/V cache; the state is left at
@@ -273,15 +275,19 @@ int sli_model_get_state_seq(sli_model* m, int32_t seq, int32_t* pos, int32_t* to
  * greedy token exactly as the reference's token-by-token predict (model.cpp:157-165) would. */
 int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n);
 /* Which path sli_model_prefill takes for this model: 1 = chunked MFMA GEMMs (prefill.h), 0 = the decode step,
- * teacher-forced (fp32 weights, batch > 1, unsupported shapes, or a TP rank without an RCCL communicator). */
+ * teacher-forced (fp32 weights, batch > 1, unsupported shapes, a TP rank without an RCCL communicator, or an FP8 K/V
+ * cache under any mode but SLI_PREFILL_GEMM_KV8). */
 int sli_model_prefill_path(const sli_model* m);
 /* Which path the next prefill takes. SLI_PREFILL_AUTO (the default): the GEMM prefill where the model can take it,
  * except MXFP4 weights, which stay on the decode step; SLI_PREFILL_GEMM: the chunked MFMA prefill for every weight
  * type that has one (fp16, int8, MXFP4), SLI_ERR_STATE with the reason where the model cannot take it (fp32 weights,
  * an FP8 K/V cache, batch > 1, a TP rank without a communicator, unsupported shapes); SLI_PREFILL_DECODE: the teacher-forced decode
- * step for any model. May be changed between prefills; sli_model_prefill_path reports the outcome. The ranks of an
- * in-process group are set through sli_tp_group_set_prefill. */
-enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2 };
+ * step for any model; SLI_PREFILL_GEMM_KV8: SLI_PREFILL_GEMM for every model, and also accepted by a model with an
+ * FP8 E4M3 K/V cache that otherwise qualifies (the chunk's K/V rows are quantised in the q/k/v GEMM's epilogue and the
+ * chunk attention reads the codes; under the other three modes an FP8-cache model keeps the decode step, and
+ * SLI_PREFILL_GEMM its refusal). May be changed between prefills; sli_model_prefill_path reports the outcome. The
+ * ranks of an in-process group are set through sli_tp_group_set_prefill. */
+enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2, SLI_PREFILL_GEMM_KV8 = 3 };
 int sli_model_set_prefill(sli_model* m, int32_t mode);
 /* 1: the batch-1 decode step runs each layer's q/k/v projection and attention as ONE launch (qkv_attn.h: the
  * attention's K/V rows below the position stream while the projection runs; q and this step's K/V row are
@@ -415,7 +421,8 @@ typedef struct {
  * role 0, q/k/v: N = (hq + 2 hkv) * hd rows [q heads; k heads; v heads], hd 64 or 128. Row scale, then rotate-half
  *   RoPE of the q and k rows at position p0 + m (clamped to T - 1) with sin_t / cos_t [T][hd / 2]; q [M][hq * hd]
  *   fp32 is stored for every chunk row m < M; the K and V rows go to kc / vc, one layer's cache [hkv][T][hd] in
- *   kv_dtype (SLI_DT_F16 / SLI_DT_F32), at position p0 + m for m < nv and p0 + m < T only.
+ *   kv_dtype (SLI_DT_F16 / SLI_DT_F32 / SLI_DT_F8E4M3: codes by the rule at sli_quant_f8, two per 2-byte store), at
+ *   position p0 + m for m < nv and p0 + m < T only.
  * role 1, gate/up: N = 2 * inter rows [gate; up]; sigmoid(g) * u (act_mode 0) or SiLU(g) * u (1) as fp16 hi / lo
  *   in ahi / alo [M][inter].
  * role 2, wo / down: y[m][r] = (resid ? resid[m][r] : 0) + sum * row scale, y and resid [M][ld] fp32, ld >= N,
@@ -458,11 +465,12 @@ int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi,
 /* Block-causal attention of M chunk rows (32, 64, 128 or 256): row m of head h attends the cache rows 0 .. p0 + m
  * of kv head h / (hq / hkv); q [rows][hq * hd] fp32, kc / vc one layer's cache [hkv][T][hd] in kv_dtype, the result
  * as fp16 hi / lo in ohi / olo [rows][hq * hd]. hd 64 or 128, hq % hkv == 0, 0 <= p0 < T. SLI_DT_F16 runs
- * pf_attn_mfma_kernel, SLI_DT_F32 pf_attn_kernel. Rows at positions >= T are computed from clamped cache reads and
- * mean nothing.
+ * and SLI_DT_F8E4M3 run pf_attn_mfma_kernel (one body, the cache format a template argument), SLI_DT_F32
+ * pf_attn_kernel; the bases q, kc, vc, ohi, olo are 16-byte aligned for every dtype. Rows at positions >= T are
+ * computed from clamped cache reads and mean nothing.
  * Buffer contract: the fp32-cache kernel works in blocks of 64 chunk rows, so at M = 32 it reads q and writes
  * ohi / olo for rows 32 .. 63 as well. rows_allocated is the number of rows q, ohi and olo really hold; the call is
- * refused unless it covers the rows the kernel touches (M for an fp16 cache, M rounded up to 64 for fp32). */
+ * refused unless it covers the rows the kernel touches (M for an fp16 or FP8 cache, M rounded up to 64 for fp32). */
 int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
                      int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
                      sli_stream_t stream);

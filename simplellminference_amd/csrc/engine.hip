@@ -1114,22 +1114,13 @@ struct StepRecorder {
         if constexpr (!std::is_same<WT, float>::value) SLI_HIP((pg_allow_lds_all<Epi, WT>()));
         return SLI_OK;
     }
-    // an FP8 cache has no chunk attention and no prefill q/k/v epilogue: its prompts run through the decode step
-    static constexpr bool kPfKT = !std::is_same<KT, f8e4m3>::value;
     static int prepare_prefill(sli_model* m) {
-        if constexpr (kPfKT) {
-            SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
-            SLI_TRY(allow_pg<PgEpiResid>(m));
-            SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
-            return SLI_OK;
-        } else {
-            return fail(SLI_ERR_STATE, "an FP8 K/V cache cannot take the GEMM prefill");
-        }
+        SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
+        SLI_TRY(allow_pg<PgEpiResid>(m));
+        SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
+        return SLI_OK;
     }
     static int record_pf_phase(sli_model* m, int p, int M) {
-      if constexpr (!kPfKT) {  // (the discarded branch keeps PgEpiQKV / launch_pf_attn from being instantiated)
-        return fail(SLI_ERR_STATE, "an FP8 K/V cache cannot take the GEMM prefill");
-      } else {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
@@ -1158,7 +1149,7 @@ struct StepRecorder {
             SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
             PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
                               1.0f / sqrtf((float)hd)};
-            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.ps, s));  // fp16 cache: MFMA; fp32: VALU (prefill.h)
+            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.ps, s));  // fp16 / FP8 cache: MFMA; fp32: VALU (prefill.h)
             er.rscale = rs(w.wo_s);
             return pg(m, w.wo, w.wo_s, D, QD, f.hhi, f.hlo, er, M, 2);
         }
@@ -1166,7 +1157,6 @@ struct StepRecorder {
         SLI_TRY(pg(m, w.gu, w.gu_s, 2 * m->Il, D, f.hhi, f.hlo, eg, M, 1));
         er.rscale = rs(w.down_s);
         return pg(m, w.down, w.down_s, D, m->Il, f.ahi, f.alo, er, M, 2);
-      }
     }
     static int record_prefill(sli_model* m, int M) {
         for (int p = 0; p < 2 * m->L; ++p) {
@@ -1875,29 +1865,34 @@ static int get_state(sli_model* m, int seq, int32_t* pos, int32_t* token, int32_
 // ---------------------------------------------------------------- prompt prefill
 // The GEMM prefill (prefill.h) needs fp16, int8 or MXFP4 weights (MXFP4 only on request: sli_model_set_prefill),
 // batch 1, head_dim 64 or 128 and 64-multiple projection depths; otherwise the prompt runs through the decode step
-// itself (teacher forcing), which gives the same tokens.
+// itself (teacher forcing), which gives the same tokens. An FP8 E4M3 cache takes it under SLI_PREFILL_GEMM_KV8 alone
+// (its chunk rows are quantised from the GEMM's sums, not the decode step's: the codes may differ where a value sits
+// on a rounding boundary, so the other modes keep today's bit-identical decode-step prefill).
 // The chunked MFMA prefill (prefill.h) takes GEMM depths that are multiples of 64 (int8: 128-deep stages with a
 // half last stage). A multi-process TP rank without an RCCL communicator (SLI_DEBUG_NOCOMM, with or without the
 // one-shot exchange) has no all-reduce for a chunk's M x D residual rows, so it prefills through the decode step,
 // whose exchange it does have; an in-process group sums the chunk rows itself (record_group_prefill).
-static bool pf_supported(const sli_model* m) {
+static bool pf_supported(const sli_model* m, int mode) {
     if (m->partial && !m->collectives && !m->group) return false;
-    if (m->c.kv_dtype == SLI_DT_F8E4M3) return false;  // no chunk attention over an FP8 cache yet
+    if (m->c.kv_dtype == SLI_DT_F8E4M3 && mode != SLI_PREFILL_GEMM_KV8) return false;  // opt-in (sli.h)
     return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
            m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
 }
 // What the next prefill runs (sli_model_set_prefill): the chunks are captured graphs of the GEMM path alone and the
 // stepwise path replays the decode graph, so the mode only selects which of the two is launched; nothing captured
 // depends on it. auto keeps MXFP4 on the decode step (the default flips once the tests that pin it are revisited).
+static bool pf_forced(int mode) { return mode == SLI_PREFILL_GEMM || mode == SLI_PREFILL_GEMM_KV8; }
+static bool pf_mode_ok(int mode) { return mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_GEMM_KV8; }
 static bool pf_use_gemm(const sli_model* m) {
-    if (m->pf.mode == SLI_PREFILL_DECODE || !pf_supported(m)) return false;
-    return m->pf.mode == SLI_PREFILL_GEMM || m->c.w_dtype != SLI_DT_MXFP4;
+    if (m->pf.mode == SLI_PREFILL_DECODE || !pf_supported(m, m->pf.mode)) return false;
+    return pf_forced(m->pf.mode) || m->c.w_dtype != SLI_DT_MXFP4;
 }
 static int pf_set_mode(sli_model* m, int mode) {
-    SLI_CHECK(mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_DECODE, SLI_ERR_ARG, "set_prefill: mode must be 0, 1 or 2");
-    SLI_CHECK(mode != SLI_PREFILL_GEMM || pf_supported(m), SLI_ERR_STATE,
-              "set_prefill: this model cannot take the GEMM prefill (fp32 weights, an FP8 K/V cache, batch > 1, a TP "
-              "rank without a communicator, head_dim not 64 / 128, or a projection depth that is no multiple of 64)");
+    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0, 1, 2 or 3");
+    SLI_CHECK(!pf_forced(mode) || pf_supported(m, mode), SLI_ERR_STATE,
+              "set_prefill: this model cannot take the GEMM prefill (fp32 weights, an FP8 K/V cache outside "
+              "SLI_PREFILL_GEMM_KV8, batch > 1, a TP rank without a communicator, head_dim not 64 / 128, or a "
+              "projection depth that is no multiple of 64)");
     m->pf.mode = mode;
     return SLI_OK;
 }
@@ -1945,9 +1940,9 @@ extern "C" int sli_model_set_prefill(sli_model* m, int32_t mode) {
 
 extern "C" int sli_tp_group_set_prefill(sli_tp_group* g, int32_t mode) {
     SLI_CHECK(g, SLI_ERR_ARG, "null argument");
-    SLI_CHECK(mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_DECODE, SLI_ERR_ARG, "set_prefill: mode must be 0, 1 or 2");
+    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0, 1, 2 or 3");
     for (sli_model* m : g->ranks)
-        SLI_CHECK(mode != SLI_PREFILL_GEMM || pf_supported(m), SLI_ERR_STATE,
+        SLI_CHECK(!pf_forced(mode) || pf_supported(m, mode), SLI_ERR_STATE,
                   "set_prefill: this group cannot take the GEMM prefill");
     for (sli_model* m : g->ranks) SLI_TRY(pf_set_mode(m, mode));
     return SLI_OK;

@@ -16,10 +16,12 @@
 //      barrier too: PgCfg::PIPE, round 6, 5-20 % faster per GEMM, bit-identical sums). Fused epilogues:
 //      RoPE + K/V cache rows + q (model.cpp:52-67), residual add (:86-90, :124-128), SwiGLU (:111-115,
 //      written straight as the down projection's hi/lo operand);
-//   3. pf_attn_mfma_kernel (fp16 KV, the default): block-causal attention of 16 chunk rows x one head against
+//   3. pf_attn_mfma_kernel (fp16 KV, the default, or an FP8 E4M3 cache): block-causal attention of 16 chunk rows x
+//      one head against
 //      the cache rows 0 .. position (mha_kernel.cpp:36-77 per query: s_t = q.k_t * scale, softmax, sum p_t v_t):
 //      S = K q^T on MFMA with q split hi/lo, online softmax in fp32, P V on MFMA with V read transposed
-//      (ds_read_b64_tr_b16) from LDS-DMA'd K/V tiles; pf_attn_kernel, the VALU form (fp32, 64-position query
+//      (ds_read_b64_tr_b16; FP8: ds_read_b64_tr_b8, codes widened to fp16 in registers) from LDS-DMA'd K/V tiles;
+//      pf_attn_kernel, the VALU form (fp32, 64-position query
 //      blocks, K/V tiles of 64 positions in LDS), serves fp32 KV caches.
 // int8 weights: stages of 128 k; a depth that is 64 mod 128 (e.g. Llama-2-7B int8 down at TP 4, 2752) ends with
 // a half stage (pgemm_kernel). MXFP4 weights: pgemm_mx_kernel, the same ring with a scale image per stage and the
@@ -29,6 +31,7 @@
 #pragma once
 #include <type_traits>
 
+#include "attn_mfma_f8.h"
 #include "common.h"
 #include "lds_mfma.h"
 #include "mxfp4.h"
@@ -658,7 +661,8 @@ hipError_t launch_pgemm_mx(const PgInMx& in, const Epi& epi, const PfState* ps, 
 // ---- epilogues. Tiles hold 4-row groups {first(u), first(u + 1), second(u), second(u + 1)} where a pair is a
 // RoPE pair {d, d + hd/2} (q/k/v) or {gate u, up u}, so each lane's 4 rows are 2 complete pairs.
 template <typename KT>
-struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows of the cache at p0 + m
+struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows of the cache at p0 + m (KT: float,
+                   // __half, or f8e4m3: codes)
     float* q;
     KT* kc;  // this layer's cache base [hkv][T][hd]
     KT* vc;
@@ -711,7 +715,10 @@ struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows o
         }
     }
     __device__ static void store2(KT* p, const float* f) {
-        if constexpr (sizeof(KT) == 2) {
+        if constexpr (sizeof(KT) == 1) {  // FP8 E4M3 codes through the one codec (common.h); d is even: aligned
+            const unsigned c0 = from_f32<KT>(f[0]).bits, c1 = from_f32<KT>(f[1]).bits;
+            *reinterpret_cast<unsigned short*>(p) = (unsigned short)(c0 | (c1 << 8));
+        } else if constexpr (sizeof(KT) == 2) {
             __half h[2] = {__float2half_rn(f[0]), __float2half_rn(f[1])};
             *reinterpret_cast<unsigned*>(p) = *reinterpret_cast<const unsigned*>(h);
         } else {
@@ -922,31 +929,45 @@ __global__ void __launch_bounds__(256) pf_attn_kernel(PfAttnArgs<KT> a, const Pf
     }
 }
 
-// ---- 3b. block-causal attention on MFMA (fp16 cache). A workgroup = 16 chunk rows (queries) of one head;
-// its 4 waves split the key range into 32-key tiles (wave w takes tiles w, w + 4, ...) and merge their
+// ---- 3b. block-causal attention on MFMA (fp16 or FP8 E4M3 cache). A workgroup = 16 chunk rows (queries) of one
+// head; its 4 waves split the key range into 32-key tiles (wave w takes tiles w, w + 4, ...) and merge their
 // (max, sum, o) through LDS at the end. Per tile a wave:
-//   - LDS-DMAs K and V rows t0 .. t0+31 (16 x 1 KiB pieces) into its own images, 16-B chunks XOR-swizzled;
+//   - LDS-DMAs K and V rows t0 .. t0+31 (1-KiB pieces) into its own images, 16-B chunks XOR-swizzled;
 //   - Sᵀ = K Qᵀ: C[key][query] on v_mfma_f32_16x16x32_f16, A = K rows (exact fp16), B = Qᵀ as hi + lo fp16
 //     (two MFMAs into one accumulator);
 //   - online softmax per query (a lane's 8 keys, then the 4 lane groups of a query by xor 16 / 32);
-//   - Oᵀ += Vᵀ Pᵀ: B = Pᵀ straight from the Sᵀ accumulators (lane l holds query l & 15, keys
-//     {4g .. 4g+3, 16+4g .. 16+4g+3}, g = l >> 4 — the k order of the B operand), P as hi + lo; A = Vᵀ by
-//     two ds_read_b64_tr_b16 per 16-d tile, whose 4-row blocks are exactly those keys.
+//   - Oᵀ += Vᵀ Pᵀ: B = Pᵀ straight from the Sᵀ accumulators (lane l holds query l & 15 and 8 keys of the tile,
+//     in the k order of the B operand), P as hi + lo; A = Vᵀ by transposed LDS reads whose row blocks are
+//     exactly those keys.
+// One body serves both cache formats, as the decode attention's does (attn_mfma.h am_attn): the format struct F
+// (AmF16, AmF8) holds what a cache row's bytes change, i.e. the element size, the chunk swizzles, which key of the
+// tile A row i of S MFMA kt is (fp16: 16 kt + i; FP8: 8 (i >> 2) + 4 kt + (i & 3)) and so which key a lane's S
+// accumulator holds (fp16: 16 kt + 4 g + r; FP8: 8 g + 4 kt + r), the K fragment read (FP8: 8 codes widened
+// exactly to fp16 in registers) and the Vᵀ reads (fp16: two ds_read_b64_tr_b16 per 16-d tile, FP8: one
+// ds_read_b64_tr_b8). After the widening the arithmetic is the fp16 cache's.
 // mha_kernel.cpp:36-77 per query: s_t = (q . k_t) * scale, softmax over t <= position, o = sum p_t v_t.
-template <int HD>
+template <class F, int HD>
 struct PaGeo {
-    static constexpr int ROWB = HD * 2;          // bytes per image row
+    static constexpr int ROWB = HD * F::EB;      // bytes per image row
     static constexpr int IMG = 32 * ROWB;        // one 32-key image
     static constexpr int WAVE = 2 * IMG;         // K + V
     static constexpr int PIECES = WAVE / 1024;   // DMA instructions per tile
     static constexpr int CPR = ROWB / 16;        // 16-B chunks per row
+    static constexpr int NT = HD / 16;           // 16-d tiles (O)
+    // the end-of-kernel merge reuses the tile LDS as [4 waves][NT][64 lanes][4] floats + (m, l) [4][64] each: 34 KiB
+    // (hd 128) or 18 KiB (hd 64), more than the four FP8 tile images (32 / 16 KiB)
+    static constexpr int MERGE = (4 * NT * 64 * 4 + 2 * 4 * 64) * 4;
+    static constexpr int LDS = 4 * WAVE > MERGE ? 4 * WAVE : MERGE;
+    static_assert(HD == 64 || HD == 128, "head_dim");
+    static_assert(PIECES >= 2 && PIECES % 2 == 0 && 1024 % ROWB == 0, "whole 1-KiB pieces per K and per V image");
 };
 
-template <int HD>
-__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a, const PfState* __restrict__ ps) {
-    using G = PaGeo<HD>;
-    constexpr int ND = HD / 32, NT = HD / 16;  // 32-d blocks (S), 16-d tiles (O)
-    __shared__ __attribute__((aligned(1024))) char sm[4 * G::WAVE];
+template <class F, int HD>
+__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F::KT> a, const PfState* __restrict__ ps) {
+    using G = PaGeo<F, HD>;
+    using KT = typename F::KT;
+    constexpr int ND = HD / 32, NT = G::NT;  // 32-d blocks (S), 16-d tiles (O)
+    __shared__ __attribute__((aligned(1024))) char sm[G::LDS];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int g = lane >> 4, i16 = lane & 15;
@@ -977,8 +998,8 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
     char* kimg = sm + wave * G::WAVE;
     const unsigned kbase = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)kimg;
     const unsigned vbase = kbase + G::IMG;
-    const __half* kc = a.kc + (size_t)kvh * a.T * HD;
-    const __half* vc = a.vc + (size_t)kvh * a.T * HD;
+    const KT* kc = a.kc + (size_t)kvh * a.T * HD;
+    const KT* vc = a.vc + (size_t)kvh * a.T * HD;
     for (int tt = wave; tt < ntiles; tt += 4) {
         const int t0 = tt * 32;
         // K pieces 0 .. P/2-1, V pieces P/2 .. P-1; lane i of a piece: row (piece rows) + i / CPR, physical
@@ -988,33 +1009,34 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
             const bool isv = j >= G::PIECES / 2;
             const int jj = isv ? j - G::PIECES / 2 : j;
             const int r = jj * (1024 / G::ROWB) + lane / G::CPR;
-            const int c = (lane % G::CPR) ^ (isv ? lm_swz_v16(r, G::ROWB) : lm_swz_k16(r, G::ROWB));
-            const __half* src = (isv ? vc : kc) + (size_t)min(t0 + r, a.T - 1) * HD + c * 8;
+            const int c = (lane % G::CPR) ^ (isv ? F::swz_v(r, G::ROWB) : F::swz_k(r, G::ROWB));
+            const KT* src = (isv ? vc : kc) + (size_t)min(t0 + r, a.T - 1) * HD + c * (16 / F::EB);
             lm_dma(src, (isv ? vbase : kbase) + (unsigned)(jj * 1024));
         }
         lm_wait_vm<0>();
-        // Sᵀ[key][query] for keys t0 + 16 kt + (0..15)
+        // Sᵀ[key][query]: A row i16 of MFMA kt is key t0 + F::a_row(kt, i16)
         lm_float4 sacc[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             sacc[kt] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
-            const int r = kt * 16 + i16;
+            const int r = F::a_row(kt, i16);
             const char* krow = kimg + r * G::ROWB;
+            const int sw = F::swz_k(r, G::ROWB);
 #pragma unroll
             for (int db = 0; db < ND; ++db) {
-                const u32x4 kf = *reinterpret_cast<const u32x4*>(krow + ((4 * db + g) ^ lm_swz_k16(r, G::ROWB)) * 16);
+                const u32x4 kf = F::k_frag(krow, sw, db, g);
                 sacc[kt] = lm_mfma(kf, qh[db], sacc[kt]);
                 sacc[kt] = lm_mfma(kf, ql[db], sacc[kt]);
             }
         }
-        // lane holds keys t0 + 16 kt + 4 g + r of query mq
+        // lane holds keys F::acc_key(t0, g, kt, r) of query mq
         float sv[8];
         float cmax = -INFINITY;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int key = t0 + kt * 16 + 4 * g + r;
+                const int key = F::acc_key(t0, g, kt, r);
                 const float v = key <= pos ? sacc[kt][r] * a.scale : -INFINITY;
                 sv[kt * 4 + r] = v;
                 cmax = fmaxf(cmax, v);
@@ -1038,23 +1060,14 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
         for (int e = 0; e < 8; ++e) pf_split(pv[e], ph[e], pl[e]);
         const u32x4 pfh = *reinterpret_cast<const u32x4*>(ph);
         const u32x4 pfl = *reinterpret_cast<const u32x4*>(pl);
-        // Vᵀ 16-d tile dt: lane 16 g + 4 q + p addresses row (4 g + q) [+16], d 16 dt + 4 p .. +3
-        const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-        const int r1 = 4 * g + q4, r2 = 16 + 4 * g + q4;
-        const unsigned a1 = vbase + r1 * G::ROWB + 8 * (p4 & 1), a2 = vbase + r2 * G::ROWB + 8 * (p4 & 1);
-        const int s1 = lm_swz_v16(r1, G::ROWB), s2 = lm_swz_v16(r2, G::ROWB);
-        uint2 x[2 * NT];  // tile t: rows r1 in x[2 t], rows r2 in x[2 t + 1]
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int c = 2 * t + (p4 >> 1);
-            x[2 * t] = lm_tr16_read(a1 + ((c ^ s1) * 16));
-            x[2 * t + 1] = lm_tr16_read(a2 + ((c ^ s2) * 16));
-        }
+        // the Vᵀ operand's transposed reads: the keys of a lane group's row block are the keys of its P elements
+        uint2 x[NT * F::VR];
+        F::template v_read<NT, G::ROWB>(vbase, lane, x);
         lm_tr_landed(x);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             o[t] *= corr;
-            const u32x4 vf = u32x4{x[2 * t].x, x[2 * t].y, x[2 * t + 1].x, x[2 * t + 1].y};
+            const u32x4 vf = F::v_frag(x, t);
             o[t] = lm_mfma(vf, pfh, o[t]);
             o[t] = lm_mfma(vf, pfl, o[t]);
         }
@@ -1097,20 +1110,21 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<__half> a,
     }
 }
 
-// The attention of M chunk rows (hd 64 or 128: the caller's check): an fp16 cache on MFMA, 16 chunk rows per
+// The attention of M chunk rows (hd 64 or 128: the caller's check): an fp16 or FP8 cache on MFMA, 16 chunk rows per
 // workgroup; an fp32 cache on the VALU kernel, 64 chunk rows per workgroup, so at M = 32 it reads q and writes
 // ohi / olo for rows 32 .. 63 too (the buffers hold at least 64 rows). The engine and sli_prefill_attn launch
 // through here.
-constexpr int pf_attn_rows(bool f16_cache, int M) { return f16_cache ? M : (M + kPaQB - 1) / kPaQB * kPaQB; }
+constexpr int pf_attn_rows(bool mfma_cache, int M) { return mfma_cache ? M : (M + kPaQB - 1) / kPaQB * kPaQB; }
 
 template <typename KT>
 hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const PfState* ps, hipStream_t s) {
-    if constexpr (std::is_same<KT, __half>::value) {
+    if constexpr (!std::is_same<KT, float>::value) {
+        using F = std::conditional_t<std::is_same<KT, f8e4m3>::value, AmF8, AmF16>;
         const dim3 ag(M / 16, aa.hq);
         if (hd == 128)
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<128>), ag, dim3(256), 0, s, aa, ps);
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 128>), ag, dim3(256), 0, s, aa, ps);
         else
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<64>), ag, dim3(256), 0, s, aa, ps);
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 64>), ag, dim3(256), 0, s, aa, ps);
     } else {
         const dim3 ag((M + kPaQB - 1) / kPaQB, aa.hq);
         if (hd == 128)

@@ -60,6 +60,10 @@ static int pf_gemm_role(const void* w, const float* rs_in, const void* hi, const
     const void* ws = is_mx<WT>::value ? (const void*)rs_in : nullptr;
     const float* rs = is_mx<WT>::value ? nullptr : rs_in;
     if (e.role == 0) {
+        if (e.kv_dtype == SLI_DT_F8E4M3) {
+            const PgEpiQKV<f8e4m3> q{e.q, (f8e4m3*)e.kc, (f8e4m3*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
+            return pf_gemm_launch<PgEpiQKV<f8e4m3>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
+        }
         if (e.kv_dtype == SLI_DT_F16) {
             const PgEpiQKV<__half> q{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
             return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
@@ -110,7 +114,8 @@ static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void*
     switch (e.role) {
         case 0:
             SLI_CHECK(e.q && e.kc && e.vc && e.sin_t && e.cos_t, SLI_ERR_ARG, "sli_prefill_gemm: null q/k/v operand");
-            SLI_CHECK(e.kv_dtype == SLI_DT_F16 || e.kv_dtype == SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_gemm: bad kv dtype");
+            SLI_CHECK(e.kv_dtype == SLI_DT_F16 || e.kv_dtype == SLI_DT_F32 || e.kv_dtype == SLI_DT_F8E4M3, SLI_ERR_ARG,
+                      "sli_prefill_gemm: bad kv dtype");
             SLI_CHECK(e.hd == 64 || e.hd == 128, SLI_ERR_ARG, "sli_prefill_gemm: head_dim must be 64 or 128");
             SLI_CHECK(e.hq >= 1 && e.hkv >= 1 && e.hq % e.hkv == 0, SLI_ERR_ARG,
                       "sli_prefill_gemm: hq must be a multiple of hkv");
@@ -162,13 +167,14 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
                      int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
                      sli_stream_t stream) {
     SLI_CHECK(q && kc && vc && ohi && olo && state, SLI_ERR_ARG, "sli_prefill_attn: null pointer");
-    SLI_CHECK(kv_dtype == SLI_DT_F16 || kv_dtype == SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_attn: bad kv dtype");
+    SLI_CHECK(kv_dtype == SLI_DT_F16 || kv_dtype == SLI_DT_F32 || kv_dtype == SLI_DT_F8E4M3, SLI_ERR_ARG,
+              "sli_prefill_attn: bad kv dtype");
     SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_attn: M must be 32, 64, 128 or 256");
     SLI_CHECK(hd == 64 || hd == 128, SLI_ERR_ARG, "sli_prefill_attn: head_dim must be 64 or 128");
     SLI_CHECK(hq >= 1 && hkv >= 1 && hq % hkv == 0 && hq <= 65535, SLI_ERR_ARG,
               "sli_prefill_attn: hq must be a multiple of hkv");
     SLI_CHECK(T >= 1 && p0 >= 0 && p0 < T, SLI_ERR_ARG, "sli_prefill_attn: p0 must be in [0, T)");
-    SLI_CHECK(rows_allocated >= pf_attn_rows(kv_dtype == SLI_DT_F16, M), SLI_ERR_ARG,
+    SLI_CHECK(rows_allocated >= pf_attn_rows(kv_dtype != SLI_DT_F32, M), SLI_ERR_ARG,
               "sli_prefill_attn: q / ohi / olo must hold M rows (fp32 cache: M rounded up to 64, the kernel's block)");
     SLI_CHECK(al16(q) && al16(kc) && al16(vc) && al16(ohi) && al16(olo) && (uintptr_t)state % 8 == 0, SLI_ERR_ARG,
               "sli_prefill_attn: 16-byte alignment");
@@ -179,6 +185,9 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
     if (kv_dtype == SLI_DT_F16) {
         const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
         SLI_HIP(launch_pf_attn<__half>(aa, hd, M, ps, s));
+    } else if (kv_dtype == SLI_DT_F8E4M3) {  // every DMA piece is 16 bytes of a row: the al16 check above
+        const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, ps, s));
     } else {
         const PfAttnArgs<float> aa{q, (const float*)kc, (const float*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
         SLI_HIP(launch_pf_attn<float>(aa, hd, M, ps, s));

@@ -21,7 +21,7 @@ from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
 _DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8,
            "mxfp4": DT_MXFP4, "fp4": DT_MXFP4,
            "f8": DT_F8E4M3, "fp8": DT_F8E4M3, "e4m3": DT_F8E4M3}  # K/V cache only (OCP FP8 E4M3, sli.h)
-_PREFILL_MODES = {"auto": 0, "gemm": 1, "decode": 2}  # SLI_PREFILL_*
+_PREFILL_MODES = {"auto": 0, "gemm": 1, "decode": 2, "gemm-kv8": 3}  # SLI_PREFILL_*
 
 
 @dataclass(frozen=True)
@@ -276,8 +276,9 @@ class LlamaModel:
 
     def set_prefill(self, mode: str):
         """Which path the next prefill takes (sli_model_set_prefill): 'auto' (the GEMM prefill where the model can
-        take it, MXFP4 weights excepted), 'gemm' (the chunked MFMA prefill; an error where the model cannot take it)
-        or 'decode' (teacher-forced decode steps). prefill_path() reports the outcome."""
+        take it, MXFP4 weights excepted), 'gemm' (the chunked MFMA prefill; an error where the model cannot take it),
+        'decode' (teacher-forced decode steps) or 'gemm-kv8' ('gemm', and also accepted by a model with an FP8 K/V
+        cache, which 'gemm' refuses and 'auto' keeps on the decode step). prefill_path() reports the outcome."""
         call("sli_model_set_prefill", self._h, _PREFILL_MODES[mode])
 
     def fused_qkv_attn(self) -> int:

@@ -294,10 +294,11 @@ def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi, scales=None):
 
 
 def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, p0: int, nv: int,
-                     row_scale=None, scales=None):
+                     row_scale=None, scales=None, kv_dtype=None):
     """One pgemm_kernel launch with the q/k/v epilogue: W [(hq + 2 hkv) hd, K]; q [M, hq hd] fp32 gets every chunk
-    row; kc / vc, one layer's cache [hkv, T, hd] (f16 or f32), get rows p0 + m for m < nv, p0 + m < T. Returns the
-    tiling that ran. scales (uint8 [N, K/32]): W is MXFP4, uint8 [N, K/2] (pgemm_mx_kernel); no row_scale then."""
+    row; kc / vc, one layer's cache [hkv, T, hd] (f16, f32, or FP8 E4M3: a float8_e4m3fn tensor, or uint8 codes with
+    kv_dtype="f8"), get rows p0 + m for m < nv, p0 + m < T. Returns the tiling that ran. scales (uint8 [N, K/32]): W is
+    MXFP4, uint8 [N, K/2] (pgemm_mx_kernel); no row_scale then."""
     if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
         raise ValueError("Tensor with Wrong Dim!")
     T = kc.shape[1]
@@ -305,7 +306,7 @@ def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: 
         raise ValueError("Tensor with Wrong Dim!")
     _dev(q, kc, vc, sin_t, cos_t)
     e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
-                           kv_dtype=_DT[kc.dtype], sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
+                           kv_dtype=_kv_dt(kc, kv_dtype), sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
                            hd=hd, T=T)
     return _prefill_gemm(w, row_scale, hi, lo, p0, nv, e, scales)
 
@@ -331,10 +332,11 @@ def prefill_gemm_resid(w, hi, lo, y, resid=None, row_scale=None, scales=None):
     return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
 
 
-def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int):
+def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int, kv_dtype=None):
     """Block-causal prefill attention of chunk rows 0 .. M-1 at positions p0 + m over one layer's cache [hkv, T, hd]
-    (f16: MFMA kernel, f32: VALU kernel). q [rows, hq hd] fp32 with rows >= M (f32 cache: >= M rounded up to 64, the
-    contract of sli_prefill_attn); returns (ohi, olo) [rows, hq hd] fp16."""
+    (f16 and FP8 E4M3: MFMA kernel, f32: VALU kernel; an FP8 cache is a float8_e4m3fn tensor, or uint8 codes with
+    kv_dtype="f8"). q [rows, hq hd] fp32 with rows >= M (f32 cache: >= M rounded up to 64, the contract of
+    sli_prefill_attn); returns (ohi, olo) [rows, hq hd] fp16."""
     rows = q.shape[0]
     if q.shape != (rows, hq * hd) or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
         raise ValueError("Tensor with Wrong Dim!")
@@ -343,7 +345,7 @@ def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int):
     olo = torch.zeros_like(ohi)
     state = _pf_state(q.device)
     _dev(q, kc, vc)
-    call("sli_prefill_attn", _p(q), _p(kc), _p(vc), _DT[kc.dtype], _p(ohi), _p(olo), M, rows, p0, hq, hkv, hd, T,
+    call("sli_prefill_attn", _p(q), _p(kc), _p(vc), _kv_dt(kc, kv_dtype), _p(ohi), _p(olo), M, rows, p0, hq, hkv, hd, T,
          _p(state), _s())
     return ohi, olo
 
