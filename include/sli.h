@@ -455,8 +455,8 @@ int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const
                      sli_pgemm_tiling* tiling, sli_stream_t stream);
 /* sli_prefill_gemm for MXFP4 weights (beside it as sli_matmul_mxfp4 is beside sli_matmul): data uint8 [N][K / 2],
  * scales uint8 [N][K / 32] in the public layout (element 2i in bits 3:0 of byte i, scale 2^(byte - 127)); one
- * pgemm_mx_kernel launch, the code object an MXFP4 model's GEMM prefill launches. The same checks; data is 16-byte
- * aligned, scales need no alignment (they are loaded by the byte). The epilogues apply no row scale. Scale bytes
+ * pgemm_kernel launch in its MXFP4 format, the code object an MXFP4 model's GEMM prefill launches. The same checks;
+ * data is 16-byte aligned, scales need no alignment (they are loaded by the byte). The epilogues apply no row scale. Scale bytes
  * 1 .. 254 are exact (the block scale is applied in fp32). */
 int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N, int32_t K,
                            int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,

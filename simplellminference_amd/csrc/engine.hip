@@ -1088,26 +1088,19 @@ struct StepRecorder {
     // position runs as an ordinary decode step. Phases as record_phase: 2l = qkv, attention, wo; 2l+1 =
     // gate/up, down; under tensor parallelism each ends with the all-reduce of the chunk's residual rows.
     // Ws: the e8m0 block scales of an mxfp4 matrix (the LayerW *_s pointer; the epilogue's rscale is null then)
-    template <class Epi, class Cfg>
-    static int pg_cfg(sli_model* m, const void* W, const void* Ws, int N, int K, const __half* hi, const __half* lo,
-                      const Epi& e, int M) {
-        if constexpr (std::is_same<WT, float>::value) {
-            return fail(SLI_ERR_ARG, "prefill needs fp16, int8 or mxfp4 weights");
-        } else if constexpr (MX) {
-            const PgInMx in{(const uint8_t*)W, (const uint8_t*)Ws, hi, lo, N, K, M};
-            SLI_HIP((launch_pgemm_mx<Epi, Cfg>(in, e, m->pf.ps, m->stream)));
-            return SLI_OK;
-        } else {
-            const PgIn<WT> in{(const WT*)W, hi, lo, N, K, M};
-            SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, m->pf.ps, m->stream)));
-            return SLI_OK;
-        }
-    }
     // the tiling per weight type, projection role and chunk size: prefill.h pg_pick (the one table)
     template <class Epi>
     static int pg(sli_model* m, const void* W, const void* Ws, int N, int K, const __half* hi, const __half* lo,
                   const Epi& e, int M, int role) {
-        return pg_pick<WT>(M, role, [&](auto cfg) { return pg_cfg<Epi, decltype(cfg)>(m, W, Ws, N, K, hi, lo, e, M); });
+        if constexpr (std::is_same<WT, float>::value) {
+            return fail(SLI_ERR_ARG, "prefill needs fp16, int8 or mxfp4 weights");
+        } else {
+            const PgIn<WT> in{(const WT*)W, hi, lo, N, K, M, MX ? (const uint8_t*)Ws : nullptr};
+            return pg_pick<WT>(M, role, [&](auto cfg) -> int {
+                SLI_HIP((launch_pgemm<Epi, decltype(cfg), WT>(in, e, m->pf.ps, m->stream)));
+                return SLI_OK;
+            });
+        }
     }
     template <class Epi>
     static int allow_pg(sli_model*) {
@@ -1125,12 +1118,8 @@ struct StepRecorder {
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
         if (p == 0) {
-            if constexpr (MX)
-                hipLaunchKernelGGL(pf_embed_mx_kernel, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const uint8_t*)m->emb,
-                                   (const uint8_t*)m->emb_s, f.x, D);
-            else
-                hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
-                                   m->emb_s, f.x, D);
+            hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
+                               (const void*)m->emb_s, f.x, D);
             SLI_HIP(hipGetLastError());
         }
         const int l = p / 2;

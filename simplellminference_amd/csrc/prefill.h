@@ -23,9 +23,10 @@
 //      (ds_read_b64_tr_b16; FP8: ds_read_b64_tr_b8, codes widened to fp16 in registers) from LDS-DMA'd K/V tiles;
 //      pf_attn_kernel, the VALU form (fp32, 64-position query
 //      blocks, K/V tiles of 64 positions in LDS), serves fp32 KV caches.
-// int8 weights: stages of 128 k; a depth that is 64 mod 128 (e.g. Llama-2-7B int8 down at TP 4, 2752) ends with
-// a half stage (pgemm_kernel). MXFP4 weights: pgemm_mx_kernel, the same ring with a scale image per stage and the
-// block scale applied to each k-block's tile in fp32 (below, "MXFP4 weights").
+// One pgemm_kernel body serves fp16, int8 and MXFP4 weights; a format struct (PgF16, PgI8, PgMx) holds what the
+// weight type changes. int8 and MXFP4: stages of 128 k; a depth that is 64 mod 128 (e.g. Llama-2-7B int8 down at
+// TP 4, 2752) ends with a half stage. MXFP4: the ring carries a scale image per stage too, and the block scale is
+// applied to each k-block's tile in fp32 (PgMx).
 // The chunk's start position and valid count live in device memory (PfState), so one captured graph per
 // chunk size serves every chunk of every prompt.
 #pragma once
@@ -46,26 +47,22 @@ struct PfState {
 };
 
 // ---------------------------------------------------------------- 1. embedding + RMSNorm / split
-// x[m] = emb[prompt[p0 + m]] (emb_kernel.cpp:4-21; padding rows repeat the last valid token)
+// x[m] = emb[prompt[p0 + m]] (emb_kernel.cpp:4-21; padding rows repeat the last valid token). emb_s: the int8 table's
+// fp32 row scales (nullable), or the MXFP4 table's block scale bytes (mxfp4.h layout: a table decode per element)
 template <typename WT>
 __global__ void __launch_bounds__(256) pf_embed_kernel(const PfState* __restrict__ ps, const int32_t* __restrict__ prompt,
-                                                      const WT* __restrict__ emb, const float* __restrict__ emb_s,
+                                                      const WT* __restrict__ emb, const void* __restrict__ emb_s,
                                                       float* __restrict__ x, int D) {
     const int m = blockIdx.x;
     const int nv = ps->nv;
     const int tok = prompt[ps->p0 + min(m, nv - 1)];
-    const float s = emb_s ? emb_s[tok] : 1.0f;
-    for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = to_f32(emb[(size_t)tok * D + i]) * s;
-}
-
-// MXFP4 table (mxfp4.h layout): a table decode per element, the block scales behind emb_s
-__global__ void __launch_bounds__(256) pf_embed_mx_kernel(const PfState* __restrict__ ps, const int32_t* __restrict__ prompt,
-                                                         const uint8_t* __restrict__ emb, const uint8_t* __restrict__ emb_s,
-                                                         float* __restrict__ x, int D) {
-    const int m = blockIdx.x;
-    const int nv = ps->nv;
-    const int tok = prompt[ps->p0 + min(m, nv - 1)];
-    for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = mx_element(emb, emb_s, (size_t)tok, D, i);
+    if constexpr (is_mx<WT>::value) {
+        const uint8_t *data = reinterpret_cast<const uint8_t*>(emb), *sc = static_cast<const uint8_t*>(emb_s);
+        for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = mx_element(data, sc, (size_t)tok, D, i);
+    } else {
+        const float s = emb_s ? static_cast<const float*>(emb_s)[tok] : 1.0f;
+        for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = to_f32(emb[(size_t)tok * D + i]) * s;
+    }
 }
 
 // one workgroup per chunk row: h = (x * 1/rms) * w (rms_kernel.cpp:12-22) or plain x (w == nullptr), as hi/lo.
@@ -117,14 +114,16 @@ __global__ void __launch_bounds__(256) pf_norm_split_kernel(const float* __restr
 // The operand images travel by LDS-DMA (lds_mfma.h lm_dma: 1-KiB pieces, counted by the kernel's own vmcnt waits).
 template <typename WT>
 struct PgIn {
-    const WT* W;        // [N][K] fp16 or int8 (row-major, PyTorch [out][in]; int8 row scales in the epilogue)
+    const WT* W;        // [N][K] fp16 or int8 (row-major, PyTorch [out][in]; int8 row scales in the epilogue), or
+                        // mxfp4 data [N][K / 2]
     const __half* Bhi;  // [M][K] activations, fp16 hi
     const __half* Blo;  // [M][K] fp16 lo
     int N, K, M;        // rows, depth, chunk rows (a multiple of BM)
+    const uint8_t* Ws;  // mxfp4: e8m0 block scales [N][K / 32]; null otherwise
 };
 
-// Tiling: a workgroup of 2 WR waves owns BN = 32 WR weight rows x BM chunk rows; wave w holds the 2 x BM/32
-// accumulator tiles of rows 32 (w % WR) .. +32 and position half w / WR. A stage covers KS depth: 64 for fp16
+// Tiling: a workgroup of 2 WR waves owns BN = 16 AT WR weight rows x BM chunk rows; wave w holds the AT x BM/32
+// accumulator tiles of rows 16 AT (w % WR) .. and position half w / WR. A stage covers KS depth: 64 for fp16
 // weights, 128 for int8, so a weight row's slice is one whole 128-byte line (a chunk row's fp16 hi / lo slice
 // one or two lines). Each LDS-DMA wave-instruction moves 1 KiB of whole lines (8 rows x 128 B or 4 x 256 B;
 // fragment-shaped pieces of 16 rows x 64 B fetched every line twice and capped the ingest at ~29 GB/s per
@@ -139,48 +138,164 @@ struct PgIn {
 // SA_ > 0 (PIPE only): the weight (A) images get a ring of their own, SA_ stages deep (SA_ - 1 issued ahead), and
 // the activation (B) images a 2-stage ring (one ahead): the A bytes come from HBM (read once per chunk), the B bytes
 // from L2, so only A needs the deep prefetch, and B, the larger image, does not pay for it in LDS.
-// KS_ (mxfp4 only, pgemm_mx_kernel): the depth a stage covers, 128 or 256 (0: 128).
-template <int BM_, int WR_, int S_, int AT_ = 2, bool PIPE_ = false, int SA_ = 0, int KS_ = 0>
+template <int BM_, int WR_, int S_, int AT_ = 2, bool PIPE_ = false, int SA_ = 0>
 struct PgCfg {
-    static constexpr int BM = BM_, WR = WR_, S = S_, AT = AT_, SA = SA_, KS = KS_;
+    static constexpr int BM = BM_, WR = WR_, S = S_, AT = AT_, SA = SA_;
     static constexpr bool PIPE = PIPE_;
-};
-
-template <class Cfg, typename WT>
-struct PgGeo {
-    static constexpr int BM = Cfg::BM, WR = Cfg::WR, S = Cfg::S, AT = Cfg::AT;
-    static constexpr int WAVES = 2 * WR, THREADS = 64 * WAVES, BN = 16 * AT * WR;
-    static constexpr int KS = sizeof(WT) == 1 ? 128 : 64;  // depth per stage
-    static constexpr int KBS = KS / 32;                    // MFMA k-blocks per stage
-    static constexpr int A_ROW = KS * (int)sizeof(WT);     // 128 B
-    static constexpr int B_ROW = KS * 2;                   // 128 or 256 B
-    static constexpr int A_IMG = 16 * A_ROW, B_IMG = 16 * B_ROW;
-    static constexpr int PT = BM / 16;  // position tiles per workgroup
-    static constexpr int WPT = PT / 2;  // per wave
-    static constexpr int NA = AT * WR;  // weight row tiles
-    static constexpr int A_BYTES = NA * A_IMG;
-    static constexpr int STAGE = A_BYTES + 2 * PT * B_IMG;
-    static constexpr int NDMA = STAGE / 1024;  // wave-instructions per stage
-    static constexpr int DPW = NDMA / WAVES;   // per wave
-    static constexpr int SA = Cfg::SA;         // split rings (PgCfg): A pieces per wave DPA, B pieces DPB
-    static constexpr int B_BYTES = STAGE - A_BYTES;
-    static constexpr int DPA = SA ? A_BYTES / 1024 / WAVES : 0, DPB = SA ? B_BYTES / 1024 / WAVES : 0;
-    static constexpr size_t LDS = SA ? (size_t)SA * A_BYTES + (size_t)S * B_BYTES : (size_t)S * STAGE;
-    static_assert(A_ROW == 128 && WPT >= 1 && NDMA % WAVES == 0 && Cfg::KS == 0, "tiling");
-    static_assert(S >= 2 && (S - 1) * DPW <= 63, "ring depth (vmcnt counts 63 loads)");
-    // (SA > S: A(s) must be issued in an earlier iteration than B(s), the wait below counts on it; SA == S computed
-    // wrong sums in tools/pgemm_lab)
-    static_assert(SA == 0 || (Cfg::PIPE && S == 2 && SA > S && (A_BYTES / 1024) % WAVES == 0 &&
-                              (B_BYTES / 1024) % WAVES == 0 && (SA - 1) * DPA + DPB <= 63), "split rings");
-    static_assert(LDS <= 160 * 1024, "LDS");
 };
 
 // 16-byte chunk swizzle of an image row (conflict-free fragment reads): rows of 128 B pair up in one 256-B
 // bank span, so the chunk index is XORed with row / 2; rows of 256 B with the row
-__device__ __forceinline__ int pg_swz(int row, int row_bytes) { return row_bytes == 128 ? (row >> 1) & 7 : row & 15; }
+__host__ __device__ constexpr int pg_swz(int row, int row_bytes) { return row_bytes == 128 ? (row >> 1) & 7 : row & 15; }
+// chunk swizzle of an mxfp4 weight image row (64 B): a k-block's fragment read is 16 rows x 16 B, 4 B per lane
+__host__ __device__ constexpr int pg_mx_swz(int row, int row_bytes) { return row_bytes == 64 ? (row >> 2) & 3 : (row >> 1) & 7; }
 
-// 8 int8 weights -> 8 fp16 (exact): common.h i8x8_to_f16
-__device__ __forceinline__ u32x4 pg_i8_to_f16(uint2 w) { return i8x8_to_f16(w.x, w.y); }
+// 8 e2m1 codes (element 2i in bits 3:0 of byte i) -> 8 fp16, exact and unscaled, in element order. The high byte
+// of the fp16 of magnitude code c is {00, 38, 3C, 3E, 40, 42, 44, 46}[c] (0, .5, 1, 1.5, 2, 3, 4, 6), the low byte 0.
+__device__ __forceinline__ u32x4 pg_fp4_to_f16(unsigned w) {
+    const unsigned lut_hi = 0x46444240u, lut_lo = 0x3E3C3800u;
+    unsigned ev = __builtin_amdgcn_perm(lut_hi, lut_lo, w & 0x07070707u);         // elements 0, 2, 4, 6
+    unsigned od = __builtin_amdgcn_perm(lut_hi, lut_lo, (w >> 4) & 0x07070707u);  // elements 1, 3, 5, 7
+    ev |= (w & 0x08080808u) << 4;  // the sign bits
+    od |= w & 0x80808080u;
+    u32x4 r;  // dword i = {00, ev_i, 00, od_i} (selector 0x0c: a zero byte)
+    r[0] = __builtin_amdgcn_perm(od, ev, 0x040c000cu);
+    r[1] = __builtin_amdgcn_perm(od, ev, 0x050c010cu);
+    r[2] = __builtin_amdgcn_perm(od, ev, 0x060c020cu);
+    r[3] = __builtin_amdgcn_perm(od, ev, 0x070c030cu);
+    return r;
+}
+
+// ---- weight formats (in the manner of attn_mfma.h AmF16 / AmF8): what the weight type changes, and nothing else.
+// KS: depth per stage; A_ROW: weight row bytes per stage; CPK: 16-byte chunks of a weight row per 32-k block; swz: the
+// weight image's chunk swizzle; SC_IMG: scale-image bytes per 16-row tile and stage; a_off / FRAG / a_frag: where in
+// an image row (sw = swz(row)) lane group kg's 8 k of k-block kb lie, how many bytes, and their decode to 8 fp16;
+// SCALED: a k-block's tile is summed on its own and scaled per row.
+struct PgF16 {
+    static constexpr int KS = 64, A_ROW = 128, CPK = 4, SC_IMG = 0, FRAG = 16;
+    static constexpr bool SCALED = false;
+    __host__ __device__ static constexpr int swz(int row) { return pg_swz(row, A_ROW); }
+    __host__ __device__ static constexpr int a_off(int kb, int kg, int sw) { return ((4 * kb + kg) ^ sw) * 16; }
+    __device__ __forceinline__ static u32x4 a_frag(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
+};
+// int8: a depth that is 64 mod 128 ends with a half stage. k 32 kb + 8 kg .. +8: chunk 2 kb + kg / 2, half kg % 2;
+// 8 int8 -> 8 fp16 exactly (common.h i8x8_to_f16)
+struct PgI8 {
+    static constexpr int KS = 128, A_ROW = 128, CPK = 2, SC_IMG = 0, FRAG = 8;
+    static constexpr bool SCALED = false;
+    __host__ __device__ static constexpr int swz(int row) { return pg_swz(row, A_ROW); }
+    __host__ __device__ static constexpr int a_off(int kb, int kg, int sw) {
+        return ((2 * kb + (kg >> 1)) ^ sw) * 16 + 8 * (kg & 1);
+    }
+    __device__ __forceinline__ static u32x4 a_frag(const char* p) {
+        const uint2 w = *reinterpret_cast<const uint2*>(p);
+        return i8x8_to_f16(w.x, w.y);
+    }
+};
+// MXFP4 (mxfp4.h: data [N][K/2], e8m0 scales [N][K/32]): a weight row's 128-k slice is half a line (64 B, one 1-KiB
+// piece = one 16-row image), a chunk row's hi / lo slice two lines, the int8 geometry, so BM = 128 still fits two
+// stages. (256-k stages tied or lost in every cell and could not take the fastest tilings:
+// profiles/mxfp4_pgemm_lab.txt.)
+// Scale scheme: one MFMA k-block is one MX block, so a (weight row, k-block) has one scale 2^e. The e2m1 codes are
+// decoded to fp16 exactly and UNSCALED (a byte LUT through v_perm: the fp16 of every e2m1 magnitude has a zero low
+// byte); the hi and lo MFMAs of a k-block run into a zeroed tile and acc = fma(tile, 2^e_row, acc) per C-fragment row
+// in fp32, where every e8m0 byte 1 .. 254 is a normal number: no fp16 overflow or flush at any block exponent.
+// The scale bytes travel through the ring too: global_load_lds_ubyte, a byte per lane into a dword of the stage's
+// scale image [k-block][tile row], so a lane's four C rows of a tile are one ds_read_b128 and 2^e is dword << 23.
+// Every wave issues the same number of pieces per stage (A, B and scale pieces), all LDS-DMA, all counted by
+// pg_wait_stages; the kernel has no plain global load between its first DMA and its last wait.
+// k 32 kb + 8 kg .. +8 of a row: chunk kb, bytes 4 kg .. +4.
+struct PgMx {
+    static constexpr int KS = 128, A_ROW = 64, CPK = 1, SC_IMG = 16 * (KS / 32) * 4, FRAG = 4;
+    static constexpr bool SCALED = true;
+    __host__ __device__ static constexpr int swz(int row) { return pg_mx_swz(row, A_ROW); }
+    __host__ __device__ static constexpr int a_off(int kb, int kg, int sw) { return (kb ^ sw) * 16 + 4 * kg; }
+    __device__ __forceinline__ static u32x4 a_frag(const char* p) {
+        return pg_fp4_to_f16(*reinterpret_cast<const unsigned*>(p));
+    }
+};
+template <typename WT>
+using PgFmt = std::conditional_t<is_mx<WT>::value, PgMx, std::conditional_t<sizeof(WT) == 1, PgI8, PgF16>>;
+
+// A stage image is [NA weight images][PT x (hi, lo) activation images][scale image], moved as pieces d = 0 .. NP - 1
+// in that order: 1 KiB each, a scale piece 64 dwords. Wave w issues DPW of them per stage: pieces w DPW .. of the
+// stage, or, with split rings and with a scaled format, its DPA weight pieces, then its DPB activation pieces, then
+// its DPS scale pieces (piece()), so that a piece's kind is known from its place in the wave's list.
+template <class Cfg, typename WT>
+struct PgGeo {
+    using F = PgFmt<WT>;
+    static constexpr int BM = Cfg::BM, WR = Cfg::WR, S = Cfg::S, AT = Cfg::AT;
+    static constexpr int WAVES = 2 * WR, THREADS = 64 * WAVES, BN = 16 * AT * WR;
+    static constexpr int KS = F::KS;     // depth per stage
+    static constexpr int KBS = KS / 32;  // MFMA k-blocks per stage
+    static constexpr int A_ROW = F::A_ROW, B_ROW = KS * 2;  // 64 or 128 B; 128 or 256 B
+    static constexpr int A_IMG = 16 * A_ROW, B_IMG = 16 * B_ROW;
+    static constexpr int PT = BM / 16;  // position tiles per workgroup
+    static constexpr int WPT = PT / 2;  // per wave
+    static constexpr int NA = AT * WR;  // weight row tiles
+    static constexpr int A_BYTES = NA * A_IMG, B_BYTES = 2 * PT * B_IMG;
+    static constexpr int SC_BYTES = NA * F::SC_IMG;  // a dword per (k-block, tile row)
+    static constexpr int STAGE = A_BYTES + B_BYTES + SC_BYTES;
+    static constexpr int NPA = A_BYTES / 1024, NPB = B_BYTES / 1024, NPS = SC_BYTES / 256, NP = NPA + NPB + NPS;
+    static constexpr int DPW = NP / WAVES;  // LDS-DMA instructions per wave and stage
+    static constexpr int SA = Cfg::SA;      // split rings (PgCfg)
+    static constexpr bool BY_KIND = SA > 0 || F::SCALED;
+    static constexpr int DPA = BY_KIND ? NPA / WAVES : 0, DPB = BY_KIND ? NPB / WAVES : 0, DPS = BY_KIND ? NPS / WAVES : 0;
+    static constexpr size_t LDS = SA ? (size_t)SA * A_BYTES + (size_t)S * B_BYTES : (size_t)S * STAGE;
+    // piece j of wave w's list, and a piece's byte offset in the stage image
+    __host__ __device__ static constexpr int piece(int w, int j) {
+        if (!BY_KIND) return w * DPW + j;
+        return j < DPA ? w * DPA + j : j < DPA + DPB ? NPA + w * DPB + j - DPA : NPA + NPB + w * DPS + j - DPA - DPB;
+    }
+    __host__ __device__ static constexpr int dst(int d) {
+        return (!F::SCALED || d < NPA + NPB) ? d * 1024 : A_BYTES + B_BYTES + (d - NPA - NPB) * 256;
+    }
+    static_assert(A_ROW == 16 * F::CPK * KBS && 1024 % A_ROW == 0 && WPT >= 1 && (AT == 2 || AT == 4), "tiling");
+    static_assert(NP % WAVES == 0 && (!BY_KIND || (NPA % WAVES == 0 && NPB % WAVES == 0 && NPS % WAVES == 0)), "pieces");
+    static_assert(S >= 2 && S <= 8 && (S - 1) * DPW <= 63, "ring depth (vmcnt counts 63 loads)");
+    // (SA > S: A(s) must be issued in an earlier iteration than B(s), the wait below counts on it; SA == S computed
+    // wrong sums in tools/pgemm_lab). A scaled format has one ring.
+    static_assert(SA == 0 || (!F::SCALED && Cfg::PIPE && S == 2 && SA > S && (SA - 1) * DPA + DPB <= 63), "split rings");
+    static_assert(LDS <= 160 * 1024, "LDS");
+};
+
+// Where piece d of a stage comes from: lane `lane` lands at byte 16 lane (scale piece: dword `lane`) of the piece, i.e.
+// image row lane / cpr, physical chunk lane % cpr (cpr = 16-B chunks per image row), so it loads the row's logical
+// chunk c = (lane % cpr) ^ swizzle(row); a scale piece's lane loads the byte of (k-block, tile row) = its dword.
+// The source is byte off + s adv of the row's K-slice at stage s. The last stage may be short: vkb < KBS valid
+// k-blocks. There a logical chunk c steps back to c mod (valid chunks) (`back` bytes; a weight k-block is CPK chunks,
+// an activation one 4, a scale one a byte): a reload of a valid part of the stage, in bounds and never read. Shared
+// with the host (tests/cpp/pgemm_pieces.cpp enumerates every piece of every table tiling).
+struct PgPiece {
+    int kind;  // 0: weights, 1: hi, 2: lo activations, 3: weight scales
+    int row;   // row of the block: weight row 16 tile + r of the row block, or chunk row of the position block
+    int off;   // byte of the row's stage-0 slice
+    int adv;   // bytes per stage
+    int back;  // bytes to step back in a short last stage
+    __host__ __device__ constexpr long at(int s, bool tail) const { return off + (long)s * adv - (tail ? back : 0); }
+};
+template <class Geo>
+__host__ __device__ constexpr PgPiece pg_piece(int d, int lane, int vkb) {
+    using F = typename Geo::F;
+    if (d < Geo::NPA) {
+        constexpr int cpr = Geo::A_ROW / 16;
+        const int o = d * 1024;
+        const int r = (o % Geo::A_IMG) / Geo::A_ROW + lane / cpr;
+        const int c = (lane % cpr) ^ F::swz(r);
+        return {0, o / Geo::A_IMG * 16 + r, c * 16, Geo::A_ROW, (c - c % (F::CPK * vkb)) * 16};
+    } else if (!F::SCALED || d < Geo::NPA + Geo::NPB) {
+        constexpr int cpr = Geo::B_ROW / 16;
+        const int o = (d - Geo::NPA) * 1024;
+        const int u = o / Geo::B_IMG;  // image 2 pt + (lo ? 1 : 0)
+        const int r = (o % Geo::B_IMG) / Geo::B_ROW + lane / cpr;
+        const int c = (lane % cpr) ^ pg_swz(r, Geo::B_ROW);
+        return {1 + (u & 1), (u >> 1) * 16 + r, c * 16, Geo::B_ROW, (c - c % (4 * vkb)) * 16};
+    } else {  // dword q of the scale image [k-block][tile row]
+        const int q = (d - Geo::NPA - Geo::NPB) * 64 + lane;
+        const int kb = q / (Geo::NA * 16);
+        return {3, q - kb * (Geo::NA * 16), kb, Geo::KBS, kb - kb % vkb};
+    }
+}
 
 // wait until at most `later` stages of DPW images each are still in flight (later: 0 .. 6)
 template <int DPW>
@@ -199,10 +314,13 @@ __device__ __forceinline__ void pg_wait_stages(int later) {
 template <class Epi, class Cfg, typename WT>
 __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi epi, const PfState* __restrict__ ps) {
     using Geo = PgGeo<Cfg, WT>;
-    constexpr int KBS = Geo::KBS, BM = Geo::BM, WR = Geo::WR, S = Geo::S;
+    using F = typename Geo::F;
+    constexpr int KBS = Geo::KBS, BM = Geo::BM, WR = Geo::WR, S = Geo::S, AT = Geo::AT, NA = Geo::NA, WPT = Geo::WPT;
+    constexpr int DPW = Geo::DPW, DPA = Geo::DPA, DPB = Geo::DPB;
     extern __shared__ __attribute__((aligned(1024))) char pg_smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    __builtin_assume(wave >= 0 && wave < Geo::WAVES);
     const int wr = wave % WR, wp = wave / WR;  // row pair, position half
     const int PB = in.M / BM;
     // workgroups that share a row block run on one XCD (blocks b and b + 8 share one under round-robin
@@ -211,87 +329,72 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
     const int rb = (slot / PB) * 8 + xcd, pb = slot - (slot / PB) * PB;
     const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
     if (rb >= nrb) return;  // (uniform) padding of the grid to a multiple of 8 row blocks
-    // stages: K is a multiple of 64, so with int8 weights (KS 128) the last stage may be a half stage. Its DMA
-    // pieces past the row's end reload the stage's first half instead (in bounds; never read), and only its
-    // first KBS / 2 k-blocks are multiplied.
+    // stages: the last one may be short, kt / 32 valid k-blocks: its pieces step back (pg_piece), and only its valid
+    // k-blocks are multiplied. K is a multiple of 64 (the callers' check), so a short 128-k stage holds KBS / 2; the
+    // pipelined loop, which multiplies k-blocks in pairs, is told so and tests once per pair.
     const int ns = (in.K + Geo::KS - 1) / Geo::KS;
-    const bool half_tail = (in.K % Geo::KS) != 0;
-    const int nt = in.N >> 4;       // row tiles
+    const int kt = in.K % Geo::KS;  // depth of a short last stage (0: none)
+    const bool half_tail = kt != 0;
+    const int vkb = half_tail ? (Cfg::PIPE ? KBS / 2 : kt / 32) : KBS;  // k-blocks of the last stage
+    const int nt = in.N >> 4;                   // row tiles
     const unsigned ring = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)pg_smem;
 
-    // this wave's DMA instructions d in [wave*DPW, (wave+1)*DPW): stage bytes [1024 d, 1024 (d + 1)). Lane i
-    // lands at byte 16 i of it: image row i / cpr, physical chunk i % cpr (cpr = 16-B chunks per image row),
-    // so it loads the row's logical chunk (i % cpr) ^ swizzle(row).
-    const char* src[Geo::DPW];
-    int adv[Geo::DPW];   // bytes per stage
-    int back[Geo::DPW];  // bytes to step back in a half last stage (logical chunk in the stage's second half)
+    // this wave's pieces Geo::piece(wave, j): stage-0 source, bytes per stage, the short last stage's step back
+    const char* src[DPW];
+    int adv[DPW], back[DPW];
 #pragma unroll
-    for (int j = 0; j < Geo::DPW; ++j) {
-        // split rings: the wave's DPA pieces of the A images, then its DPB pieces of the B images
-        const int off = Geo::SA ? (j < Geo::DPA ? (wave * Geo::DPA + j) * 1024
-                                                : Geo::A_BYTES + (wave * Geo::DPB + j - Geo::DPA) * 1024)
-                                : (wave * Geo::DPW + j) * 1024;
-        if (off < Geo::A_BYTES) {
-            const int t = rb * Geo::NA + off / Geo::A_IMG;
-            const int r = (off % Geo::A_IMG) / Geo::A_ROW + lane / 8;
-            const int c = (lane % 8) ^ pg_swz(r, Geo::A_ROW);
-            const int row = epi.row(min(t, nt - 1), r);
-            src[j] = reinterpret_cast<const char*>(in.W) + (size_t)row * in.K * sizeof(WT) + c * 16;
-            adv[j] = Geo::A_ROW;
-            back[j] = c >= 4 ? Geo::A_ROW / 2 : 0;
+    for (int j = 0; j < DPW; ++j) {
+        const PgPiece p = pg_piece<Geo>(Geo::piece(wave, j), lane, vkb);
+        const char* rowp;
+        if (p.kind == 0 || (F::SCALED && p.kind == 3)) {
+            const int row = epi.row(min(rb * NA + (p.row >> 4), nt - 1), p.row & 15);
+            if (F::SCALED && p.kind == 3)
+                rowp = reinterpret_cast<const char*>(in.Ws) + (size_t)row * (in.K / kMxBlock);
+            else
+                rowp = reinterpret_cast<const char*>(in.W) + (size_t)row * wt_row_bytes<WT>(in.K);
         } else {
-            constexpr int cpr = Geo::B_ROW / 16;
-            const int o2 = off - Geo::A_BYTES;
-            const int u = o2 / Geo::B_IMG, pt = u >> 1;
-            const int r = (o2 % Geo::B_IMG) / Geo::B_ROW + lane / cpr;
-            const int c = (lane % cpr) ^ pg_swz(r, Geo::B_ROW);
-            const __half* B = (u & 1) ? in.Blo : in.Bhi;
-            const int m = pb * BM + pt * 16 + r;
-            src[j] = reinterpret_cast<const char*>(B) + (size_t)m * in.K * 2 + c * 16;
-            adv[j] = Geo::B_ROW;
-            back[j] = c >= cpr / 2 ? Geo::B_ROW / 2 : 0;
+            const __half* B = p.kind == 2 ? in.Blo : in.Bhi;
+            rowp = reinterpret_cast<const char*>(B) + (size_t)(pb * BM + p.row) * in.K * 2;
         }
+        src[j] = rowp + p.off;
+        adv[j] = p.adv;
+        back[j] = p.back;
     }
-    auto issue = [&](int s) {
-        const unsigned dst = ring + (unsigned)((s % S) * Geo::STAGE);
+    // pieces [j0, j1) of stage s; `slot`: the LDS address the stage image would start at
+    auto issue_pieces = [&](int s, int j0, int j1, unsigned slot) {
         const bool tail = half_tail && s == ns - 1;
 #pragma unroll
-        for (int j = 0; j < Geo::DPW; ++j) {
+        for (int j = j0; j < j1; ++j) {
+            const int d = Geo::piece(wave, j);
 #ifdef PG_LAB_SKIP  // tools/pgemm_lab only (bit 0: no A pieces, bit 1: no B pieces): timing bounds, wrong sums
-            const bool isa = (wave * Geo::DPW + j) * 1024 < Geo::A_BYTES;
-            if (((PG_LAB_SKIP & 1) && isa) || ((PG_LAB_SKIP & 2) && !isa)) continue;
+            if (((PG_LAB_SKIP & 1) && d < Geo::NPA) || ((PG_LAB_SKIP & 2) && d >= Geo::NPA && d < Geo::NPA + Geo::NPB))
+                continue;
 #endif
-            lm_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPW + j) * 1024));
+            // (one offset, then one add: subtracted from src on its own, the step-back is hoisted out of the stage loop
+            // as a second pointer per piece, 2 VGPRs each)
+            const char* g = src[j] + ((ptrdiff_t)s * adv[j] - (tail ? back[j] : 0));
+            if (F::SCALED && j >= DPA + DPB)
+                lm_dma_u8(g, slot + (unsigned)Geo::dst(d));
+            else
+                lm_dma(g, slot + (unsigned)Geo::dst(d));
         }
     };
-
+    auto issue = [&](int s) { issue_pieces(s, 0, DPW, ring + (unsigned)((s % S) * Geo::STAGE)); };
     // split rings: A stage s in slot s % SA at ring, B stage s in slot s % 2 behind the A ring
-    const unsigned ring_b = ring + (unsigned)(Geo::SA * Geo::A_BYTES);
-    auto issue_a = [&](int s) {
-        const unsigned dst = ring + (unsigned)((s % Geo::SA) * Geo::A_BYTES);
-        const bool tail = half_tail && s == ns - 1;
-#pragma unroll
-        for (int j = 0; j < Geo::DPA; ++j)
-            lm_dma(src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0), dst + (unsigned)((wave * Geo::DPA + j) * 1024));
-    };
+    constexpr int SAD = Geo::SA ? Geo::SA : 1;
+    auto issue_a = [&](int s) { issue_pieces(s, 0, DPA, ring + (unsigned)((s % SAD) * Geo::A_BYTES)); };
     auto issue_b = [&](int s) {
-        const unsigned dst = ring_b + (unsigned)((s & 1) * Geo::B_BYTES);
-        const bool tail = half_tail && s == ns - 1;
-#pragma unroll
-        for (int j = 0; j < Geo::DPB; ++j)
-            lm_dma(src[Geo::DPA + j] + (size_t)s * adv[Geo::DPA + j] - (tail ? back[Geo::DPA + j] : 0),
-                   dst + (unsigned)((wave * Geo::DPB + j) * 1024));
+        issue_pieces(s, DPA, DPA + DPB, ring + (unsigned)((Geo::SA - 1) * Geo::A_BYTES + (s & 1) * Geo::B_BYTES));
     };
-    constexpr int AT = Geo::AT;
-    lm_float4 acc[AT][Geo::WPT];
+    lm_float4 acc[AT][WPT];
 #pragma unroll
     for (int a = 0; a < AT; ++a)
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int b = 0; b < WPT; ++b) acc[a][b] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
 
     // fragment read offsets: lane l reads row / column r = l & 15, k group kg = l >> 4 of each 32-k block
     const int kg = lane >> 4, r16 = lane & 15;
-    const int sa = pg_swz(r16, Geo::A_ROW), sb = pg_swz(r16, Geo::B_ROW);
+    const int sa = F::swz(r16), sb = pg_swz(r16, Geo::B_ROW);
     if constexpr (Geo::SA == 0) {
         for (int s = 0; s < S - 1 && s < ns; ++s) issue(s);
     } else {  // the schedule of iterations -(SA - 1) .. -1: B(i + 1), then A(i + SA - 1)
@@ -300,362 +403,130 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
             if (i + Geo::SA - 1 >= 0 && i + Geo::SA - 1 < ns) issue_a(i + Geo::SA - 1);
         }
     }
-    // fragments of k-block kb of stage buffer st (A images at st, B images at stb) into (af, bh, bl)
-    auto read_frags = [&](const char* st, const char* stb, int kb, u32x4(&af)[AT], u32x4(&bh)[Geo::WPT],
-                          u32x4(&bl)[Geo::WPT]) {
+    // the fragments of one k-block; sc (scaled formats): the scale dwords of this lane's C rows 4 kg .. +4 per tile
+    struct Frags {
+        u32x4 a[AT], h[WPT], l[WPT], sc[F::SCALED ? AT : 1];
+    };
+    // k-block kb of a stage buffer (A images at st; B images, then the scale image, at stb)
+    auto read_frags = [&](const char* st, const char* stb, int kb, Frags& f) {
 #pragma unroll
         for (int a = 0; a < AT; ++a) {
-            const char* img = st + (wr * AT + a) * Geo::A_IMG + r16 * Geo::A_ROW;
-            if constexpr (sizeof(WT) == 2) {
-                af[a] = *reinterpret_cast<const u32x4*>(img + ((4 * kb + kg) ^ sa) * 16);
-            } else {
-                const int off = ((2 * kb + (kg >> 1)) ^ sa) * 16 + 8 * (kg & 1);
-                af[a] = pg_i8_to_f16(*reinterpret_cast<const uint2*>(img + off));
-            }
+            const int ti = wr * AT + a;
+            f.a[a] = F::a_frag(st + ti * Geo::A_IMG + r16 * Geo::A_ROW + F::a_off(kb, kg, sa));
+            if constexpr (F::SCALED)
+                f.sc[a] = *reinterpret_cast<const u32x4*>(stb + Geo::B_BYTES + ((kb * NA + ti) * 16 + 4 * kg) * 4);
         }
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) {
-            const int pt = wp * Geo::WPT + b;
+        for (int b = 0; b < WPT; ++b) {
+            const int pt = wp * WPT + b;
             const char* img = stb + (2 * pt) * Geo::B_IMG + r16 * Geo::B_ROW + ((4 * kb + kg) ^ sb) * 16;
-            bh[b] = *reinterpret_cast<const u32x4*>(img);
-            bl[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
+            f.h[b] = *reinterpret_cast<const u32x4*>(img);
+            f.l[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
         }
     };
-    auto mfmas = [&](const u32x4(&af)[AT], const u32x4(&bh)[Geo::WPT], const u32x4(&bl)[Geo::WPT]) {
+    // every hi MFMA of the k-block, then every lo one: into acc, or (scaled) into a zeroed tile that one fp32 fma
+    // per C row adds to acc times 2^(byte - 127)
+    auto mfmas = [&](const Frags& f) {
+        lm_float4 tile[AT][WPT];
+        lm_float4(&t)[AT][WPT] = *(F::SCALED ? &tile : &acc);
+#if defined(PG_LAB_MFMA) && PG_LAB_MFMA == 0  // tools/pgemm_lab only: no MFMA (data movement alone)
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b)
+        for (int b = 0; b < WPT; ++b)
 #pragma unroll
-            for (int a = 0; a < AT; ++a) acc[a][b] = lm_mfma(af[a], bh[b], acc[a][b]);
-#pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b)
-#pragma unroll
-            for (int a = 0; a < AT; ++a) acc[a][b] = lm_mfma(af[a], bl[b], acc[a][b]);
-    };
-    if constexpr (Cfg::PIPE) {
-        // set X holds even k-blocks, set Y odd ones (KBS is even; an int8 half stage has KBS / 2 = 2): per stage
-        // read(0) -> X, MFMA(Y: the previous stage's last k-block), read(1) -> Y, MFMA(X), ... The stage barrier
-        // follows this wave's lgkmcnt(0), so the previous stage's buffer is free for the DMA issued after it while
-        // its last fragments wait in registers.
-        static_assert(KBS % 2 == 0, "k-blocks per stage");
-        u32x4 xa[AT], xh[Geo::WPT], xl[Geo::WPT], ya[AT], yh[Geo::WPT], yl[Geo::WPT];
-        for (int s = 0; s < ns; ++s) {
-            const char *st, *stb;
-            if constexpr (Geo::SA == 0) {
-                pg_wait_stages<Geo::DPW>(min(S - 2, ns - 1 - s));
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (s + S - 1 < ns) issue(s + S - 1);
-                st = pg_smem + (size_t)(s % S) * Geo::STAGE;
-                stb = st + Geo::A_BYTES;
-            } else {
-                // B(s) was the first load of iteration s - 1; only that iteration's A pieces (if it issued any) were
-                // issued after it, and A(s) before it
-                if (s + Geo::SA - 2 < ns)
-                    lm_wait_vm<Geo::DPA>();
-                else
-                    lm_wait_vm<0>();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                if (s + 1 < ns) issue_b(s + 1);
-                if (s + Geo::SA - 1 < ns) issue_a(s + Geo::SA - 1);
-                st = pg_smem + (size_t)(s % Geo::SA) * Geo::A_BYTES;
-                stb = pg_smem + (size_t)Geo::SA * Geo::A_BYTES + (size_t)(s & 1) * Geo::B_BYTES;
+            for (int a = 0; a < AT; ++a) {
+                t[a][b] = F::SCALED ? lm_float4{0.0f, 0.0f, 0.0f, 0.0f} : acc[a][b];
+                t[a][b][0] += __uint_as_float(f.a[a][0] ^ f.h[b][0] ^ f.l[b][0]);
             }
-            const int kbs = (half_tail && s == ns - 1) ? KBS / 2 : KBS;  // wave-uniform, even
+#else
+#pragma unroll
+        for (int b = 0; b < WPT; ++b)
+#pragma unroll
+            for (int a = 0; a < AT; ++a)
+                t[a][b] = lm_mfma(f.a[a], f.h[b], F::SCALED ? lm_float4{0.0f, 0.0f, 0.0f, 0.0f} : acc[a][b]);
+#if !(defined(PG_LAB_MFMA) && PG_LAB_MFMA == 1)  // PG_LAB_MFMA 1: the hi MFMA only
+#pragma unroll
+        for (int b = 0; b < WPT; ++b)
+#pragma unroll
+            for (int a = 0; a < AT; ++a) t[a][b] = lm_mfma(f.a[a], f.l[b], t[a][b]);
+#endif
+#endif
+        if constexpr (F::SCALED) {
+#pragma unroll
+            for (int a = 0; a < AT; ++a) {
+                float sc[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sc[e] = __uint_as_float(f.sc[a][e] << 23);
+#pragma unroll
+                for (int b = 0; b < WPT; ++b)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[a][b][e] = fmaf(tile[a][b][e], sc[e], acc[a][b][e]);
+            }
+        }
+    };
+    // PIPE: set x holds even k-blocks, set y odd ones (KBS is even, and so is a short stage's KBS / 2 at 128-k
+    // stages): per stage read(0) -> x, MFMA(y: the previous stage's last k-block), read(1) -> y, MFMA(x), ... The
+    // stage barrier follows this wave's lgkmcnt(0), so the previous stage's buffer is free for the DMA issued after it
+    // while its last fragments wait in registers.
+    static_assert(!Cfg::PIPE || (KBS % 2 == 0 && (KBS / 2 % 2 == 0 || Geo::KS == 64)), "k-blocks per stage");
+    Frags x, y;
+    for (int s = 0; s < ns; ++s) {
+        const char *st, *stb;
+        if constexpr (Geo::SA == 0) {
+            // this wave's pieces of stage s landed: it issued whole stages only, DPW LDS-DMAs each and nothing else
+            // that the counter counts, so at most min(S - 2, ns - 1 - s) later stages are behind them in order
+            pg_wait_stages<DPW>(min(S - 2, ns - 1 - s));
+            if constexpr (Cfg::PIPE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();  // every wave's pieces of s landed; every wave is done with s - 1
+            if (s + S - 1 < ns) issue(s + S - 1);  // into the buffer of s - 1
+            st = pg_smem + (size_t)(s % S) * Geo::STAGE;
+            stb = st + Geo::A_BYTES;
+        } else {
+            // B(s) was the first load of iteration s - 1; only that iteration's A pieces (if it issued any) were
+            // issued after it, and A(s) before it
+            if (s + Geo::SA - 2 < ns)
+                lm_wait_vm<DPA>();
+            else
+                lm_wait_vm<0>();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (s + 1 < ns) issue_b(s + 1);
+            if (s + Geo::SA - 1 < ns) issue_a(s + Geo::SA - 1);
+            st = pg_smem + (size_t)(s % SAD) * Geo::A_BYTES;
+            stb = pg_smem + (size_t)Geo::SA * Geo::A_BYTES + (size_t)(s & 1) * Geo::B_BYTES;
+        }
+        const int kbs = s == ns - 1 ? vkb : KBS;  // wave-uniform
+        if constexpr (Cfg::PIPE) {
 #pragma unroll
             for (int kb = 0; kb < KBS; kb += 2) {
                 if (kb >= kbs) break;
-                read_frags(st, stb, kb, xa, xh, xl);
-                if (s > 0 || kb > 0) mfmas(ya, yh, yl);
-                read_frags(st, stb, kb + 1, ya, yh, yl);
-                mfmas(xa, xh, xl);
+                read_frags(st, stb, kb, x);
+                if (s > 0 || kb > 0) mfmas(y);
+                read_frags(st, stb, kb + 1, y);
+                mfmas(x);
+            }
+        } else {
+#pragma unroll
+            for (int kb = 0; kb < KBS; ++kb) {
+                if (kb >= kbs) break;
+                read_frags(st, stb, kb, x);
+                mfmas(x);
             }
         }
-        mfmas(ya, yh, yl);
-    } else {
-    for (int s = 0; s < ns; ++s) {
-        // this wave's pieces of stage s landed (stages s + 1 .. s + S - 2 may stay in flight)
-        pg_wait_stages<Geo::DPW>(min(S - 2, ns - 1 - s));
-        __builtin_amdgcn_s_barrier();  // every wave's pieces of s landed; every wave is done with s - 1
-        if (s + S - 1 < ns) issue(s + S - 1);  // into the buffer of s - 1
-        const char* st = pg_smem + (size_t)(s % S) * Geo::STAGE;
-        const int kbs = (half_tail && s == ns - 1) ? KBS / 2 : KBS;  // wave-uniform
-#pragma unroll
-        for (int kb = 0; kb < KBS; ++kb) {
-            if (kb >= kbs) break;
-            u32x4 af[AT], bh[Geo::WPT], bl[Geo::WPT];
-#pragma unroll
-            for (int a = 0; a < AT; ++a) {
-                const char* img = st + (wr * AT + a) * Geo::A_IMG + r16 * Geo::A_ROW;
-                if constexpr (sizeof(WT) == 2) {
-                    af[a] = *reinterpret_cast<const u32x4*>(img + ((4 * kb + kg) ^ sa) * 16);
-                } else {  // k 32 kb + 8 kg .. +8: chunk 2 kb + kg / 2, half kg % 2
-                    const int off = ((2 * kb + (kg >> 1)) ^ sa) * 16 + 8 * (kg & 1);
-                    af[a] = pg_i8_to_f16(*reinterpret_cast<const uint2*>(img + off));
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < Geo::WPT; ++b) {
-                const int pt = wp * Geo::WPT + b;
-                const char* img = st + Geo::A_BYTES + (2 * pt) * Geo::B_IMG + r16 * Geo::B_ROW + ((4 * kb + kg) ^ sb) * 16;
-                bh[b] = *reinterpret_cast<const u32x4*>(img);
-                bl[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int a = 0; a < AT; ++a)
-#pragma unroll
-                for (int b = 0; b < Geo::WPT; ++b) {
-#if defined(PG_LAB_MFMA) && PG_LAB_MFMA == 0  // tools/pgemm_lab only: no MFMA (data movement alone)
-                    acc[a][b][0] += __uint_as_float(af[a][0] ^ bh[b][0] ^ bl[b][0]);
-#else
-                    acc[a][b] = lm_mfma(af[a], bh[b], acc[a][b]);
-#if !(defined(PG_LAB_MFMA) && PG_LAB_MFMA == 1)  // PG_LAB_MFMA 1: the hi MFMA only
-                    acc[a][b] = lm_mfma(af[a], bl[b], acc[a][b]);
-#endif
-#endif
-                }
-        }
     }
-    }
+    if constexpr (Cfg::PIPE) mfmas(y);
     // C[i][n] of a 16x16 tile: lane l holds rows 4 (l >> 4) + r, column l & 15
-    const int i0 = 4 * (lane >> 4);
-#pragma unroll
-    for (int a = 0; a < AT; ++a) {
-        const int t = rb * Geo::NA + wr * AT + a;
-        if (t >= nt) continue;
-#pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) {
-            const int m = pb * BM + (wp * Geo::WPT + b) * 16 + r16;
-            const float v[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
-            epi.store(t, i0, m, v, ps);
-        }
-    }
-}
-
-// ---- MXFP4 weights (mxfp4.h: data [N][K/2], e8m0 scales [N][K/32]). A stage covers 128 k (PgCfg::KS 0 / 128): a
-// weight row's slice is half a line (64 B, one 1-KiB piece = one 16-row image), a chunk row's hi / lo slice two lines,
-// the int8 geometry, so BM = 128 still fits two stages; or 256 k (KS 256): whole weight lines, but the activation
-// image doubles to 16 KiB per position tile and BM <= 64 (the activations, 32 x the weight bytes per k, are what the
-// ring carries). pg_pick<mxfp4> holds whichever tools/pgemm_lab measured faster per cell.
-// Scale scheme: one MFMA k-block is one MX block, so a (weight row, k-block) has one scale 2^e. The e2m1 codes are
-// decoded to fp16 exactly and UNSCALED (a byte LUT through v_perm: the fp16 of every e2m1 magnitude has a zero low
-// byte); the hi and lo MFMAs of a k-block run into a zeroed tile and acc = fma(tile, 2^e_row, acc) per C-fragment row
-// in fp32, where every e8m0 byte 1 .. 254 is a normal number: no fp16 overflow or flush at any block exponent.
-// The scale bytes travel through the ring too: global_load_lds_ubyte, a byte per lane into a dword of the stage's
-// scale image [k-block][tile row], so a lane's four C rows of a tile are one ds_read_b128 and 2^e is dword << 23.
-// Every wave issues the same number of pieces per stage (NPW: A, B and scale pieces), all LDS-DMA, all counted by
-// pg_wait_stages<NPW>; the kernel has no plain global load between its first DMA and its last wait.
-template <class Cfg>
-struct PgGeoMx {
-    static constexpr int BM = Cfg::BM, WR = Cfg::WR, S = Cfg::S, AT = Cfg::AT;
-    static constexpr int WAVES = 2 * WR, THREADS = 64 * WAVES, BN = 16 * AT * WR;
-    static constexpr int KS = Cfg::KS ? Cfg::KS : 128, KBS = KS / 32;
-    static constexpr int A_ROW = KS / 2, B_ROW = KS * 2;  // 64 B and 256 B, or 128 B and 512 B
-    static constexpr int A_IMG = 16 * A_ROW, B_IMG = 16 * B_ROW;
-    static constexpr int PT = BM / 16, WPT = PT / 2, NA = AT * WR;
-    static constexpr int A_BYTES = NA * A_IMG, B_BYTES = 2 * PT * B_IMG;
-    static constexpr int SC_BYTES = NA * 16 * KBS * 4;  // a dword per (tile row, k-block)
-    static constexpr int STAGE = A_BYTES + B_BYTES + SC_BYTES;
-    static constexpr int DPA = A_BYTES / 1024 / WAVES, DPB = B_BYTES / 1024 / WAVES, DPS = SC_BYTES / 256 / WAVES;
-    static constexpr int NPW = DPA + DPB + DPS;  // LDS-DMA instructions per wave and stage
-    static constexpr size_t LDS = (size_t)S * STAGE;
-    static_assert((KS == 128 || KS == 256) && WPT >= 1 && (AT == 2 || AT == 4), "tiling");
-    static_assert((A_BYTES / 1024) % WAVES == 0 && (B_BYTES / 1024) % WAVES == 0 && (SC_BYTES / 256) % WAVES == 0, "pieces");
-    static_assert(S >= 2 && S <= 8 && (S - 1) * NPW <= 63, "ring depth (vmcnt counts 63 loads)");
-    static_assert(Cfg::SA == 0, "mxfp4: one ring");
-    static_assert(LDS <= 160 * 1024, "LDS");
-};
-
-// chunk swizzle of a weight image row (64 or 128 B): a k-block's fragment read is 16 rows x 16 B, 4 B per lane
-__device__ __forceinline__ int pg_mx_swz(int row, int row_bytes) { return row_bytes == 64 ? (row >> 2) & 3 : (row >> 1) & 7; }
-
-// 8 e2m1 codes (element 2i in bits 3:0 of byte i) -> 8 fp16, exact and unscaled, in element order. The high byte
-// of the fp16 of magnitude code c is {00, 38, 3C, 3E, 40, 42, 44, 46}[c] (0, .5, 1, 1.5, 2, 3, 4, 6), the low byte 0.
-__device__ __forceinline__ u32x4 pg_fp4_to_f16(unsigned w) {
-    const unsigned lut_hi = 0x46444240u, lut_lo = 0x3E3C3800u;
-    unsigned ev = __builtin_amdgcn_perm(lut_hi, lut_lo, w & 0x07070707u);         // elements 0, 2, 4, 6
-    unsigned od = __builtin_amdgcn_perm(lut_hi, lut_lo, (w >> 4) & 0x07070707u);  // elements 1, 3, 5, 7
-    ev |= (w & 0x08080808u) << 4;  // the sign bits
-    od |= w & 0x80808080u;
-    u32x4 r;  // dword i = {00, ev_i, 00, od_i} (selector 0x0c: a zero byte)
-    r[0] = __builtin_amdgcn_perm(od, ev, 0x040c000cu);
-    r[1] = __builtin_amdgcn_perm(od, ev, 0x050c010cu);
-    r[2] = __builtin_amdgcn_perm(od, ev, 0x060c020cu);
-    r[3] = __builtin_amdgcn_perm(od, ev, 0x070c030cu);
-    return r;
-}
-
-struct PgInMx {
-    const uint8_t* W;   // [N][K / 2]
-    const uint8_t* Ws;  // [N][K / 32]
-    const __half* Bhi;
-    const __half* Blo;
-    int N, K, M;
-};
-
-template <class Epi, class Cfg>
-__global__ void __launch_bounds__(128 * Cfg::WR) pgemm_mx_kernel(PgInMx in, Epi epi, const PfState* __restrict__ ps) {
-    using Geo = PgGeoMx<Cfg>;
-    constexpr int KBS = Geo::KBS, BM = Geo::BM, WR = Geo::WR, S = Geo::S, AT = Geo::AT, NA = Geo::NA;
-    extern __shared__ __attribute__((aligned(1024))) char pg_smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wr = wave % WR, wp = wave / WR;
-    const int PB = in.M / BM;
-    const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;  // as pgemm_kernel
-    const int rb = (slot / PB) * 8 + xcd, pb = slot - (slot / PB) * PB;
-    const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
-    if (rb >= nrb) return;
-    // K % 64 == 0: the last stage may hold 64 k (128-k stages) or 64, 128 or 192 k (256-k stages), kt / 32 whole
-    // k-blocks. Its pieces past the row's end (data, scales and activations alike) reload the valid part of the
-    // stage instead (logical chunk c -> c % valid chunks: in bounds; never read), and only its valid k-blocks are
-    // multiplied.
-    const int ns = (in.K + Geo::KS - 1) / Geo::KS;
-    const int kt = in.K % Geo::KS;  // k of a short last stage (0: none)
-    const bool half_tail = kt != 0;
-    const int vkb = half_tail ? kt / 32 : KBS;  // its k-blocks: a 16-B weight chunk and a scale byte each
-    const int nt = in.N >> 4;
-    const unsigned ring = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)pg_smem;
-
-    // this wave's pieces: DPA weight pieces (16 rows x 64 B with the 16-B chunks XORed with row / 4, or 8 rows x
-    // 128 B XORed with row / 2: the fragment reads, 4 B per lane, then cover 64 banks), DPB activation pieces (4 rows
-    // x 256 B or 2 x 512 B, chunks XORed with the row), DPS scale pieces
-    const char* src[Geo::NPW];
-    int adv[Geo::NPW], back[Geo::NPW];
-    unsigned dsto[Geo::NPW];
-#pragma unroll
-    for (int j = 0; j < Geo::NPW; ++j) {
-        if (j < Geo::DPA) {
-            constexpr int cpr = Geo::A_ROW / 16;
-            const int off = (wave * Geo::DPA + j) * 1024;
-            const int ti = off / Geo::A_IMG;  // weight tile of the block
-            const int r = (off % Geo::A_IMG) / Geo::A_ROW + lane / cpr;
-            const int c = (lane % cpr) ^ pg_mx_swz(r, Geo::A_ROW);
-            const int row = epi.row(min(rb * NA + ti, nt - 1), r);
-            src[j] = reinterpret_cast<const char*>(in.W) + (size_t)row * (in.K / 2) + c * 16;
-            adv[j] = Geo::A_ROW;
-            back[j] = (c - c % vkb) * 16;
-            dsto[j] = (unsigned)off;
-        } else if (j < Geo::DPA + Geo::DPB) {
-            constexpr int cpr = Geo::B_ROW / 16;
-            const int o2 = (wave * Geo::DPB + j - Geo::DPA) * 1024;
-            const int u = o2 / Geo::B_IMG, pt = u >> 1;
-            const int r = (o2 % Geo::B_IMG) / Geo::B_ROW + lane / cpr;
-            const int c = (lane % cpr) ^ pg_swz(r, Geo::B_ROW);
-            const __half* B = (u & 1) ? in.Blo : in.Bhi;
-            const int m = pb * BM + pt * 16 + r;
-            src[j] = reinterpret_cast<const char*>(B) + (size_t)m * in.K * 2 + c * 16;
-            adv[j] = Geo::B_ROW;
-            back[j] = (c - c % (4 * vkb)) * 16;  // four 16-B chunks of 8 fp16 per k-block
-            dsto[j] = (unsigned)(Geo::A_BYTES + o2);
-        } else {  // dword d of the scale image [k-block][tile row]
-            const int q = wave * Geo::DPS + j - Geo::DPA - Geo::DPB;
-            const int d = q * 64 + lane;
-            const int kb = d / (NA * 16), tr = d - kb * (NA * 16);
-            const int row = epi.row(min(rb * NA + (tr >> 4), nt - 1), tr & 15);
-            src[j] = reinterpret_cast<const char*>(in.Ws) + (size_t)row * (in.K / kMxBlock) + kb;
-            adv[j] = KBS;
-            back[j] = kb - kb % vkb;
-            dsto[j] = (unsigned)(Geo::A_BYTES + Geo::B_BYTES + q * 256);
-        }
-    }
-    auto issue = [&](int s) {
-        const unsigned dst = ring + (unsigned)((s % S) * Geo::STAGE);
-        const bool tail = half_tail && s == ns - 1;
-#pragma unroll
-        for (int j = 0; j < Geo::NPW; ++j) {
-            const char* g = src[j] + (size_t)s * adv[j] - (tail ? back[j] : 0);
-            if (j < Geo::DPA + Geo::DPB)
-                lm_dma(g, dst + dsto[j]);
-            else
-                lm_dma_u8(g, dst + dsto[j]);
-        }
-    };
-    lm_float4 acc[AT][Geo::WPT];
-#pragma unroll
-    for (int a = 0; a < AT; ++a)
-#pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) acc[a][b] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
-
-    const int kg = lane >> 4, r16 = lane & 15;
-    const int sa = pg_mx_swz(r16, Geo::A_ROW), sb = pg_swz(r16, Geo::B_ROW);
-    for (int s = 0; s < S - 1 && s < ns; ++s) issue(s);
-    for (int s = 0; s < ns; ++s) {
-        // this wave's NPW pieces of stage s landed: it issued whole stages only, NPW LDS-DMAs each and nothing else
-        // that the counter counts, so at most min(S - 2, ns - 1 - s) later stages are behind them in order
-        pg_wait_stages<Geo::NPW>(min(S - 2, ns - 1 - s));
-        __builtin_amdgcn_s_barrier();  // every wave's pieces of s landed; every wave has read s - 1 (its MFMAs, which
-                                       // wait for their operands, precede this barrier in program order)
-        if (s + S - 1 < ns) issue(s + S - 1);
-        const char* st = pg_smem + (size_t)(s % S) * Geo::STAGE;
-        const char* stb = st + Geo::A_BYTES;
-        const char* sts = stb + Geo::B_BYTES;
-        const int kbs = s == ns - 1 ? vkb : KBS;  // wave-uniform
-#pragma unroll
-        for (int kb = 0; kb < KBS; ++kb) {
-            if (kb >= kbs) break;
-            u32x4 af[AT], sc[AT], bh[Geo::WPT], bl[Geo::WPT];
-#pragma unroll
-            for (int a = 0; a < AT; ++a) {
-                const int ti = wr * AT + a;
-                // k 32 kb + 8 kg .. +8 of row r16: chunk kb, bytes 4 kg .. +4
-                const unsigned w = *reinterpret_cast<const unsigned*>(st + ti * Geo::A_IMG + r16 * Geo::A_ROW +
-                                                                      ((kb ^ sa) * 16) + 4 * kg);
-                af[a] = pg_fp4_to_f16(w);
-                // the scale dwords of this lane's C rows 4 kg .. +4 of the tile
-                sc[a] = *reinterpret_cast<const u32x4*>(sts + ((kb * NA + ti) * 16 + 4 * kg) * 4);
-            }
-#pragma unroll
-            for (int b = 0; b < Geo::WPT; ++b) {
-                const int pt = wp * Geo::WPT + b;
-                const char* img = stb + (2 * pt) * Geo::B_IMG + r16 * Geo::B_ROW + ((4 * kb + kg) ^ sb) * 16;
-                bh[b] = *reinterpret_cast<const u32x4*>(img);
-                bl[b] = *reinterpret_cast<const u32x4*>(img + Geo::B_IMG);
-            }
-            lm_float4 tmp[AT][Geo::WPT];
-#pragma unroll
-            for (int b = 0; b < Geo::WPT; ++b)
-#pragma unroll
-                for (int a = 0; a < AT; ++a) tmp[a][b] = lm_mfma(af[a], bh[b], lm_float4{0.0f, 0.0f, 0.0f, 0.0f});
-#pragma unroll
-            for (int b = 0; b < Geo::WPT; ++b)
-#pragma unroll
-                for (int a = 0; a < AT; ++a) tmp[a][b] = lm_mfma(af[a], bl[b], tmp[a][b]);
-#pragma unroll
-            for (int a = 0; a < AT; ++a) {
-                float f[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) f[e] = __uint_as_float(sc[a][e] << 23);  // 2^(byte - 127)
-#pragma unroll
-                for (int b = 0; b < Geo::WPT; ++b)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[a][b][e] = fmaf(tmp[a][b][e], f[e], acc[a][b][e]);
-            }
-        }
-    }
     const int i0 = 4 * (lane >> 4);
 #pragma unroll
     for (int a = 0; a < AT; ++a) {
         const int t = rb * NA + wr * AT + a;
         if (t >= nt) continue;
 #pragma unroll
-        for (int b = 0; b < Geo::WPT; ++b) {
-            const int m = pb * BM + (wp * Geo::WPT + b) * 16 + r16;
+        for (int b = 0; b < WPT; ++b) {
+            const int m = pb * BM + (wp * WPT + b) * 16 + r16;
             const float v[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
             epi.store(t, i0, m, v, ps);
         }
     }
-}
-
-template <class Epi, class Cfg>
-hipError_t launch_pgemm_mx(const PgInMx& in, const Epi& epi, const PfState* ps, hipStream_t s) {
-    using Geo = PgGeoMx<Cfg>;
-    const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
-    const int nrb8 = (nrb + 7) / 8 * 8;
-    const dim3 grid(nrb8 * (in.M / Geo::BM));
-    hipLaunchKernelGGL((pgemm_mx_kernel<Epi, Cfg>), grid, dim3(Geo::THREADS), Geo::LDS, s, in, epi, ps);
-    return hipGetLastError();
 }
 
 // ---- epilogues. Tiles hold 4-row groups {first(u), first(u + 1), second(u), second(u + 1)} where a pair is a
@@ -786,12 +657,8 @@ hipError_t launch_pgemm(const PgIn<WT>& in, const Epi& epi, const PfState* ps, h
 
 template <class Epi, class Cfg, typename WT>
 hipError_t pgemm_allow_lds() {
-    if constexpr (is_mx<WT>::value)
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_mx_kernel<Epi, Cfg>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeoMx<Cfg>::LDS);
-    else
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_kernel<Epi, Cfg, WT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeo<Cfg, WT>::LDS);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&pgemm_kernel<Epi, Cfg, WT>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)PgGeo<Cfg, WT>::LDS);
 }
 
 // The GEMM tiling (PgCfg<BM, WR, S, AT, PIPE, SA>) per weight type, projection role and chunk size: the fastest of
@@ -804,11 +671,9 @@ hipError_t pgemm_allow_lds() {
 template <typename WT, class F>
 int pg_pick(int M, int role, F&& f) {
     if constexpr (is_mx<WT>::value) {
-        // pgemm_mx_kernel (PIPE and SA are not knobs of it): the fastest of tools/pgemm_lab's LAB_MX sweep per 7B
-        // shape and chunk size, weights rotated over four copies (profiles/mxfp4_pgemm_lab.txt). 256-k stages tie the
-        // 128-k ones at BM = 32 (within 1 %), lose at BM = 64 (148 KiB: one workgroup per CU) and cannot take BM = 128
-        // or 8 waves at BM = 64, the fastest q/k/v and gate/up tilings, so every cell is a 128-k one; wo / down (N = D,
-        // few row blocks) want 32-row chunk blocks.
+        // the fastest of tools/pgemm_lab's LAB_MX sweep per 7B shape and chunk size, weights rotated over four copies
+        // (profiles/mxfp4_pgemm_lab.txt; PIPE is not yet measured for this format, SA is refused for it). wo / down
+        // (N = D, few row blocks) want 32-row chunk blocks.
         if (M == 32) return f(PgCfg<32, 2, 4, 2>{});
         if (role == 2) return M == 256 ? f(PgCfg<32, 4, 4, 2>{}) : f(PgCfg<32, 2, 4, 2>{});
         if (role == 1) return M == 128 ? f(PgCfg<128, 4, 2, 2>{}) : f(PgCfg<64, 4, 3, 2>{});

@@ -38,17 +38,11 @@ static int pf_gemm_launch(const void* w, const void* ws, const void* hi, const v
     SLI_HIP((pg_allow_lds_all<Epi, WT>()));
     return pg_pick<WT>(M, role, [&](auto cfg) -> int {
         using Cfg = decltype(cfg);
-        if constexpr (is_mx<WT>::value) {  // ws: the e8m0 block scales
-            if (tiling)
-                *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeoMx<Cfg>::KS};
-            const PgInMx in{(const uint8_t*)w, (const uint8_t*)ws, (const __half*)hi, (const __half*)lo, N, K, M};
-            SLI_HIP((launch_pgemm_mx<Epi, Cfg>(in, e, ps, s)));
-        } else {
-            if (tiling)
-                *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeo<Cfg, WT>::KS};
-            const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M};
-            SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
-        }
+        if (tiling)
+            *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeo<Cfg, WT>::KS};
+        // ws: the e8m0 block scales (mxfp4), else null
+        const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M, (const uint8_t*)ws};
+        SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
         return SLI_OK;
     });
 }

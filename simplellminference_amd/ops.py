@@ -298,7 +298,7 @@ def prefill_gemm_qkv(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: 
     """One pgemm_kernel launch with the q/k/v epilogue: W [(hq + 2 hkv) hd, K]; q [M, hq hd] fp32 gets every chunk
     row; kc / vc, one layer's cache [hkv, T, hd] (f16, f32, or FP8 E4M3: a float8_e4m3fn tensor, or uint8 codes with
     kv_dtype="f8"), get rows p0 + m for m < nv, p0 + m < T. Returns the tiling that ran. scales (uint8 [N, K/32]): W is
-    MXFP4, uint8 [N, K/2] (pgemm_mx_kernel); no row_scale then."""
+    MXFP4, uint8 [N, K/2] (the kernel's MXFP4 format); no row_scale then."""
     if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
         raise ValueError("Tensor with Wrong Dim!")
     T = kc.shape[1]

@@ -1,4 +1,4 @@
-"""Inputs for the MXFP4 prefill GEMM tests (simplellminference_amd/csrc/prefill.h pgemm_mx_kernel): weights as
+"""Inputs for the MXFP4 prefill GEMM tests (simplellminference_amd/csrc/prefill.h pgemm_kernel, MXFP4 format): weights as
 4-bit codes and e8m0 block scales (tests/mxfp4_ref.py layout) whose sums with k/8 activations are exact in fp32 in
 any order, and the list of cases tests/test_gpu_mxfp4_prefill.py runs, so the CPU suite
 (test_mxfp4_prefill_ref_cpu.py) can check every one of them against the condition before a GPU sees it.

@@ -1,4 +1,4 @@
-"""Prompt prefill on MXFP4 weights: pgemm_mx_kernel (simplellminference_amd/csrc/prefill.h) one launch at a time
+"""Prompt prefill on MXFP4 weights: pgemm_kernel<…, mxfp4> (simplellminference_amd/csrc/prefill.h) one launch at a time
 through sli_prefill_gemm_mxfp4, against the float64 reference of tests/prefill_ref.py on W = the rule's
 dequantisation of the codes and scales (tests/mxfp4_ref.py), then the model path behind set_prefill("gemm") against an
 eager fp32 oracle whose matrices were overwritten with that dequantisation.
@@ -145,12 +145,13 @@ def _check_swiglu(fails, tag, got, Y, dY, silu):
     _hold(fails, tag, got, R.act(g, u, silu), R.act_tol(g, u, silu, dg, du))
 
 
-def _run_resid(torch, w, hi, lo, resid, pad=0, data=None, scales=None):
-    """y [M][N + pad], sentinel-filled: the columns past N stay untouched."""
+def _run_resid(torch, w, hi, lo, resid, pad=0, data=None, scales=None, acts=None):
+    """y [M][N + pad], sentinel-filled: the columns past N stay untouched. acts: device (hi, lo) to use instead."""
     from simplellminference_amd import ops
     M, N = hi.shape[0], w.N
     y = _sentinel(torch, (M, N + pad), False)
-    tl = ops.prefill_gemm_resid(w.data if data is None else data, _t(torch, hi), _t(torch, lo), y,
+    dhi, dlo = (_t(torch, hi), _t(torch, lo)) if acts is None else acts
+    tl = ops.prefill_gemm_resid(w.data if data is None else data, dhi, dlo, y,
                                 resid=_t(torch, resid), scales=w.scales if scales is None else scales)
     y = y.cpu().numpy()
     assert _is_sentinel(y[:, N:]).all(), "columns past N were written"
@@ -224,8 +225,8 @@ def test_block_scales_far_outside_fp16(gpu):
 @pytest.mark.parametrize("K", [64, 192, 704])
 def test_reads_stay_inside_data_and_scales(gpu, K):
     """data and scales are views into larger buffers filled with 0xFF (scale byte 255, elements -6) in front and
-    behind: a DMA piece of a short last stage that ran past a row's end, multiplied in, would change the sums. The
-    scales view starts at an odd byte."""
+    behind, the hi / lo activations views into buffers filled with NaN: a DMA piece of a short last stage that ran
+    past a row's end, multiplied in, would change the sums. The scales view starts at an odd byte."""
     torch = gpu
     N, M = G.N_RESID, 32
     codes, scales, hi, lo = G.grid_inputs(N, K, M, 500 + K)
@@ -237,11 +238,18 @@ def test_reads_stay_inside_data_and_scales(gpu, K):
     sv = big_s[4099:4099 + N * K // 32].view(N, K // 32)
     dv.copy_(w.data)
     sv.copy_(w.scales)
-    y, _ = _run_resid(torch, w, hi, lo, None, data=dv, scales=sv)
+    big_a = [torch.full((4096 + M * K + 4096,), float("nan"), dtype=torch.float16, device="cuda") for _ in range(2)]
+    av = [b[4096:4096 + M * K].view(M, K) for b in big_a]
+    av[0].copy_(_t(torch, hi))
+    av[1].copy_(_t(torch, lo))
+    y, _ = _run_resid(torch, w, hi, lo, None, data=dv, scales=sv, acts=av)
     fails = []
     _hold(fails, f"K {K} views", y, Y, 0.0)
     assert not fails, "\n".join(fails)
     assert bool((big_d[:4096] == 0xFF).all()) and bool((big_s[:4099] == 0xFF).all())
+    assert bool((big_d[-4096:] == 0xFF).all()) and bool((big_s[-4096:] == 0xFF).all())
+    for b in big_a:
+        assert bool(b[:4096].isnan().all()) and bool(b[-4096:].isnan().all())
 
 
 # ---------------------------------------------------------------- 4. realistic values

@@ -260,6 +260,42 @@ def test_picker_table_has_a_split_ring_cell(gpu, tables):
         assert 1024 // 64 > 2 * t["SA"], (c, t)  # the deepest case of the test above wraps this ring more than once
 
 
+@pytest.mark.parametrize("K", [64, 192, 704])
+@pytest.mark.parametrize("w", ["f16", "i8"])
+def test_reads_stay_inside_weights_scales_and_activations(gpu, w, K):
+    """The weights, the int8 row scales and the hi / lo activations are views into larger buffers filled in front and
+    behind with a value that changes any sum it enters (NaN; int8: 127): a DMA piece that ran past a row's end,
+    multiplied in, would show. The depths are 64 mod 128, so int8 ends in a half stage whose pieces step back (1, 3
+    and 11 fp16 stages). Exact grid sums, and the guard regions stay as they were."""
+    torch = gpu
+    from simplellminference_amd import ops
+    N, M, guard = N_RESID, 32, 4096
+    W, scale, hi, lo = R.grid_inputs(N, K, M, w == "i8", 700 + K)
+    Y = R.epi_resid(R.gemm_sums(W, hi, lo), scale, None)
+    bufs = []
+
+    def view(a):
+        if a is None:
+            return None
+        t = _t(torch, a)
+        big = torch.full((guard + t.numel() + guard,), 127 if t.dtype == torch.int8 else float("nan"), dtype=t.dtype,
+                         device="cuda")
+        v = big[guard:guard + t.numel()].view(t.shape)
+        v.copy_(t)
+        bufs.append(big)
+        return v
+
+    y = _sentinel(torch, (M, N), False)
+    ops.prefill_gemm_resid(view(W), view(hi), view(lo), y, resid=None, row_scale=view(scale))
+    fails = []
+    _hold(fails, f"{w} K {K} views", y.cpu().numpy(), Y, 0.0)
+    assert not fails, "\n".join(fails)
+    assert len(bufs) == (4 if w == "i8" else 3)
+    for big in bufs:
+        for g in (big[:guard], big[-guard:]):
+            assert bool(((g == 127) if big.dtype == torch.int8 else g.isnan()).all())
+
+
 # ---------------------------------------------------------------- (b) padding and bounds of the cache stores
 def _bounds_cases(M):
     return [(0, M - 27, M + 8), (256, M, 256 + M + 8), (256, M - 20, 256 + M - 20), (256, M, 256 + M - 20)]

@@ -7,7 +7,7 @@ bytes per row).
     python tools/mxfp4_time.py [--rounds 3] [--iters 20] [--layers 32] [--ctx 2048]
 
 --prefill: the prompt prefill instead. One process, a 512-token prompt, three configurations timed in interleaved
-rounds: the MXFP4 model after set_prefill("gemm") (pgemm_mx_kernel), the same model on the decode step
+rounds: the MXFP4 model after set_prefill("gemm") (pgemm_kernel<…, mxfp4>), the same model on the decode step
 (set_prefill("decode"), one weight pass per prompt token) and the int8 model's GEMM prefill. A time is the host clock
 around sli_model_prefill, which ends in a stream synchronise; every configuration is warmed up once first (graph
 capture, code objects), the GEMM legs repeat --reps times per round so a window is a fraction of a second at least.
