@@ -126,6 +126,17 @@ size_t sli_matmul_batch_i8_workspace_bytes(int32_t rows, int32_t cols, int32_t b
 int sli_matmul_batch_i8(const float* x, const void* w, const float* w_row_scale, float* y, int32_t rows, int32_t cols,
                         int32_t batch, int32_t tiled, void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
+/* The same projection from MXFP4 weights (data uint8 [rows][cols / 2] and e8m0 scales uint8 [rows][cols / 32] in the
+ * public layout above): y[b][r] = sum_c x[b][c] * code(W[r][c]) * 2^(scale[r][c / 32] - 127). The codes become the
+ * MFMA's fp16 A operand exactly and unscaled; each 32-column block's MFMA tile is multiplied by the block's scale in
+ * fp32 (the float whose exponent field is the scale byte; byte 0 is the subnormal 2^-127), so no block exponent
+ * overflows or flushes an fp16. tiled = 0 streams data and scales as given; tiled = 1 first re-lays both into the
+ * model's fragment-layout images inside the workspace and streams those. Checks and statuses as sli_matmul_batch_i8.
+ * A plain-rows form of sli_batch_gemm_mxfp4's store role, compiled beside it. */
+size_t sli_matmul_batch_mxfp4_workspace_bytes(int32_t rows, int32_t cols, int32_t batch, int32_t tiled);
+int sli_matmul_batch_mxfp4(const float* x, const void* data, const void* scales, float* y, int32_t rows, int32_t cols,
+                           int32_t batch, int32_t tiled, void* workspace, size_t workspace_bytes, sli_stream_t stream);
+
 /* kernel::rmsnorm_kernel_cuda (rms_kernel.cuh:6-7; CPU rms_kernel.cpp:5-23): y = x / sqrt(mean(x^2)+eps) * w.
  * Single-workgroup reduction: no atomics, no per-call allocation (the reference allocates + memsets a
  * {1} tensor per call and races across blocks, rms_kernel.cu:29-33,48-51). */
@@ -187,19 +198,20 @@ typedef struct {
     int32_t vocab, dim, n_heads, n_kv_heads, head_dim, ffn, n_layers, max_len;
     float eps, theta;
     int32_t w_dtype;  /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_I8 (per-row symmetric; any batch) / SLI_DT_MXFP4 (fp32 weights handed to
-                         the model are quantised by the rule at sli_quant_mxfp4; batch 1 only, the launch graph only,
-                         no GEMM prefill; dim, the local ffn width and the local q width multiples of 32, else
+                         the model are quantised by the rule at sli_quant_mxfp4; batch 1, or batch <= 8 for a model
+                         created with SLI_CREATE_MX_BATCH; the launch graph only; dim, the local ffn width and the local q width multiples of 32, else
                          SLI_ERR_SHAPE) */
     int32_t kv_dtype; /* SLI_DT_F32 / SLI_DT_F16 / SLI_DT_F8E4M3 (one byte per element, the rule at sli_quant_f8; with
-                         fp16 and int8 weights at any batch, MXFP4 at batch 1, not fp32 weights: SLI_ERR_ARG; the launch
+                         fp16 and int8 weights at any batch, MXFP4 at batch 1 or batch <= 8 under SLI_CREATE_MX_BATCH, not fp32 weights: SLI_ERR_ARG; the launch
                          graph only; prompts through the decode step, or through the GEMM prefill after
                          sli_model_set_prefill(SLI_PREFILL_GEMM_KV8); sli_model_get_kv returns the decoded fp32) */
     int32_t act_mode; /* 0: reference sigmoid(gate)*up (swiglu_kernel.cpp:12-13); 1: SiLU(gate)*up */
     int32_t tp_rank, tp_size;
     int32_t device;
     int32_t batch;    /* sequences decoding in lockstep, <= 8 (0 or 1: batch 1, the reference's case).
-                         batch > 1 runs the projections on MFMA (sli_matmul_batch, sli_matmul_batch_i8) and needs
-                         fp16 or int8 weights */
+                         batch > 1 runs the projections on MFMA (sli_matmul_batch, sli_matmul_batch_i8,
+                         sli_matmul_batch_mxfp4) and needs fp16 or int8 weights, or MXFP4 weights and
+                         SLI_CREATE_MX_BATCH (sli_model_create_flags) */
 } sli_model_config;
 
 typedef struct sli_model sli_model;
@@ -240,6 +252,14 @@ int sli_comm_id_bytes(void);
 int sli_comm_get_id(void* out);
 
 int sli_model_create(const sli_model_config* cfg, const void* comm_id, sli_model** out);
+/* sli_model_create with creation flags; flags = 0 is sli_model_create exactly. An unknown bit is SLI_ERR_ARG, decided
+ * before the device is touched.
+ * SLI_CREATE_MX_BATCH: an SLI_DT_MXFP4 model may have batch > 1 (<= 8): its projections run on MFMA from FP4 tiles
+ * (bgemm.h), with every cache type. Without the flag that combination is refused as before. It has no effect on
+ * fp32, fp16 and int8 models (fp32 weights at batch > 1 stay refused). The limits of every batched model hold: the
+ * launch graph only, prompts through the decode step, dim <= 4096, projection inputs multiples of 32. */
+enum { SLI_CREATE_MX_BATCH = 1 };
+int sli_model_create_flags(const sli_model_config* cfg, const void* comm_id, uint32_t flags, sli_model** out);
 int sli_model_destroy(sli_model* m);
 /* Seeded synthetic weights (include/sli_synth.h), generated on device in this rank's shard. */
 int sli_model_init_synthetic(sli_model* m, uint32_t seed);
@@ -353,6 +373,8 @@ int sli_model_step_bytes(sli_model* m, double* weight_bytes, double* kv_bytes);
  * read logits through them; step and destroy only through the group. */
 typedef struct sli_tp_group sli_tp_group;
 int sli_tp_group_create(const sli_model_config* cfg, int32_t tp_size, sli_tp_group** out);
+/* The same with the creation flags of sli_model_create_flags, applied to every rank; flags = 0 is sli_tp_group_create. */
+int sli_tp_group_create_flags(const sli_model_config* cfg, int32_t tp_size, uint32_t flags, sli_tp_group** out);
 int sli_tp_group_destroy(sli_tp_group* g);
 int sli_tp_group_rank(sli_tp_group* g, int32_t rank, sli_model** out);
 int sli_tp_group_step(sli_tp_group* g);
@@ -557,6 +579,19 @@ size_t sli_batch_gemm_workspace_bytes(int32_t rows, int32_t K, int32_t B, int32_
 int sli_batch_gemm(const float* x, const float* norm_w, float eps, const void* w, int w_dtype, const float* w_row_scale,
                    int32_t tiled, int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan,
                    void* workspace, size_t workspace_bytes, sli_stream_t stream);
+
+/* sli_batch_gemm from MXFP4 weights: `data` uint8 [rows][K / 2] and `scales` uint8 [rows][K / 32] in the public
+ * layout (sli_quant_mxfp4). The contract is sli_batch_gemm's word for word: the roles and their norm pairing, forced
+ * plans and the refusals of plans the kernel cannot take, *plan filled with what ran, the counters left zero,
+ * everything refused as SLI_ERR_ARG before the device is touched. There is no row scale: each 32-column block's
+ * MFMA tile is multiplied by its block scale in fp32 before it joins the row sum. tiled != 0: the call first builds
+ * the fragment-layout data image and the scale image (16 bytes per tile and k-block: the scales of the tile's rows in
+ * the epilogue's row order) inside the workspace and streams those, as a batched MXFP4 model does. */
+size_t sli_batch_gemm_mxfp4_workspace_bytes(int32_t rows, int32_t K, int32_t B, int32_t norm, int32_t tiled,
+                                            sli_bgemm_plan* plan);
+int sli_batch_gemm_mxfp4(const float* x, const float* norm_w, float eps, const void* data, const void* scales,
+                         int32_t tiled, int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan,
+                         void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ STATUS = {0: "ok", 1: "invalid argument", 2: "shape mismatch", 3: "index out of 
           5: "out of device memory", 6: "RCCL error", 7: "invalid state", 8: "communicator wait timed out"}
 SLI_ERR_COMM, SLI_ERR_TIMEOUT = 6, 8
 DT_F32, DT_F16, DT_I8, DT_MXFP4, DT_F8E4M3 = 0, 1, 2, 3, 4
+CREATE_MX_BATCH = 1  # sli_model_create_flags / sli_tp_group_create_flags: SLI_CREATE_MX_BATCH
 
 c_int, c_i32, c_u32, c_i64, c_f, c_d, c_vp, c_sz = (ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
                                                     ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t)
@@ -93,6 +94,8 @@ _SIGS = {
     "sli_matmul_batch": (c_int, [c_vp, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "sli_matmul_batch_i8_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "sli_matmul_batch_i8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "sli_matmul_batch_mxfp4_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "sli_matmul_batch_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "sli_rmsnorm": (c_int, [c_vp, c_vp, c_vp, c_i32, c_f, c_vp]),
     "sli_rope_cache": (c_int, [c_i32, c_i32, c_vp, c_vp, c_f, c_vp]),
     "sli_rope": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
@@ -112,6 +115,7 @@ _SIGS = {
     "sli_comm_id_bytes": (c_int, []),
     "sli_comm_get_id": (c_int, [c_vp]),
     "sli_model_create": (c_int, [ctypes.POINTER(ModelConfig), c_vp, ctypes.POINTER(c_vp)]),
+    "sli_model_create_flags": (c_int, [ctypes.POINTER(ModelConfig), c_vp, c_u32, ctypes.POINTER(c_vp)]),
     "sli_model_destroy": (c_int, [c_vp]),
     "sli_model_init_synthetic": (c_int, [c_vp, c_u32]),
     "sli_model_set_weight": (c_int, [c_vp, c_i32, c_i32, c_vp, c_i64]),
@@ -163,6 +167,10 @@ _SIGS = {
     "sli_batch_gemm": (c_int, [c_vp, c_vp, c_f, c_vp, c_int, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
                                ctypes.POINTER(BgemmPlan), c_vp, c_sz, c_vp]),
     "sli_tp_group_create": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(c_vp)]),
+    "sli_tp_group_create_flags": (c_int, [ctypes.POINTER(ModelConfig), c_i32, c_u32, ctypes.POINTER(c_vp)]),
+    "sli_batch_gemm_mxfp4_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmPlan)]),
+    "sli_batch_gemm_mxfp4": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
+                                     ctypes.POINTER(BgemmPlan), c_vp, c_sz, c_vp]),
     "sli_tp_group_destroy": (c_int, [c_vp]),
     "sli_tp_group_rank": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
     "sli_tp_group_step": (c_int, [c_vp]),
@@ -184,6 +192,8 @@ def load() -> ctypes.CDLL:
                               "(no CPU fallback exists for the decode path)")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in _SIGS.items():
+            if os.environ.get("SLI_LIB_VARIANT") and not hasattr(L, name):
+                continue  # an A/B build of an older tree lacks the newer entries; libsli.so itself must have all
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
@@ -207,6 +217,8 @@ def call(name: str, *args) -> int:
                                                  "sli_model_comm_handle_bytes",
                                                  "sli_matmul_batch_workspace_bytes",
                                                  "sli_matmul_batch_i8_workspace_bytes",
-                                                 "sli_batch_gemm_workspace_bytes"):
+                                                 "sli_batch_gemm_workspace_bytes",
+                                                 "sli_matmul_batch_mxfp4_workspace_bytes",
+                                                 "sli_batch_gemm_mxfp4_workspace_bytes"):
         check(rc, name)
     return rc

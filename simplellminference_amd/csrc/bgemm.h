@@ -31,11 +31,25 @@
 // clamped duplicate loads, the plan table), so every K % 32 == 0 and every per-wave block count the fp16
 // kernel takes works unchanged, with nothing read past the matrix. The weight type is a template parameter;
 // the fp16 instantiations have no int8 code in them.
+//
+// MXFP4 weights (WT = mxfp4; mxfp4.h: e2m1 codes, one e8m0 scale per 32 columns): one MFMA k-block is exactly one
+// MX block, so a (weight row, k-block) pair has one scale. A lane's 8 weights of a 16x32 block are 4 bytes (one
+// 4-byte load per lane and block, a quarter of the fp16 path's bytes), decoded to the fp16 A fragment exactly and
+// UNSCALED (mxfp4.h pg_fp4_to_f16, the prefill GEMM's decoder). The scale never touches the fp16 operand: the
+// kBgU MFMAs of a step run into zeroed tiles of their own, then acc[r] = fma(tile[r], 2^e[r], acc[r]) in fp32 for
+// the lane's four C rows 4 (l >> 4) + r, so no block exponent can overflow or flush an fp16. Both activation
+// columns (hi: b, lo: 8 + b) take the same row scale, so the lane + 8 fold at the end of a tile stays where it is.
+// The scale bytes are loaded beside the data, one byte per lane and block: lane l loads the scale of tile row
+// 4 (l >> 4) + (l & 3), and the four lanes of a quad hand each other the four C rows' scales as DPP quad
+// broadcasts (VALU operand modifiers, no LDS). Every scale load is unconditional and clamped exactly like the data
+// load of the same block, so the loads stay straight-line and nothing is read past either array. The fp16 and
+// int8 instantiations have no MXFP4 code in them (if constexpr); the epilogues' rscale stays null.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
 #include "lds_mfma.h"
+#include "mxfp4.h"
 
 namespace sli {
 
@@ -89,7 +103,13 @@ struct BgIn {
     // of four 128-B lines (row-major: 16 rows x 32 B, 16 quarter lines), and a wave's consecutive blocks are
     // consecutive in memory, so the loads of one step cover one run of kBgU * 512 B. (Pairing two k-blocks into
     // 16-byte lane loads would tie the image to the plan: a wave's first block is odd or even with the split.)
+    // mxfp4: two images. Data: block kb of tile t is 256 B at ((t * K/32) + kb) * 256, lane l's 4 bytes (the codes of
+    // W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7]) at l * 4: one wave load is two full 128-B lines. Scales: 16 B per
+    // (tile, k-block) at ((t * K/32) + kb) * 16, byte i the e8m0 scale of row(t, i) (a clamped row carries its real
+    // row's scale); lane l loads byte 4 (l >> 4) + (l & 3). A wave's consecutive blocks are consecutive in both
+    // images. tiled = 0: data [rows][K/2] and scales [rows][K/32] in the public layout of sli.h.
     int tiled = 0;
+    const uint8_t* wscale = nullptr;  // mxfp4 only: the e8m0 block scales, in the layout `tiled` names
 };
 
 // ---------------------------------------------------------------- host-side plan
@@ -169,6 +189,23 @@ __device__ __forceinline__ void bg_split8(const float* y, u32x4& hi, u32x4& lo) 
     lo = u32x4{l[0], l[1], l[2], l[3]};
 }
 
+// bytes of a lane's 8 weights of one 16x32 block: 16 (fp16), 8 (int8), 4 (mxfp4)
+template <typename WT>
+__host__ __device__ constexpr size_t bg_lane_bytes() {
+    return is_mx<WT>::value ? 4 : 8 * sizeof(WT);
+}
+
+// mxfp4: the fp32 scale of C row r of a lane from the quad's scale bytes (QP: quad_perm [r, r, r, r]). The scale is the
+// float whose exponent field is the e8m0 byte: bytes 1 .. 254 are the normal numbers 2^-126 .. 2^127. Byte 0 is
+// 2^-127, an fp32 subnormal (word 0x00400000), not the zero that byte << 23 would give: the unsigned max supplies
+// it (fp32 denormals are kept, so the product is the exact one whenever it is representable). Byte 255 (the
+// format's NaN) becomes an infinity, and the row sum a NaN or an infinity.
+template <int QP>
+__device__ __forceinline__ float bg_mx_scale(unsigned sbyte) {
+    const unsigned b = (unsigned)__builtin_amdgcn_mov_dpp((int)sbyte, QP, 0xF, 0xF, true);
+    return __uint_as_float(max(b << 23, 0x00400000u));
+}
+
 // Epilogue contract (a mutable copy per thread):
 //   row(t, i)                   weight row of tile t's row i (i < 16), always a valid row (clamped)
 //   store(t, i, b, v0, v1, kl)  final sums of tile rows i (< 8) and i + 8 for sequence b; kl = the
@@ -181,10 +218,12 @@ __device__ __forceinline__ void bg_split8(const float* y, u32x4& hi, u32x4& lo) 
 //                               costing a round trip after it
 template <class Epi, bool NORM, int kBgU = 4, typename WT = __half>
 __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict__ W, BgIn in, Epi epi_in) {
-    static_assert(std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value, "fp16 or int8 weights");
+    static_assert(std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value || is_mx<WT>::value,
+                  "fp16, int8 or mxfp4 weights");
     constexpr bool I8 = std::is_same<WT, int8_t>::value;
-    constexpr size_t ES = sizeof(WT);  // a lane's A operand of one k-block: 8 elements = 8 * ES bytes
-    using WV = typename std::conditional<I8, u32x2, u32x4>::type;
+    constexpr bool MX = is_mx<WT>::value;
+    constexpr size_t ES = sizeof(WT);  // fp16, int8: a lane's A operand of one k-block: 8 elements = 8 * ES bytes
+    using WV = typename std::conditional<MX, unsigned, typename std::conditional<I8, u32x2, u32x4>::type>::type;
     Epi epi = epi_in;
     extern __shared__ __attribute__((aligned(16))) char bg_smem[];
     float* red = reinterpret_cast<float*>(bg_smem);  // [16][8]
@@ -261,28 +300,55 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
     const size_t row_bytes = (size_t)K * ES;
     const int q8 = (lane >> 4) * 8;  // this lane's k offset inside a 32-k block
     const size_t bstride = in.tiled ? 512 * ES : 32 * ES;  // bytes between a lane's consecutive k-blocks
-    auto load_step = [&](int k, WV(&w)[kBgU]) {
+    // mxfp4: the tile row whose scale this lane loads (its quad holds the scales of the lane's four C rows)
+    const int srow = (lane >> 4) * 4 + (lane & 3);
+    auto load_step = [&](int k, WV(&w)[kBgU], unsigned(&ws)[MX ? kBgU : 1]) {
         const int kk = min(k, nsteps - 1);
         const int j = kk / cpt, c = kk - j * cpt;
-        const char* base;
-        if (in.tiled) {
-            base = reinterpret_cast<const char*>(W) + (size_t)(t0 + j) * nkb * (512 * ES) + (size_t)lane * (8 * ES);
-        } else {
-            const int row = epi.row(t0 + j, lane & 15);
-            base = reinterpret_cast<const char*>(W) + (size_t)row * row_bytes + (size_t)q8 * ES;
-        }
+        if constexpr (MX) {
+            // 4 data bytes and 1 scale byte per lane and block. 32-bit block offsets (at most 256 B x K / 32 blocks),
+            // and a block's scale offset is its data offset / 16 in both layouts (256 and 16 bytes per block tiled,
+            // 16 and 1 row-major): that keeps the widest epilogue within the scalar registers (no scratch).
+            const unsigned mstride = in.tiled ? 256u : 16u;
+            const char* base;
+            const uint8_t* sbase;
+            if (in.tiled) {
+                base = reinterpret_cast<const char*>(W) + (size_t)(t0 + j) * nkb * 256 + (size_t)lane * 4;
+                sbase = in.wscale + (size_t)(t0 + j) * nkb * 16 + srow;
+            } else {
+                base = reinterpret_cast<const char*>(W) + (size_t)epi.row(t0 + j, lane & 15) * (size_t)(K >> 1) +
+                       (size_t)(lane >> 4) * 4;
+                sbase = in.wscale + (size_t)epi.row(t0 + j, srow) * nkb;
+            }
 #pragma unroll
-        for (int u = 0; u < kBgU; ++u) {
-            const int bi = wb0 + min(c * kBgU + u, max(wnb - 1, 0));
-            if constexpr (I8)
-                w[u] = load8<true>(base + (size_t)bi * bstride);
-            else
-                w[u] = load16<true>(base + (size_t)bi * bstride);
+            for (int u = 0; u < kBgU; ++u) {
+                const int bi = wb0 + min(c * kBgU + u, max(wnb - 1, 0));
+                const unsigned off = (unsigned)bi * mstride;
+                w[u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(base + off));
+                ws[u] = __builtin_nontemporal_load(sbase + (off >> 4));
+            }
+        } else {
+            const char* base;
+            if (in.tiled) {
+                base = reinterpret_cast<const char*>(W) + (size_t)(t0 + j) * nkb * (512 * ES) + (size_t)lane * (8 * ES);
+            } else {
+                const int row = epi.row(t0 + j, lane & 15);
+                base = reinterpret_cast<const char*>(W) + (size_t)row * row_bytes + (size_t)q8 * ES;
+            }
+#pragma unroll
+            for (int u = 0; u < kBgU; ++u) {
+                const int bi = wb0 + min(c * kBgU + u, max(wnb - 1, 0));
+                if constexpr (I8)
+                    w[u] = load8<true>(base + (size_t)bi * bstride);
+                else
+                    w[u] = load16<true>(base + (size_t)bi * bstride);
+            }
         }
     };
     WV wa[kBgU], wb[kBgU];  // (a third step in flight measured slower: C4 1660 -> 1546 tok/s)
-    load_step(0, wa);
-    load_step(1, wb);
+    unsigned sa[MX ? kBgU : 1], sb_[MX ? kBgU : 1];  // mxfp4: the steps' scale bytes
+    load_step(0, wa, sa);
+    load_step(1, wb, sb_);
     __builtin_amdgcn_sched_barrier(0);
     epi.pre_b();
 
@@ -322,15 +388,34 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
     // ---- 5. stream the tiles
     lm_float4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const u32x4* wimg = img + (size_t)(wb0 - kb0) * 64 + lane;
-    auto mfma_step = [&](int k, const WV(&w)[kBgU]) {
+    auto mfma_step = [&](int k, const WV(&w)[kBgU], const unsigned(&ws)[MX ? kBgU : 1]) {
         const int c = k - (k / cpt) * cpt;
+        if constexpr (MX) {
+            // the step's MFMAs into zeroed tiles of their own, then the scaled adds (no MFMA waits on an FMA)
+            lm_float4 tile[kBgU];
 #pragma unroll
-        for (int u = 0; u < kBgU; ++u) {
-            const int r = c * kBgU + u;
-            if constexpr (I8) {
-                if (r < wnb) acc = lm_mfma(i8x8_to_f16(w[u].x, w[u].y), wimg[(size_t)r * 64], acc);
-            } else {
-                if (r < wnb) acc = lm_mfma(w[u], wimg[(size_t)r * 64], acc);
+            for (int u = 0; u < kBgU; ++u) {
+                tile[u] = lm_float4{0.0f, 0.0f, 0.0f, 0.0f};
+                if (c * kBgU + u < wnb) tile[u] = lm_mfma(pg_fp4_to_f16(w[u]), wimg[(size_t)(c * kBgU + u) * 64], tile[u]);
+            }
+#pragma unroll
+            // (unconditional: a block past the wave's range left its tile zero, and its clamped duplicate's scale
+            // is that of a real block of the same rows, so it adds +0 to a sum that is never -0)
+            for (int u = 0; u < kBgU; ++u) {
+                acc[0] = fmaf(tile[u][0], bg_mx_scale<0x00>(ws[u]), acc[0]);
+                acc[1] = fmaf(tile[u][1], bg_mx_scale<0x55>(ws[u]), acc[1]);
+                acc[2] = fmaf(tile[u][2], bg_mx_scale<0xAA>(ws[u]), acc[2]);
+                acc[3] = fmaf(tile[u][3], bg_mx_scale<0xFF>(ws[u]), acc[3]);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < kBgU; ++u) {
+                const int r = c * kBgU + u;
+                if constexpr (I8) {
+                    if (r < wnb) acc = lm_mfma(i8x8_to_f16(w[u].x, w[u].y), wimg[(size_t)r * 64], acc);
+                } else {
+                    if (r < wnb) acc = lm_mfma(w[u], wimg[(size_t)r * 64], acc);
+                }
             }
         }
     };
@@ -363,19 +448,19 @@ __global__ void __launch_bounds__(kBgThreads) bgemm_kernel(const WT* __restrict_
     // The next step's loads go out as soon as the current step's MFMAs have read their registers, BEFORE
     // the tile-end workgroup barrier: two steps stay in flight through every tile boundary.
     for (; k + 2 < nsteps; k += 2) {
-        mfma_step(k, wa);
-        load_step(k + 2, wa);
+        mfma_step(k, wa, sa);
+        load_step(k + 2, wa, sa);
         tile_end(k);
-        mfma_step(k + 1, wb);
-        load_step(k + 3, wb);
+        mfma_step(k + 1, wb, sb_);
+        load_step(k + 3, wb, sb_);
         tile_end(k + 1);
     }
     if (k < nsteps) {
-        mfma_step(k, wa);
+        mfma_step(k, wa, sa);
         tile_end(k);
     }
     if (k + 1 < nsteps) {
-        mfma_step(k + 1, wb);
+        mfma_step(k + 1, wb, sb_);
         tile_end(k + 1);
     }
     __syncthreads();
@@ -589,13 +674,14 @@ struct BgEpiLogits {
 
 // Row-major W [rows][K] -> the fragment layout of BgIn::tiled, rows in the epilogue's tile order (Epi::row:
 // RoPE pairs, gate/up pairs, the last tile's clamped rows): out[(t * K/32 + kb) * 64 + l] (16-byte pieces) =
-// W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7]; int8: the same pieces at 8 bytes each (BgIn::tiled). Init-time
-// only (weights placed or replaced).
+// W[row(t, l & 15)][32 kb + 8 (l >> 4) .. + 7]; int8: the same pieces at 8 bytes each, mxfp4: at 4 bytes each
+// (BgIn::tiled). Init-time only (weights placed or replaced).
 template <class Epi, typename WT>
 __global__ void __launch_bounds__(256) bg_tile_kernel(const WT* __restrict__ W, int K, int ntiles, Epi epi,
                                                        void* __restrict__ out_) {
-    using PV = typename std::conditional<sizeof(WT) == 1, uint2, uint4>::type;  // a lane's 8 weights
-    PV* out = reinterpret_cast<PV*>(out_);
+    constexpr size_t LB = bg_lane_bytes<WT>();
+    using PV = typename std::conditional<LB == 4, unsigned, typename std::conditional<LB == 8, uint2, uint4>::type>::type;
+    PV* out = reinterpret_cast<PV*>(out_);  // a lane's 8 weights
     const int nkb = K / 32;
     const size_t n = (size_t)ntiles * nkb * 64;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
@@ -603,22 +689,47 @@ __global__ void __launch_bounds__(256) bg_tile_kernel(const WT* __restrict__ W, 
         const size_t tb = p >> 6;
         const int t = (int)(tb / nkb), kb = (int)(tb - (size_t)t * nkb);
         const int row = epi.row(t, l & 15);
-        out[p] = *reinterpret_cast<const PV*>(W + (size_t)row * K + (size_t)kb * 32 + 8 * (l >> 4));
+        out[p] = *reinterpret_cast<const PV*>(reinterpret_cast<const char*>(W) +
+                                              ((size_t)row * nkb + (size_t)kb) * (4 * LB) + LB * (l >> 4));
+    }
+}
+// mxfp4: the scale image of BgIn::tiled, out[(t * K/32 + kb) * 16 + i] = scales[row(t, i)][kb]
+template <class Epi>
+__global__ void __launch_bounds__(256) bg_tile_scales_kernel(const uint8_t* __restrict__ scales, int K, int ntiles, Epi epi,
+                                                              uint8_t* __restrict__ out) {
+    const int nkb = K / 32;
+    const size_t n = (size_t)ntiles * nkb * 16;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
+        const int i = (int)(p & 15);
+        const size_t tb = p >> 4;
+        const int t = (int)(tb / nkb), kb = (int)(tb - (size_t)t * nkb);
+        out[p] = scales[(size_t)epi.row(t, i) * nkb + kb];
     }
 }
 
+// mxfp4: `scales` (public layout) and `sout` (the scale image) are laid out beside the data
 template <class Epi, typename WT>
-hipError_t launch_bg_tile(const WT* W, int K, int ntiles, const Epi& epi, void* out, hipStream_t s) {
+hipError_t launch_bg_tile(const WT* W, int K, int ntiles, const Epi& epi, void* out, hipStream_t s,
+                          const uint8_t* scales = nullptr, void* sout = nullptr) {
     if (K % 32) return hipErrorInvalidValue;
     const size_t n = (size_t)ntiles * (K / 32) * 64;
     const int blocks = (int)std::min<size_t>(8192, (n + 255) / 256);
     hipLaunchKernelGGL((bg_tile_kernel<Epi, WT>), dim3(blocks), dim3(256), 0, s, W, K, ntiles, epi, out);
+    if constexpr (is_mx<WT>::value) {
+        if (!scales || !sout) return hipErrorInvalidValue;
+        const int sblocks = (int)std::min<size_t>(8192, (n / 4 + 255) / 256);
+        hipLaunchKernelGGL((bg_tile_scales_kernel<Epi>), dim3(sblocks), dim3(256), 0, s, scales, K, ntiles, epi,
+                           (uint8_t*)sout);
+    }
     return hipGetLastError();
 }
 // bytes of a tiled matrix of `esize`-byte weights (2: fp16, 1: int8)
 inline size_t bg_tiled_bytes(int ntiles, int K, int esize = 2) {
     return (size_t)ntiles * (size_t)(K / 32) * 512 * (size_t)esize;
 }
+// mxfp4: bytes of the data image (256 per block) and of the scale image (16 per block) of a tiled matrix
+inline size_t bg_tiled_mx_bytes(int ntiles, int K) { return (size_t)ntiles * (size_t)(K / 32) * 256; }
+inline size_t bg_tiled_mx_scale_bytes(int ntiles, int K) { return (size_t)ntiles * (size_t)(K / 32) * 16; }
 
 // Allow the kernel its full dynamic LDS (once per instantiation; call outside stream capture).
 template <class Epi, bool NORM, typename WT = __half>
@@ -628,7 +739,7 @@ hipError_t bg_allow_lds() {
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
         const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 2, WT>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
-        if (!NORM) {
+        if constexpr (!NORM) {  // (no 7-wide NORM kernel is ever launched: bg_launch_width)
             const hipError_t e7 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bgemm_kernel<Epi, NORM, 7, WT>),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kBgLdsMax);
             if (e7 != hipSuccess) return e7;

@@ -53,6 +53,8 @@ struct LayerW {
     // batch > 1 (fp16 or int8): the same matrices in bgemm's fragment layout (bgemm.h BgIn::tiled), rows in each
     // epilogue's tile order; the decode step streams these, the row-major copies serve prefill-free readback
     void *qkv_t = nullptr, *wo_t = nullptr, *gu_t = nullptr, *down_t = nullptr;
+    // mxfp4 at batch > 1 (SLI_CREATE_MX_BATCH): the fragment-layout scale images beside the data images above
+    uint8_t *qkv_ts = nullptr, *wo_ts = nullptr, *gu_ts = nullptr, *down_ts = nullptr;
 };
 
 }  // namespace sli
@@ -74,6 +76,7 @@ struct sli_model {
     void* emb = nullptr;
     float* emb_s = nullptr;
     void* lm_t = nullptr;     // batch > 1: this rank's LM-head rows of emb in the fragment layout (LayerW::*_t)
+    uint8_t* lm_ts = nullptr; // mxfp4: their scale image (LayerW::*_ts)
     bool bg_tiled = false;    // the batched projections stream the fragment-layout copies
     bool tiles_dirty = false; // a weight was placed since the copies were last built (bg_sync_tiles)
     float* norms = nullptr;
@@ -373,6 +376,16 @@ __global__ void embedding_batch_kernel(const DevState* st, const T* __restrict__
     const float s = (ok && row_scale) ? row_scale[token] : 1.0f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dim; i += gridDim.x * blockDim.x)
         out[(size_t)b * dim + i] = ok ? to_f32(table[(size_t)token * dim + i]) * s : 0.0f;
+}
+
+// the same from the MXFP4 table: a table decode per element (mxfp4.h mx_element), not a hot path
+__global__ void embedding_batch_mx_kernel(const DevState* st, const uint8_t* __restrict__ data,
+                                          const uint8_t* __restrict__ scales, float* __restrict__ out, int vocab, int dim) {
+    const int b = blockIdx.y;
+    const int token = st[b].token;
+    const bool ok = token >= 0 && token < vocab;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dim; i += gridDim.x * blockDim.x)
+        out[(size_t)b * dim + i] = ok ? mx_element(data, scales, (size_t)token, dim, i) : 0.0f;
 }
 
 // second argmax stage per sequence: block b reduces keys[b][0 .. n) into out[b]
@@ -855,16 +868,24 @@ struct StepRecorder {
 
     // ---- batch > 1: the same step for B sequences, projections on MFMA (bgemm.h)
     static constexpr int kPosStride = (int)(sizeof(DevState) / sizeof(int32_t));
-    // weight types bgemm.h streams; int8: every epilogue gets the matrix's row scales (null for fp16)
-    static constexpr bool kBgWT = std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value;
+    // weight types bgemm.h streams; int8: every epilogue gets the matrix's row scales (null for fp16 and mxfp4);
+    // mxfp4: the launch gets the matrix's block scales (ws: the scale image when the model streams the fragment
+    // layout, else the *_s scales in the public layout)
+    static constexpr bool kBgWT = std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value || MX;
     template <class Epi>
-    static int bg(sli_model* m, const void* W, const BgIn& in, const Epi& e, const BgPlan& p) {
+    static int bg(sli_model* m, const void* W, const void* ws, const BgIn& in_, const Epi& e, const BgPlan& p) {
         if constexpr (kBgWT) {
+            BgIn in = in_;
+            if (MX) in.wscale = (const uint8_t*)ws;
             SLI_HIP(launch_bgemm((const WT*)W, in, e, p, m->stream));
             return SLI_OK;
         } else {
-            return fail(SLI_ERR_ARG, "batch > 1 needs fp16 or int8 weights");
+            return fail(SLI_ERR_ARG, "batch > 1 needs fp16, int8 or mxfp4 weights");
         }
+    }
+    // the scales a batched launch streams for a matrix: its scale image or its row-major block scales (mxfp4 only)
+    static const void* bsc(sli_model* m, const uint8_t* img, const float* rowmajor) {
+        return m->bg_tiled ? (const void*)img : (const void*)rowmajor;
     }
     template <class Epi, bool NORM>
     static int allow(sli_model*) {
@@ -897,7 +918,7 @@ struct StepRecorder {
         BgEpiQKV<KT> e{m->q, (KT*)m->kc + lay, (KT*)m->vc + lay, &m->st->pos, kPosStride, m->sin_t, m->cos_t,
                        m->hq, m->hkv, m->hd, m->T};
         e.rscale = rs(m->layers[l].qkv_s);
-        return bg(m, m->bg_tiled ? m->layers[l].qkv_t : m->layers[l].qkv, bin(m, m->x, m->norms + (size_t)(2 * l) * m->D, m->D), e, m->bp_qkv);
+        return bg(m, m->bg_tiled ? m->layers[l].qkv_t : m->layers[l].qkv, bsc(m, m->layers[l].qkv_ts, m->layers[l].qkv_s), bin(m, m->x, m->norms + (size_t)(2 * l) * m->D, m->D), e, m->bp_qkv);
     }
     // batched wo / down with the exchange per group (oneshot.h BgEpiPush; region 3: wo, 4: down)
     static BgEpiPush push_bg(sli_model* m, int region, const BgPlan& p, const float* rscale) {
@@ -926,25 +947,29 @@ struct StepRecorder {
     static int b_wo(sli_model* m, int l) {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].wo_t : m->layers[l].wo;
-        if (fused_ar(m)) return bg(m, w, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo, m->layers[l].wo_s), m->bp_wo);
+        const void* ws = bsc(m, m->layers[l].wo_ts, m->layers[l].wo_s);
+        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo, m->layers[l].wo_s), m->bp_wo);
         BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].wo_s), 1.0f, m->D, m->D};
-        return bg(m, w, bin(m, m->attn, nullptr, m->hq * m->hd), e, m->bp_wo);
+        return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), e, m->bp_wo);
     }
     static int b_gu(sli_model* m, int l) {
         BgEpiSwiGLU e{m->act, m->Il, m->c.act_mode, rs(m->layers[l].gu_s)};
-        return bg(m, m->bg_tiled ? m->layers[l].gu_t : m->layers[l].gu, bin(m, m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->D), e, m->bp_gu);
+        return bg(m, m->bg_tiled ? m->layers[l].gu_t : m->layers[l].gu, bsc(m, m->layers[l].gu_ts, m->layers[l].gu_s), bin(m, m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->D), e, m->bp_gu);
     }
     static int b_down(sli_model* m, int l) {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].down_t : m->layers[l].down;
-        if (fused_ar(m)) return bg(m, w, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down, m->layers[l].down_s), m->bp_down);
+        const void* ws = bsc(m, m->layers[l].down_ts, m->layers[l].down_s);
+        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down, m->layers[l].down_s), m->bp_down);
         BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].down_s), 1.0f, m->D, m->D};
-        return bg(m, w, bin(m, m->act, nullptr, m->Il), e, m->bp_down);
+        return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), e, m->bp_down);
     }
     static int b_lm(sli_model* m) {
         BgEpiLogits e{m->logits, m->keys, m->v_n, m->v_n, m->v_lo, m->key_ld, m->emb_s && !MX ? m->emb_s + m->v_lo : nullptr};
         const void* w = m->bg_tiled ? m->lm_t : wptr(m->emb, m->wbytes, (size_t)m->v_lo * m->D);
-        return bg(m, w, bin(m, m->x, m->norms + (size_t)(2 * m->L) * m->D, m->D), e, m->bp_lm);
+        // (mxfp4 row-major: the block scales of table row v_lo on; sptr)
+        const void* ws = bsc(m, m->lm_ts, sptr(m, m->emb_s, (size_t)m->v_lo, m->D));
+        return bg(m, w, ws, bin(m, m->x, m->norms + (size_t)(2 * m->L) * m->D, m->D), e, m->bp_lm);
     }
     // ---- one step = phases 0 .. 2L (model.cpp:48-139). Phase 2l: [embedding when l = 0,] qkv(l),
     // attention(l), wo(l); phase 2l+1: gate/up(l), down(l); phase 2L: LM head + first argmax stage.
@@ -956,10 +981,12 @@ struct StepRecorder {
         const bool batched = m->B > 1;
         if (p == 0) {
             if (batched) {
+                const int eb = std::min(64, (m->D + 255) / 256);
                 if constexpr (MX) {
-                    return fail(SLI_ERR_ARG, "batch > 1 needs fp16 or int8 weights");
+                    hipLaunchKernelGGL(embedding_batch_mx_kernel, dim3(eb, m->B), dim3(256), 0, s, m->st,
+                                       (const uint8_t*)m->emb, mx_scales(m->emb_s), m->x, m->V, m->D);
+                    SLI_HIP(hipGetLastError());
                 } else {
-                    const int eb = std::min(64, (m->D + 255) / 256);
                     hipLaunchKernelGGL(embedding_batch_kernel<WT>, dim3(eb, m->B), dim3(256), 0, s, m->st,
                                        (const WT*)m->emb, m->emb_s, m->x, m->V, m->D);
                     SLI_HIP(hipGetLastError());
@@ -1285,18 +1312,21 @@ static int bg_build_tiles(sli_model* m) {
     eg.inter = m->Il;
     BgEpiLogits el{};
     el.nrows = m->v_n;
+    // (mxfp4: the *_s pointers hold the block scales, laid out into the scale images beside the data; else unused)
     for (const LayerW& w : m->layers) {
-        SLI_HIP(launch_bg_tile((const WT*)w.qkv, D, m->bp_qkv.ntiles, eq, w.qkv_t, s));
-        SLI_HIP(launch_bg_tile((const WT*)w.wo, QD, m->bp_wo.ntiles, eo, w.wo_t, s));
-        SLI_HIP(launch_bg_tile((const WT*)w.gu, D, m->bp_gu.ntiles, eg, w.gu_t, s));
-        SLI_HIP(launch_bg_tile((const WT*)w.down, m->Il, m->bp_down.ntiles, eo, w.down_t, s));
+        SLI_HIP(launch_bg_tile((const WT*)w.qkv, D, m->bp_qkv.ntiles, eq, w.qkv_t, s, mx_scales(w.qkv_s), w.qkv_ts));
+        SLI_HIP(launch_bg_tile((const WT*)w.wo, QD, m->bp_wo.ntiles, eo, w.wo_t, s, mx_scales(w.wo_s), w.wo_ts));
+        SLI_HIP(launch_bg_tile((const WT*)w.gu, D, m->bp_gu.ntiles, eg, w.gu_t, s, mx_scales(w.gu_s), w.gu_ts));
+        SLI_HIP(launch_bg_tile((const WT*)w.down, m->Il, m->bp_down.ntiles, eo, w.down_t, s, mx_scales(w.down_s), w.down_ts));
     }
-    SLI_HIP(launch_bg_tile((const WT*)m->emb + (size_t)m->v_lo * D, D, m->bp_lm.ntiles, el, m->lm_t, s));
+    SLI_HIP(launch_bg_tile((const WT*)wptr(m->emb, m->wbytes, (size_t)m->v_lo * D), D, m->bp_lm.ntiles, el, m->lm_t, s,
+                           mx_scales(sptr(m, m->emb_s, (size_t)m->v_lo, D)), m->lm_ts));
     m->tiles_dirty = false;
     return SLI_OK;
 }
 static int bg_sync_tiles(sli_model* m) {
     if (!m->bg_tiled || !m->tiles_dirty) return SLI_OK;
+    if (m->c.w_dtype == SLI_DT_MXFP4) return bg_build_tiles<mxfp4>(m);
     return m->c.w_dtype == SLI_DT_I8 ? bg_build_tiles<int8_t>(m) : bg_build_tiles<__half>(m);
 }
 
@@ -1484,16 +1514,22 @@ static int wo_ksplit(const sli_model* m) {
 // correct, only slower. SLI_DEBUG_BG_ROWMAJOR=1 forces that fallback (tests).
 static void bg_alloc_tiles(sli_model* m) {
     m->bg_tiled = false;
-    if ((m->c.w_dtype != SLI_DT_F16 && m->c.w_dtype != SLI_DT_I8) || std::getenv("SLI_DEBUG_BG_ROWMAJOR")) return;
+    const bool mx = m->c.w_dtype == SLI_DT_MXFP4;
+    if ((m->c.w_dtype != SLI_DT_F16 && m->c.w_dtype != SLI_DT_I8 && !mx) || std::getenv("SLI_DEBUG_BG_ROWMAJOR")) return;
     const int D = m->D, QD = m->hq * m->hd, es = m->c.w_dtype == SLI_DT_I8 ? 1 : 2;
     std::vector<std::pair<void**, size_t>> want;
+    // a matrix's data image, and for mxfp4 its scale image (BgIn::tiled)
+    auto both = [&](void** t, uint8_t** ts, int ntiles, int K) {
+        want.push_back({t, mx ? bg_tiled_mx_bytes(ntiles, K) : bg_tiled_bytes(ntiles, K, es)});
+        if (mx) want.push_back({(void**)ts, bg_tiled_mx_scale_bytes(ntiles, K)});
+    };
     for (auto& w : m->layers) {
-        want.push_back({&w.qkv_t, bg_tiled_bytes(m->bp_qkv.ntiles, D, es)});
-        want.push_back({&w.wo_t, bg_tiled_bytes(m->bp_wo.ntiles, QD, es)});
-        want.push_back({&w.gu_t, bg_tiled_bytes(m->bp_gu.ntiles, D, es)});
-        want.push_back({&w.down_t, bg_tiled_bytes(m->bp_down.ntiles, m->Il, es)});
+        both(&w.qkv_t, &w.qkv_ts, m->bp_qkv.ntiles, D);
+        both(&w.wo_t, &w.wo_ts, m->bp_wo.ntiles, QD);
+        both(&w.gu_t, &w.gu_ts, m->bp_gu.ntiles, D);
+        both(&w.down_t, &w.down_ts, m->bp_down.ntiles, m->Il);
     }
-    want.push_back({&m->lm_t, bg_tiled_bytes(m->bp_lm.ntiles, D, es)});
+    both(&m->lm_t, &m->lm_ts, m->bp_lm.ntiles, D);
     size_t need = 0, free_b = 0, total_b = 0;
     for (const auto& p : want) need += p.second;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need + ((size_t)1 << 30)) return;
@@ -1511,8 +1547,10 @@ static void bg_alloc_tiles(sli_model* m) {
     m->bg_tiled = true;
 }
 
-static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp_group* group, sli_model** out) {
+static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp_group* group, uint32_t flags,
+                        sli_model** out) {
     SLI_CHECK(cfg && out, SLI_ERR_ARG, "sli_model_create: null");
+    SLI_CHECK((flags & ~(uint32_t)SLI_CREATE_MX_BATCH) == 0, SLI_ERR_ARG, "sli_model_create_flags: unknown flag bit");
     const sli_model_config& c = *cfg;
     SLI_CHECK(c.vocab > 0 && c.dim > 0 && c.n_heads > 0 && c.n_kv_heads > 0 && c.head_dim > 0 && c.ffn > 0 &&
                   c.n_layers > 0 && c.max_len > 0,
@@ -1549,8 +1587,9 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     const int B = c.batch > 0 ? c.batch : 1;
     SLI_CHECK(B <= kBgMaxBatch, SLI_ERR_SHAPE, "batch must be at most 8");
     if (B > 1) {
-        SLI_CHECK(c.w_dtype == SLI_DT_F16 || c.w_dtype == SLI_DT_I8, SLI_ERR_ARG,
-                  "batch > 1 needs fp16 or int8 weights (MFMA projections)");  // f32 and mxfp4 are refused
+        // f32 is refused; mxfp4 too unless the caller opted in (SLI_CREATE_MX_BATCH)
+        SLI_CHECK(c.w_dtype == SLI_DT_F16 || c.w_dtype == SLI_DT_I8 || (mx && (flags & SLI_CREATE_MX_BATCH)), SLI_ERR_ARG,
+                  "batch > 1 needs fp16 or int8 weights (MFMA projections)");
         SLI_CHECK(c.dim % 32 == 0 && (c.ffn / c.tp_size) % 32 == 0 && ((c.n_heads / c.tp_size) * c.head_dim) % 32 == 0,
                   SLI_ERR_SHAPE, "batch > 1: projection inputs must be multiples of 32");
         SLI_CHECK(c.dim <= kBgMaxStageK, SLI_ERR_SHAPE, "batch > 1: dim must be at most 4096 (RMS staging)");
@@ -1702,7 +1741,11 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
 }
 
 int sli_model_create(const sli_model_config* cfg, const void* comm_id, sli_model** out) {
-    return create_model(cfg, comm_id, nullptr, out);
+    return create_model(cfg, comm_id, nullptr, 0, out);
+}
+
+int sli_model_create_flags(const sli_model_config* cfg, const void* comm_id, uint32_t flags, sli_model** out) {
+    return create_model(cfg, comm_id, nullptr, flags, out);
 }
 
 int sli_model_destroy(sli_model* m) {
@@ -2569,7 +2612,12 @@ int sli_model_time_gemv(sli_model* m, int32_t iters, double* avg_us, double* byt
 
 // ---------------------------------------------------------------- in-process tensor-parallel group
 int sli_tp_group_create(const sli_model_config* cfg, int32_t tp_size, sli_tp_group** out) {
+    return sli_tp_group_create_flags(cfg, tp_size, 0, out);
+}
+
+int sli_tp_group_create_flags(const sli_model_config* cfg, int32_t tp_size, uint32_t flags, sli_tp_group** out) {
     SLI_CHECK(cfg && out, SLI_ERR_ARG, "sli_tp_group_create: null");
+    SLI_CHECK((flags & ~(uint32_t)SLI_CREATE_MX_BATCH) == 0, SLI_ERR_ARG, "sli_tp_group_create_flags: unknown flag bit");
     SLI_CHECK(tp_size >= 1 && tp_size <= kMaxGroup, SLI_ERR_ARG, "tp group size must be in [1, 8]");
     SLI_HIP(hipSetDevice(cfg->device));
     sli_tp_group* g = new sli_tp_group();
@@ -2584,7 +2632,7 @@ int sli_tp_group_create(const sli_model_config* cfg, int32_t tp_size, sli_tp_gro
         c.tp_rank = r;
         c.tp_size = tp_size;
         sli_model* m = nullptr;
-        const int rc = create_model(&c, nullptr, g, &m);
+        const int rc = create_model(&c, nullptr, g, flags, &m);
         if (rc != SLI_OK) {
             const std::string err = sli_last_error();
             sli_tp_group_destroy(g);

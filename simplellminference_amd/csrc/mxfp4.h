@@ -63,6 +63,22 @@ struct Vec16<mxfp4> {
     }
 };
 
+// 8 e2m1 codes (element 2i in bits 3:0 of byte i) -> 8 fp16, exact and unscaled, in element order. The high byte
+// of the fp16 of magnitude code c is {00, 38, 3C, 3E, 40, 42, 44, 46}[c] (0, .5, 1, 1.5, 2, 3, 4, 6), the low byte 0.
+__device__ __forceinline__ u32x4 pg_fp4_to_f16(unsigned w) {
+    const unsigned lut_hi = 0x46444240u, lut_lo = 0x3E3C3800u;
+    unsigned ev = __builtin_amdgcn_perm(lut_hi, lut_lo, w & 0x07070707u);         // elements 0, 2, 4, 6
+    unsigned od = __builtin_amdgcn_perm(lut_hi, lut_lo, (w >> 4) & 0x07070707u);  // elements 1, 3, 5, 7
+    ev |= (w & 0x08080808u) << 4;  // the sign bits
+    od |= w & 0x80808080u;
+    u32x4 r;  // dword i = {00, ev_i, 00, od_i} (selector 0x0c: a zero byte)
+    r[0] = __builtin_amdgcn_perm(od, ev, 0x040c000cu);
+    r[1] = __builtin_amdgcn_perm(od, ev, 0x050c010cu);
+    r[2] = __builtin_amdgcn_perm(od, ev, 0x060c020cu);
+    r[3] = __builtin_amdgcn_perm(od, ev, 0x070c030cu);
+    return r;
+}
+
 // ---------------------------------------------------------------- the quantisation rule (sli.h), in plain C++
 // floor(log2(a)) of a finite a > 0, exact (denormals included)
 __device__ __forceinline__ int mx_floor_log2(float a) {

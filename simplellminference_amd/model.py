@@ -16,7 +16,7 @@ from dataclasses import dataclass, replace
 import numpy as np
 
 from . import _lib
-from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
+from ._lib import CREATE_MX_BATCH, DT_F8E4M3, DT_F16, DT_F32, DT_I8, DT_MXFP4, ModelConfig, call
 
 _DTYPES = {"f32": DT_F32, "fp32": DT_F32, "f16": DT_F16, "fp16": DT_F16, "i8": DT_I8, "int8": DT_I8,
            "mxfp4": DT_MXFP4, "fp4": DT_MXFP4,
@@ -67,7 +67,7 @@ class LlamaModel:
     def __init__(self, tokenizer_path: str = "", model_path: str = "", device_type: str = "cuda",
                  config: LlamaModelConfig | None = None, w_dtype: str = "f16", kv_dtype: str = "f16",
                  act_mode: int = 0, tp_rank: int = 0, tp_size: int = 1, comm_id: bytes | None = None,
-                 device: int = 0, seed: int | None = None, batch: int = 1):
+                 device: int = 0, seed: int | None = None, batch: int = 1, mx_batch: bool = False):
         if device_type not in ("cuda", "hip"):
             raise ValueError("Device Type ERROR!")  # op/*.cpp dispatch: only the HIP backend exists here
         self.tokenizer_path = tokenizer_path
@@ -81,6 +81,8 @@ class LlamaModel:
         self.device = device
         self.seed = seed
         self.batch = batch  # sequences decoding in lockstep (extension: the reference is batch 1)
+        # opt in to MXFP4 weights at batch > 1 (SLI_CREATE_MX_BATCH); no effect on the other weight types
+        self.mx_batch = bool(mx_batch)
         self._h = None
         self.encode_layer = None
 
@@ -101,7 +103,10 @@ class LlamaModel:
         mc = self._config_struct()
         h = ctypes.c_void_p()
         cid = ctypes.create_string_buffer(self.comm_id, len(self.comm_id)) if self.comm_id else None
-        call("sli_model_create", ctypes.byref(mc), cid, ctypes.byref(h))
+        if self.mx_batch:
+            call("sli_model_create_flags", ctypes.byref(mc), cid, CREATE_MX_BATCH, ctypes.byref(h))
+        else:
+            call("sli_model_create", ctypes.byref(mc), cid, ctypes.byref(h))
         self._h = h
         return self._load_weights()
 
@@ -386,20 +391,24 @@ class TPGroup:
 
     def __init__(self, config: LlamaModelConfig, tp_size: int, w_dtype: str = "f16", kv_dtype: str = "f16",
                  act_mode: int = 0, device: int = 0, seed: int | None = None, batch: int = 1,
-                 model_path: str = ""):
+                 model_path: str = "", mx_batch: bool = False):
         self.config, self.tp_size, self.batch = config, tp_size, batch
         proto = LlamaModel(model_path=model_path, config=config, w_dtype=w_dtype, kv_dtype=kv_dtype,
                            act_mode=act_mode, tp_rank=0, tp_size=tp_size, device=device, seed=seed, batch=batch)
         mc = proto._config_struct()
         g = ctypes.c_void_p()
-        call("sli_tp_group_create", ctypes.byref(mc), tp_size, ctypes.byref(g))
+        if mx_batch:
+            call("sli_tp_group_create_flags", ctypes.byref(mc), tp_size, CREATE_MX_BATCH, ctypes.byref(g))
+        else:
+            call("sli_tp_group_create", ctypes.byref(mc), tp_size, ctypes.byref(g))
         self._g = g
         self.ranks = []
         for r in range(tp_size):
             h = ctypes.c_void_p()
             call("sli_tp_group_rank", g, r, ctypes.byref(h))
             m = LlamaModel(model_path=model_path, config=config, w_dtype=w_dtype, kv_dtype=kv_dtype,
-                           act_mode=act_mode, tp_rank=r, tp_size=tp_size, device=device, seed=seed, batch=batch)
+                           act_mode=act_mode, tp_rank=r, tp_size=tp_size, device=device, seed=seed, batch=batch,
+                           mx_batch=mx_batch)
             m._h = h
             m._borrowed = True
             self.ranks.append(m)

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, call
+from ._lib import DT_F8E4M3, DT_F16, DT_F32, DT_I8, DT_MXFP4, call
 
 _DT = {torch.float32: DT_F32, torch.float16: DT_F16, torch.int8: DT_I8, torch.float8_e4m3fn: DT_F8E4M3}
 _KV_NAMES = {"f32": DT_F32, "f16": DT_F16, "f8": DT_F8E4M3, "fp8": DT_F8E4M3, "e4m3": DT_F8E4M3}
@@ -149,6 +149,27 @@ def matmul_batch_i8(x, w, row_scale=None, tiled: bool = False, y=None):
     ws = torch.empty(nbytes // 4 + 1, device=x.device, dtype=torch.float32)
     _dev(x, w, row_scale, y, ws)
     call("sli_matmul_batch_i8", _p(x), _p(w), _p(row_scale), _p(y), rows, cols, batch, int(tiled), _p(ws),
+         ws.numel() * 4, _s())
+    return y
+
+
+def matmul_batch_mxfp4(x, data, scales, tiled: bool = False, y=None):
+    """The batched projection from MXFP4 weights: y[b][r] = sum_c x[b][c] * code(W[r][c]) * 2^(scale[r][c / 32] - 127);
+    x [B, cols] fp32, data uint8 [rows, cols / 2] and scales uint8 [rows, cols / 32] (quant_mxfp4's layout), y [B, rows]
+    fp32. tiled=True first re-lays data and scales into the model's fragment-layout images (inside the workspace) and
+    streams those, the path a batched MXFP4 model runs."""
+    batch, cols = x.shape
+    rows = data.shape[0]
+    if (data.dtype != torch.uint8 or scales.dtype != torch.uint8 or cols % 32 or data.shape != (rows, cols // 2)
+            or scales.shape != (rows, cols // 32)):
+        raise ValueError("Tensor with Wrong Dim!")
+    y = torch.empty(batch, rows, device=x.device, dtype=torch.float32) if y is None else y
+    nbytes = _lib.load().sli_matmul_batch_mxfp4_workspace_bytes(rows, cols, batch, int(tiled))
+    if nbytes == 0:
+        raise ValueError("unsupported batched shape (cols % 32 != 0 or batch > 8)")
+    ws = torch.empty(nbytes // 4 + 1, device=x.device, dtype=torch.float32)
+    _dev(x, data, scales, y, ws)
+    call("sli_matmul_batch_mxfp4", _p(x), _p(data), _p(scales), _p(y), rows, cols, batch, int(tiled), _p(ws),
          ws.numel() * 4, _s())
     return y
 
@@ -355,16 +376,48 @@ BG_ROLE_QKV, BG_ROLE_GATE_UP, BG_ROLE_STORE, BG_ROLE_LOGITS = 0, 1, 2, 3
 
 def batch_gemm_plan(rows: int, K: int, B: int, norm: bool, w_dtype=DT_F16, tiled: bool = False, plan=None):
     """The plan sli_batch_gemm would run for a [rows, K] matrix and the workspace bytes it needs, without a device:
-    plan None asks the engine's planner, (tpw, splits) forces one. Returns (plan dict, bytes); bytes 0: refused."""
+    plan None asks the engine's planner, (tpw, splits) forces one. Returns (plan dict, bytes); bytes 0: refused.
+    w_dtype DT_MXFP4: the plan and bytes of sli_batch_gemm_mxfp4."""
     p = _lib.BgemmPlan(tpw=plan[0], splits=plan[1]) if plan else _lib.BgemmPlan()
-    nbytes = call("sli_batch_gemm_workspace_bytes", rows, K, B, int(norm), w_dtype, int(tiled), ctypes.byref(p))
+    if w_dtype == DT_MXFP4:
+        nbytes = call("sli_batch_gemm_mxfp4_workspace_bytes", rows, K, B, int(norm), int(tiled), ctypes.byref(p))
+    else:
+        nbytes = call("sli_batch_gemm_workspace_bytes", rows, K, B, int(norm), w_dtype, int(tiled), ctypes.byref(p))
     return {n: getattr(p, n) for n, _ in p._fields_}, nbytes
 
 
-def _batch_gemm(x, norm_w, eps, w, row_scale, tiled, epi, rows, plan, ws):
+def _batch_gemm_mx(x, norm_w, eps, data, scales, tiled, epi, rows, plan, ws):
+    """sli_batch_gemm_mxfp4: _batch_gemm with w = the uint8 data [rows, K / 2] and scales = the block scales [rows, K / 32]."""
+    B, K = x.shape
+    if (K % 32 or data.dtype != torch.uint8 or scales.dtype != torch.uint8 or data.shape != (rows, K // 2)
+            or scales.shape != (rows, K // 32) or x.dtype != torch.float32):
+        raise ValueError("Tensor with Wrong Dim!")
+    if norm_w is not None and norm_w.numel() != K:
+        raise ValueError("Tensor with Wrong Dim!")
+    p = _lib.BgemmPlan(tpw=plan[0], splits=plan[1]) if plan else _lib.BgemmPlan()
+    q = _lib.BgemmPlan(tpw=p.tpw, splits=p.splits)
+    nbytes = call("sli_batch_gemm_mxfp4_workspace_bytes", rows, K, B, int(norm_w is not None), int(tiled), ctypes.byref(q))
+    if nbytes == 0:
+        raise _lib.SliError(1, "sli_batch_gemm_mxfp4_workspace_bytes", (_lib.load().sli_last_error() or b"").decode())
+    if ws is None:
+        ws = torch.zeros(nbytes, device=x.device, dtype=torch.uint8)
+    _dev(x, norm_w, data, scales, ws)
+    call("sli_batch_gemm_mxfp4", _p(x), _p(norm_w), eps, _p(data), _p(scales), int(tiled), K, B, ctypes.byref(epi),
+         ctypes.byref(p), _p(ws), ws.numel(), _s())
+    out = {n: getattr(p, n) for n, _ in p._fields_}
+    out["ws"] = ws
+    return out
+
+
+def _batch_gemm(x, norm_w, eps, w, row_scale, tiled, epi, rows, plan, ws, scales=None):
     """sli_batch_gemm. plan None: the engine's planner; (tpw, splits): forced. ws: a workspace of an earlier call
     with the same plan, reused as it is (its arrival counters are zero again), or None for a fresh zeroed one.
-    Returns the plan that ran as a dict, with the workspace (a uint8 tensor) under "ws"."""
+    Returns the plan that ran as a dict, with the workspace (a uint8 tensor) under "ws".
+    scales given: MXFP4 weights, w is the uint8 data and scales the block scales (sli_batch_gemm_mxfp4)."""
+    if scales is not None:
+        if row_scale is not None:
+            raise ValueError("MXFP4 weights have block scales, not a row scale: pass scales or row_scale, not both")
+        return _batch_gemm_mx(x, norm_w, eps, w, scales, tiled, epi, rows, plan, ws)
     B, K = x.shape
     if w.shape != (rows, K) or w.dtype not in (torch.float16, torch.int8) or x.dtype != torch.float32:
         raise ValueError("Tensor with Wrong Dim!")
@@ -386,8 +439,10 @@ def _batch_gemm(x, norm_w, eps, w, row_scale, tiled, epi, rows, plan, ws):
     return out
 
 
+# With `scales` given, every batch_gemm_* below runs MXFP4 weights: w is the uint8 data [rows, K / 2] and scales the e8m0
+# block scales [rows, K / 32] (quant_mxfp4's layout); row_scale together with scales is a ValueError.
 def batch_gemm_qkv(x, norm_w, eps: float, w, q, kc, vc, pos, sin_t, cos_t, hq: int, hkv: int, hd: int, row_scale=None,
-                   tiled: bool = False, plan=None, kv_dtype=None, ws=None):
+                   tiled: bool = False, plan=None, kv_dtype=None, ws=None, scales=None):
     """One bgemm_kernel launch with the q/k/v epilogue (fused RMSNorm, row scale, RoPE, K/V cache write): x [B, K]
     fp32, W [(hq + 2 hkv) hd, K] fp16 or int8; q [>= B, hq hd] fp32; kc / vc one layer's cache [B, hkv, T, hd] (f32, f16,
     or E4M3 codes with kv_dtype="f8"); pos int32 [B] on the device, 0 <= pos[b] < T. Returns the plan that ran."""
@@ -403,11 +458,11 @@ def batch_gemm_qkv(x, norm_w, eps: float, w, q, kc, vc, pos, sin_t, cos_t, hq: i
     e = _lib.BgemmEpilogue(role=BG_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
                            kv_dtype=_kv_dt(kc, kv_dtype), pos=pos.data_ptr(), sin_t=sin_t.data_ptr(),
                            cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv, hd=hd, T=T)
-    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, (hq + 2 * hkv) * hd, plan, ws)
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, (hq + 2 * hkv) * hd, plan, ws, scales)
 
 
 def batch_gemm_gate_up(x, norm_w, eps: float, w, act, act_mode: int = 0, row_scale=None, tiled: bool = False,
-                       plan=None, ws=None):
+                       plan=None, ws=None, scales=None):
     """One bgemm_kernel launch with the gate/up epilogue: W [2 inter, K] = [gate; up]; act [>= B, inter] fp32 gets
     sigmoid(g) * u (act_mode 0) or SiLU(g) * u (1) of the RMS-normalised x. Returns the plan that ran."""
     inter = w.shape[0] // 2
@@ -415,10 +470,11 @@ def batch_gemm_gate_up(x, norm_w, eps: float, w, act, act_mode: int = 0, row_sca
         raise ValueError("Tensor with Wrong Dim!")
     _dev(act)
     e = _lib.BgemmEpilogue(role=BG_ROLE_GATE_UP, act=act.data_ptr(), inter=inter, act_mode=act_mode)
-    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, 2 * inter, plan, ws)
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, 2 * inter, plan, ws, scales)
 
 
-def batch_gemm_store(x, w, y, resid=None, scale: float = 1.0, row_scale=None, tiled: bool = False, plan=None, ws=None):
+def batch_gemm_store(x, w, y, resid=None, scale: float = 1.0, row_scale=None, tiled: bool = False, plan=None, ws=None,
+                     scales=None):
     """One bgemm_kernel launch with the wo / down epilogue: y [>= B, ld] = (resid or 0) + (W x) * row scale * scale for
     the W.shape[0] rows; resid [B, ld] may be y itself. Returns the plan that ran."""
     if y.dim() != 2 or y.shape[0] < x.shape[0] or y.dtype != torch.float32 or (resid is not None and resid.shape != y.shape):
@@ -426,11 +482,11 @@ def batch_gemm_store(x, w, y, resid=None, scale: float = 1.0, row_scale=None, ti
     _dev(y, resid)
     e = _lib.BgemmEpilogue(role=BG_ROLE_STORE, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
                            scale=scale, nrows=w.shape[0], ld=y.shape[1])
-    return _batch_gemm(x, None, 0.0, w, row_scale, tiled, e, w.shape[0], plan, ws)
+    return _batch_gemm(x, None, 0.0, w, row_scale, tiled, e, w.shape[0], plan, ws, scales)
 
 
 def batch_gemm_logits(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int = 0, row_scale=None,
-                      tiled: bool = False, plan=None, ws=None):
+                      tiled: bool = False, plan=None, ws=None, scales=None):
     """One bgemm_kernel launch with the LM-head epilogue: logits [>= B, ld] fp32 of the RMS-normalised x and, in keys_out
     [>= B, key_ld] (int64 holding the uint64 keys), each workgroup group's largest argmax key per sequence. Returns
     the plan that ran."""
@@ -441,7 +497,7 @@ def batch_gemm_logits(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int
     _dev(logits, keys_out)
     e = _lib.BgemmEpilogue(role=BG_ROLE_LOGITS, logits=logits.data_ptr(), keys_out=keys_out.data_ptr(),
                            nrows=w.shape[0], ld=logits.shape[1], vocab_off=vocab_off, key_ld=keys_out.shape[1])
-    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, w.shape[0], plan, ws)
+    return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, w.shape[0], plan, ws, scales)
 
 
 def argmax(logits, out=None):
