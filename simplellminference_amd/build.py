@@ -22,7 +22,10 @@ LIB = os.path.join(PKG, "libsli.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("SLI_OFFLOAD_ARCH", "gfx950")
 
-CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
+# -amdgpu-kernarg-preload-count: the leading plain (pointer / int) kernel arguments arrive in SGPRs at wave start
+# instead of behind a kernarg load; the decode kernels put what their first loads need there (gemv.h gemv_kernel)
+KERNARG_PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
+CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", *KERNARG_PRELOAD,
             "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "include", "base"),
             "-I", os.path.join(ROOT, "include", "memory"), "-I", os.path.join(ROOT, "include", "op"),
             "-I", os.path.join(ROOT, "include", "model"), "-I", os.path.join(ROOT, "include", "kernel")]

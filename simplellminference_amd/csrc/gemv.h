@@ -17,8 +17,18 @@
 #include "common.h"
 #include "mxfp4.h"
 
+// Per-wave stamps (GemvIn::stamps) of the launches with a hot block exist in the lab binaries only: tools/gemv_lab
+// defines this to 1 ahead of the include.
+#ifndef SLI_GEMV_STAMPS
+#define SLI_GEMV_STAMPS 0
+#endif
+
 namespace sli {
 
+// The host-side description of a GEMV's input, and the kernels' argument behind the hot block. The launch sites
+// (launch_gemv*) pass x, norm_w, cols, csplit and cw again as plain leading kernel arguments (preloaded into
+// SGPRs), and the kernels read those: the copies of these five fields in the kernel-side struct are overwritten
+// from the hot block before use, so the host-side struct stays the one source of the values.
 struct GemvIn {
     const float* x;       // [cols] fp32 input vector
     const float* norm_w;  // nullptr: plain; else fused RMSNorm weight [cols]
@@ -38,6 +48,25 @@ constexpr int kGemvLdsHead = 64;  // floats of reduction scratch in front of the
 inline size_t gemv_lds_bytes(int cols) { return sizeof(float) * (size_t)(kGemvLdsHead + cols); }
 
 constexpr int kGemvStageV4 = 4;  // float4 of x per thread: 1024 threads x 4 x 4 = 16384 columns
+
+// Exact unsigned division by a divisor known on the host when the launch is recorded (Granlund & Montgomery,
+// "Division by invariant integers using multiplication", the round-up form): for every 32-bit n,
+// n / d == (q + ((n - q) >> s1)) >> s2 with q = mulhi(n, m). One v_mul_hi / s_mul_hi and four ALU ops instead of
+// the long serial sequence a division by a runtime value compiles to, on the path to the first weight load.
+struct UDiv {
+    unsigned m;   // the multiplier
+    unsigned sh;  // s1 | s2 << 8
+};
+inline UDiv udiv_make(unsigned d) {
+    unsigned l = 0;  // ceil(log2 d)
+    while (l < 32 && (1ull << l) < d) ++l;
+    const unsigned m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
+    return {m, (l < 1u ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 8)};
+}
+__host__ __device__ __forceinline__ unsigned udiv(unsigned n, unsigned m, unsigned sh) {
+    const unsigned q = (unsigned)(((unsigned long long)n * m) >> 32);
+    return (q + ((n - q) >> (sh & 255u))) >> ((sh >> 8) & 255u);
+}
 
 // The prologue is split into issue (global loads into registers) and commit (normalise, write LDS) so
 // the kernel can issue its input loads FIRST, its weight loads second, and wait only for the input:
@@ -136,6 +165,8 @@ struct XStage {
 // kernel's own last-arriver merge, without that merge's serial tail (an arrival counter, a second round
 // trip to the partials and a store) inside the attention launch. The partials are loaded with the input
 // loads, before the weight stream, like XStage's x (NS splits in flight per thread, the rest from memory).
+// (gemv_merge_kernel takes part, pos_dev, max_splits and hd again in its hot block and overwrites the kernel-side
+// copies from it, like GemvIn's)
 struct AttnMergeIn {
     const float* part;       // [heads][max_splits][hd + kAttnPartPad]
     const int32_t* pos_dev;  // the live context: ns = min(pos / ppwg + 1, max_splits)
@@ -153,6 +184,7 @@ struct XStageMerge {
     float2 ml[NS];
     int pos = 0;
     int h0 = 0;  // first head of this workgroup's input (K-split wo)
+    unsigned tw_m = 0, tw_sh = 0;  // udiv by the grid's waves (the kernel sets them from its hot block)
     __device__ __forceinline__ const float* row(int f, int s) const {
         const int h = h0 + f / (am.hd >> 2);
         return am.part + ((size_t)h * am.max_splits + min(s, am.max_splits - 1)) * (am.hd + kAttnPartPad);
@@ -160,7 +192,7 @@ struct XStageMerge {
     __device__ __forceinline__ void issue(const GemvIn& in) {
         if (am.ksplit > 1) {  // the block k of the workgroup's first unit (gemv_block's balanced partition)
             const int nw = kGemvThreads >> 6;
-            const int ub = (int)(((unsigned)(blockIdx.x * nw) * (unsigned)(am.ksplit * am.kunits)) / (unsigned)(gridDim.x * nw));
+            const int ub = (int)udiv((unsigned)(blockIdx.x * nw) * (unsigned)(am.ksplit * am.kunits), tw_m, tw_sh);
             h0 = (ub / am.kunits) * (in.cols / am.hd);
         }
         const int f = min((int)threadIdx.x, (in.cols >> 2) - 1);  // the first round of the input
@@ -330,6 +362,24 @@ __device__ __forceinline__ int gemv_unit_begin(int gwave, int nunits, int total_
     return (int)(((unsigned)gwave * (unsigned)nunits) / (unsigned)total_waves);
 }
 
+// The launch's unit partition, computed once on the host where the launch is recorded (launch_gemv*): what
+// gemv_block would otherwise derive by division before its first weight load. The same partition as
+// gemv_unit_begin's, bit for bit (udiv is exact).
+struct GemvPart {
+    int nunits;      // epi.units()
+    int cpp;         // chunks per column part: ceil(ceil(nvec / CV) / csplit)
+    unsigned tw_m;   // udiv by the grid's waves (gemv_unit_begin)
+    unsigned cw_m;   // udiv by the streaming waves per workgroup
+    unsigned sh;     // tw's shifts | cw's shifts << 16
+};
+template <typename WT, int U>
+inline GemvPart gemv_part(int cols, int csplit, int nunits, int grid, int cw) {
+    const int nvec = cols / Vec16<WT>::N, cv = U * 64;
+    const int cpr = (nvec + cv - 1) / cv;
+    const UDiv tw = udiv_make((unsigned)grid * (kGemvThreads / 64)), c = udiv_make((unsigned)cw);
+    return {nunits, (cpr + csplit - 1) / csplit, tw.m, c.m, tw.sh | (c.sh << 16)};
+}
+
 // Result slots in LDS behind the staged x: R floats per (unit, column part) of the workgroup.
 inline size_t gemv_res_floats(int units, int grid, int R, int csplit = 1) {
     return (size_t)R * csplit * ((size_t)units / grid + 2);
@@ -349,9 +399,12 @@ inline size_t gemv_res_floats(int units, int grid, int R, int csplit = 1) {
 // for the first weight chunk (staged 4-6 us into a 10-30 us launch). The epilogue (residual reads,
 // RoPE, K/V writes, logits) runs once per workgroup after the loop, one thread per unit.
 // Prologue order: input loads, first weight chunk, input commit + barrier (see XStage).
-template <typename WT, int R, int U, bool NT, class Epi, class Stage, int NB = 2, bool SPLIT = false, bool OFFS = false>
+// PART: the partition values come from the host (pt, gemv_part) instead of the divisions below: the same values.
+template <typename WT, int R, int U, bool NT, class Epi, class Stage, int NB = 2, bool SPLIT = false, bool OFFS = false,
+          bool PART = false>
 __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvIn& in, Epi& epi, Stage& stage,
-                                           float* smem) {
+                                           float* smem, const GemvPart& pt = GemvPart{}) {
+    static_assert(!(PART && OFFS), "a launch shared with other workgroups derives its partition on the device");
     const float* xs = smem + kGemvLdsHead;
 
     constexpr int EPV = Vec16<WT>::N;
@@ -361,34 +414,48 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     const int nwaves = kGemvThreads >> 6;  // compile-time: blockDim.x is a dispatch-packet load
     const int nvec = in.cols / EPV;
     const size_t row_bytes = wt_row_bytes<WT>((size_t)in.cols);
-    const int nunits = epi.units();
+    const int nunits = PART ? pt.nunits : epi.units();
     // OFFS: the GEMV is workgroups [in.blk0, gridDim.x) of a launch it shares (qkv_attn.h)
     const int bx = OFFS ? (int)blockIdx.x - in.blk0 : (int)blockIdx.x;
     const int total_waves = (OFFS ? (in.blk1 > 0 ? in.blk1 : (int)gridDim.x) - in.blk0 : (int)gridDim.x) * nwaves;
-    const int ub = gemv_unit_begin(bx * nwaves, nunits, total_waves);  // workgroup's first unit
-    const int ue = gemv_unit_begin((bx + 1) * nwaves, nunits, total_waves);
+    const auto unit_begin = [&](int gwave) {
+        if constexpr (PART) return (int)udiv((unsigned)gwave * (unsigned)nunits, pt.tw_m, pt.sh & 0xffffu);
+        else return gemv_unit_begin(gwave, nunits, total_waves);
+    };
+    const int ub = unit_begin(bx * nwaves);  // workgroup's first unit
+    const int ue = unit_begin((bx + 1) * nwaves);
     const int cpr = (nvec + CV - 1) / CV;  // chunks per row
     // Column split (small matrices, e.g. tensor-parallel shards): a unit's rows are cut into CS parts of
     // cpp chunks; the workgroup's (unit, part) items are balanced over its waves and the parts' row sums
     // are added in part order in the epilogue. CS = 1: one item per unit, the whole row per wave.
     const int CS = SPLIT ? in.csplit : 1;  // compile-time 1 unless the launch split the columns
-    const int cpp = (cpr + CS - 1) / CS;  // chunks per part (a part past the row end is all masked)
+    const int cpp = PART && SPLIT ? pt.cpp : (cpr + CS - 1) / CS;  // chunks per part (a part past the row end is all masked)
     const int ni = (ue - ub) * CS;       // the workgroup's items
     // in.cw streaming waves share the items; a wave past them has none and repeats the loads of wave
     // (wave - cw)'s first steps (L2 hits on lines in flight), so no load sits behind a branch
     const int cw = in.cw;
     const bool idle = wave >= cw;
     const int wq = idle ? wave - cw : wave;
-    const int ib = (int)(((unsigned)wq * (unsigned)ni) / (unsigned)cw);
-    const int ie = idle ? ib : (int)(((unsigned)(wq + 1) * (unsigned)ni) / (unsigned)cw);
+    const auto item_begin = [&](int w) {
+        if constexpr (PART) return (int)udiv((unsigned)w * (unsigned)ni, pt.cw_m, pt.sh >> 16);
+        else return (int)(((unsigned)w * (unsigned)ni) / (unsigned)cw);
+    };
+    const int ib = item_begin(wq);
+    const int ie = idle ? ib : item_begin(wq + 1);
     const int nsteps = (ie - ib) * cpp;
     float* res = smem + kGemvLdsHead + in.cols;
 
-    const unsigned long long t_entry = in.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-    unsigned long long t_staged = 0;
+    // PART kernels (the launches with a hot block): stamps are compiled into the lab binaries only
+    // (SLI_GEMV_STAMPS): a runtime test of in.stamps here makes every wave wait for the kernarg load of that field
+    // before its first input load. The other callers (qkv_attn.h) keep the runtime test and the former load order.
+    const bool stamps = (!PART || SLI_GEMV_STAMPS) && in.stamps != nullptr;
+    const unsigned long long t_entry = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
+    unsigned long long t_staged = 0, t_first = 0;
     // (a LATE stage (qkv_attn.h XStageHand) waits for its input inside issue(): it is issued after the first
     // weight steps, so the weights stream during the wait)
     if constexpr (!stage_late<Stage>()) stage.issue(in);
+    // PART: the input loads need the hot block only: issued before anything waits for the epilogue's kernarg loads
+    if constexpr (PART) __builtin_amdgcn_sched_barrier(0);
     // the epilogue's own inputs for this thread's unit (the store loop's first unit): in flight with the
     // input, landed long before the stream ends instead of a round trip after it
     const int pre_unit = max(min(ub + (int)threadIdx.x, nunits - 1), 0);
@@ -472,13 +539,15 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
     for (int b = 0; b < NB; ++b) {
         load_step(lq, wbuf[b], sbuf[b]);
         next(lq);
+        if constexpr (PART)
+            if (b == 0 && stamps) t_first = __builtin_amdgcn_s_memrealtime();  // the first weight step is issued
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (stage_late<Stage>()) stage.issue(in);
     stage.commit(smem, in);
     __syncthreads();
     epi.prefetch_b(pre_unit);
-    t_staged = in.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
+    t_staged = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     int k = 0;
     for (; k + NB < nsteps; k += NB) {
 #pragma unroll
@@ -510,43 +579,69 @@ __device__ __forceinline__ void gemv_block(const WT* __restrict__ W, const GemvI
         epi.store(u, rows, v);
     }
     epi.finish(smem);
-    if (in.stamps && lane == 0) {
+    if (stamps && lane == 0) {
         unsigned long long* p = in.stamps + ((size_t)bx * nwaves + wave) * 4;
         p[0] = t_entry;
         p[1] = t_staged;
         p[2] = __builtin_amdgcn_s_memrealtime();
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        p[3] = (unsigned long long)max(nsteps, 1) | ((unsigned long long)(xcc & 15) << 32);  // diagnostic: XCD
+        // steps | XCD << 32 | PART: (entry -> first weight step issued, in 10 ns ticks) << 36
+        p[3] = (unsigned long long)max(nsteps, 1) | ((unsigned long long)(xcc & 15) << 32) |
+               (PART ? (t_first - t_entry) << 36 : 0ull);
     }
 }
 
+// Kernel arguments: a leading run of 14 dwords of plain pointers and ints (the hot block), then the by-value
+// structs. The build preloads the leading plain arguments into SGPRs (-amdgpu-kernarg-preload-count=14; the
+// preload stops at the first struct), so what the first input load and the first weight address need (pointers,
+// column count, the host's partition: GemvPart) is in registers at the wave's first instruction, and only the rest
+// (eps, stamps, block scales, the epilogue) waits for the kernarg loads. The hot values replace the same fields of
+// the struct copies.
 template <typename WT, int R, int U, bool NT, class Epi, int NB = 2, bool SPLIT = false>
-__global__ void __launch_bounds__(kGemvThreads) gemv_kernel(const WT* __restrict__ W, GemvIn in, Epi epi_in) {
+__global__ void __launch_bounds__(kGemvThreads)
+    gemv_kernel(const WT* __restrict__ W, const float* x, const float* norm_w, int cols, int csplit, int cw, int nunits,
+                int cpp, unsigned tw_m, unsigned cw_m, unsigned div_sh, GemvIn in_, Epi epi_in) {
     Epi epi = epi_in;  // mutable per-thread copy (EpiLogits keeps a running key)
+    GemvIn in = in_;
+    in.x = x, in.norm_w = norm_w, in.cols = cols, in.csplit = csplit, in.cw = cw;
+    const GemvPart pt{nunits, cpp, tw_m, cw_m, div_sh};
     extern __shared__ __attribute__((aligned(16))) float smem[];
     XStage<Vec16<WT>::N / 4> stage;
-    gemv_block<WT, R, U, NT, Epi, XStage<Vec16<WT>::N / 4>, NB, SPLIT>(W, in, epi, stage, smem);
+    gemv_block<WT, R, U, NT, Epi, XStage<Vec16<WT>::N / 4>, NB, SPLIT, false, true>(W, in, epi, stage, smem, pt);
 }
 
-// the wo GEMV with its input merged from the attention's split partials (XStageMerge)
+// the wo GEMV with its input merged from the attention's split partials (XStageMerge); hot block: the partials,
+// the position and their geometry instead of x (unused here)
 template <typename WT, int R, int U, bool NT, class Epi, int NS = 8, int NB = 2>
-__global__ void __launch_bounds__(kGemvThreads) gemv_merge_kernel(const WT* __restrict__ W, GemvIn in, Epi epi_in,
-                                                                  AttnMergeIn am) {
+__global__ void __launch_bounds__(kGemvThreads)
+    gemv_merge_kernel(const WT* __restrict__ W, const float* part, const int32_t* pos_dev, int cols, int cw, int nunits,
+                      unsigned tw_m, unsigned cw_m, unsigned div_sh, int max_splits, int hd, GemvIn in_, Epi epi_in,
+                      AttnMergeIn am_) {
     Epi epi = epi_in;
+    GemvIn in = in_;
+    in.cols = cols, in.csplit = 1, in.cw = cw;
+    AttnMergeIn am = am_;
+    am.part = part, am.pos_dev = pos_dev, am.max_splits = max_splits, am.hd = hd;
+    const GemvPart pt{nunits, 0, tw_m, cw_m, div_sh};
     extern __shared__ __attribute__((aligned(16))) float smem[];
     XStageMerge<Vec16<WT>::N / 4, NS> stage{am};
-    gemv_block<WT, R, U, NT, Epi, XStageMerge<Vec16<WT>::N / 4, NS>, NB>(W, in, epi, stage, smem);
+    stage.tw_m = tw_m, stage.tw_sh = div_sh & 0xffffu;
+    gemv_block<WT, R, U, NT, Epi, XStageMerge<Vec16<WT>::N / 4, NS>, NB, false, false, true>(W, in, epi, stage, smem, pt);
 }
 
 // a GEMV whose input is x plus NP partial vectors (XStageSum)
 template <typename WT, int R, int U, bool NT, class Epi, int NP, int NB = 2>
-__global__ void __launch_bounds__(kGemvThreads) gemv_sum_kernel(const WT* __restrict__ W, GemvIn in, Epi epi_in,
-                                                                const float* parts) {
+__global__ void __launch_bounds__(kGemvThreads)
+    gemv_sum_kernel(const WT* __restrict__ W, const float* x, const float* norm_w, const float* parts, int cols, int cw,
+                    int nunits, unsigned tw_m, unsigned cw_m, unsigned div_sh, GemvIn in_, Epi epi_in) {
     Epi epi = epi_in;
+    GemvIn in = in_;
+    in.x = x, in.norm_w = norm_w, in.cols = cols, in.csplit = 1, in.cw = cw;
+    const GemvPart pt{nunits, 0, tw_m, cw_m, div_sh};
     extern __shared__ __attribute__((aligned(16))) float smem[];
     XStageSum<Vec16<WT>::N / 4, NP> stage{parts};
-    gemv_block<WT, R, U, NT, Epi, XStageSum<Vec16<WT>::N / 4, NP>, NB>(W, in, epi, stage, smem);
+    gemv_block<WT, R, U, NT, Epi, XStageSum<Vec16<WT>::N / 4, NP>, NB, false, false, true>(W, in, epi, stage, smem, pt);
 }
 
 // Row-by-row fallback for shapes the vector kernel cannot take (cols*sizeof(WT) not a multiple of 16
@@ -672,19 +767,21 @@ struct EpiKPart {
     int D, ks;
     int pre_u = -1;
     float pre_s = 1.0f;
+    unsigned d_m = 0, d_sh = 0;  // udiv by D (epi_prepare; 0: divide on the device)
     __device__ int units() const { return D * ks; }
+    __device__ int div_d(int u) const { return d_m ? (int)udiv((unsigned)u, d_m, d_sh) : u / D; }
     __device__ void rows(int u, int* r) const {
-        const int k = u / D;
+        const int k = div_d(u);
         r[0] = (u - k * D) * ks + k;
     }
     __device__ void prefetch_a(int u) {
         pre_u = u;
-        const int k = u / D;
+        const int k = div_d(u);
         pre_s = rscale ? rscale[u - k * D] : 1.0f;
     }
     __device__ void prefetch_b(int) {}
     __device__ void store(int u, const int*, const float* v) const {
-        const int k = u / D;
+        const int k = div_d(u);
         const float s = rscale ? (u == pre_u ? pre_s : rscale[u - k * D]) : 1.0f;
         part[u] = v[0] * s;
     }
@@ -707,6 +804,8 @@ struct EpiQKV {
     int hq, hkv, hd, T;
     int pre_u = -1, pre_pos = 0;  // entry prefetch: position, row scales; then the RoPE table entries
     float pre_s0 = 1.0f, pre_s1 = 1.0f, pre_sin = 0.0f, pre_cos = 1.0f;
+    unsigned half_m = 0, half_sh = 0;  // udiv by hd / 2 (epi_prepare; 0: divide on the device)
+    __device__ int div_half(int u) const { return half_m ? (int)udiv((unsigned)u, half_m, half_sh) : u / (hd / 2); }
     __device__ int units() const { return (hq + 2 * hkv) * (hd / 2); }
     __device__ void prefetch_a(int u) {
         pre_u = u;
@@ -722,20 +821,20 @@ struct EpiQKV {
     // after the input commit (the position has landed with the input): the table row of this position
     __device__ void prefetch_b(int u) {
         const int half = hd / 2;
-        const int d = u - (u / half) * half;
+        const int d = u - div_half(u) * half;
         pre_sin = sin_t[pre_pos * half + d];
         pre_cos = cos_t[pre_pos * half + d];
     }
     __device__ void rows(int u, int* r) const {
         const int half = hd / 2;
-        const int uh = u / half;
+        const int uh = div_half(u);
         const int d = u - uh * half;
         r[0] = uh * hd + d;
         r[1] = uh * hd + d + half;
     }
     __device__ void store(int u, const int* r, const float* acc) const {
         const int half = hd / 2;
-        const int uh = u / half;
+        const int uh = div_half(u);
         const int d = u - uh * half;
         const bool pre = u == pre_u;
         float a0 = acc[0], a1 = acc[1];
@@ -920,17 +1019,41 @@ inline int gemv_wave_count(int units, int grid) {
 #ifndef SLI_WO_NB
 #define SLI_WO_NB 2
 #endif
+// Host-side preparation of an epilogue at the launch site: the exact multipliers (udiv) of its launch-invariant
+// divisors. Epilogues without one are passed as they are.
+template <class Epi>
+inline void epi_prepare(Epi&) {}
+template <typename KT>
+inline void epi_prepare(EpiQKV<KT>& e) {
+    const UDiv h = udiv_make((unsigned)(e.hd / 2));
+    e.half_m = h.m, e.half_sh = h.sh;
+}
+inline void epi_prepare(EpiKPart& e) {
+    const UDiv d = udiv_make((unsigned)e.D);
+    e.d_m = d.m, e.d_sh = d.sh;
+}
+
+// the merge-staged launch of a prepared grid (launch_gemv_merge, launch_gemv_merge_ks)
+template <typename WT, int R, int U, bool NT, class Epi, int NS, int NB>
+hipError_t launch_gemv_merge_grid(const WT* W, const GemvIn& in_, const Epi& epi_, const AttnMergeIn& am, int units,
+                                  int grid, hipStream_t s) {
+    GemvIn in = in_;
+    in.cw = gemv_wave_count<WT>(units, grid);
+    Epi epi = epi_;
+    epi_prepare(epi);
+    const GemvPart pt = gemv_part<WT, U>(in.cols, 1, units, grid, in.cw);
+    const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
+    hipLaunchKernelGGL((gemv_merge_kernel<WT, R, U, NT, Epi, NS, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W,
+                       am.part, am.pos_dev, in.cols, in.cw, pt.nunits, pt.tw_m, pt.cw_m, pt.sh, am.max_splits, am.hd, in,
+                       epi, am);
+    return hipGetLastError();
+}
+
 template <typename WT, int R, int U, bool NT, class Epi, int NS = 8, int NB = SLI_WO_NB>
 hipError_t launch_gemv_merge(const WT* W, const GemvIn& in_, const Epi& epi, const AttnMergeIn& am, int units,
                              hipStream_t s) {
     if (in_.csplit != 1) return hipErrorInvalidValue;  // the merge-staged wo GEMV runs unsplit
-    const int grid = gemv_balanced_blocks(units);
-    GemvIn in = in_;
-    in.cw = gemv_wave_count<WT>(units, grid);
-    const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
-    hipLaunchKernelGGL((gemv_merge_kernel<WT, R, U, NT, Epi, NS, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W, in,
-                       epi, am);
-    return hipGetLastError();
+    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, gemv_balanced_blocks(units), s);
 }
 
 // K-split wo: the grid must keep every workgroup's units inside one block k (gemv_block's partition b * N / g):
@@ -946,35 +1069,36 @@ hipError_t launch_gemv_merge_ks(const WT* W, const GemvIn& in_, const Epi& epi, 
                                 hipStream_t s) {
     const int units = am.ksplit * am.kunits;
     if (in_.csplit != 1 || grid <= 0 || grid % am.ksplit || am.kunits % (grid / am.ksplit)) return hipErrorInvalidValue;
-    GemvIn in = in_;
-    in.cw = gemv_wave_count<WT>(units, grid);
-    const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
-    hipLaunchKernelGGL((gemv_merge_kernel<WT, R, U, NT, Epi, NS, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W, in,
-                       epi, am);
-    return hipGetLastError();
+    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, grid, s);
 }
 template <typename WT, int R, int U, bool NT, class Epi, int NP, int NB = 2>
-hipError_t launch_gemv_sum(const WT* W, const GemvIn& in_, const Epi& epi, const float* parts, int units,
+hipError_t launch_gemv_sum(const WT* W, const GemvIn& in_, const Epi& epi_, const float* parts, int units,
                            hipStream_t s) {
     if (in_.csplit != 1 || in_.cols > 4 * kGemvThreads) return hipErrorInvalidValue;  // XStageSum: one round
     GemvIn in = in_;
     const int grid = gemv_balanced_blocks(units);
     in.cw = gemv_wave_count<WT>(units, grid);
     const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
-    hipLaunchKernelGGL((gemv_sum_kernel<WT, R, U, NT, Epi, NP, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W, in,
-                       epi, parts);
+    Epi epi = epi_;
+    epi_prepare(epi);
+    const GemvPart pt = gemv_part<WT, U>(in.cols, 1, units, grid, in.cw);
+    hipLaunchKernelGGL((gemv_sum_kernel<WT, R, U, NT, Epi, NP, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W, in.x,
+                       in.norm_w, parts, in.cols, in.cw, pt.nunits, pt.tw_m, pt.cw_m, pt.sh, in, epi);
     return hipGetLastError();
 }
 
 template <typename WT, int R, int U, bool NT, class Epi, int NB = 2, bool SPLIT = false>
-hipError_t launch_gemv(const WT* W, const GemvIn& in_, const Epi& epi, int units, hipStream_t s) {
+hipError_t launch_gemv(const WT* W, const GemvIn& in_, const Epi& epi_, int units, hipStream_t s) {
     if (!SPLIT && in_.csplit != 1) return hipErrorInvalidValue;  // a split needs the SPLIT instantiation
     GemvIn in = in_;
     const int grid = in.csplit == 1 ? gemv_balanced_blocks(units) : gemv_blocks(units, in.csplit);
     in.cw = in.csplit == 1 ? gemv_wave_count<WT>(units, grid) : kGemvThreads / 64;
     const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R, in.csplit);
-    hipLaunchKernelGGL((gemv_kernel<WT, R, U, NT, Epi, NB, SPLIT>), dim3(grid), dim3(kGemvThreads), lds, s, W, in,
-                       epi);
+    Epi epi = epi_;
+    epi_prepare(epi);
+    const GemvPart pt = gemv_part<WT, U>(in.cols, in.csplit, units, grid, in.cw);
+    hipLaunchKernelGGL((gemv_kernel<WT, R, U, NT, Epi, NB, SPLIT>), dim3(grid), dim3(kGemvThreads), lds, s, W, in.x,
+                       in.norm_w, in.cols, in.csplit, in.cw, pt.nunits, pt.cpp, pt.tw_m, pt.cw_m, pt.sh, in, epi);
     return hipGetLastError();
 }
 

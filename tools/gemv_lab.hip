@@ -3,7 +3,8 @@
 // inside a replayed hipGraph so no launch re-reads weights from the Infinity Cache. Prints µs per launch
 // and GB/s of algorithmic weight bytes, a pure streaming-read kernel as the per-shape ceiling, and the
 // 4-GEMV layer chain for chosen per-shape configurations.
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include tools/gemv_lab.hip -o tools/gemv_lab
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -amdgpu-kernarg-preload-count=14 -I include tools/gemv_lab.hip
+//         -o tools/gemv_lab      (one line; the preload flag as in simplellminference_amd/build.py)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#define SLI_GEMV_STAMPS 1  // per-wave stamps exist in the lab binaries only
 #include "../simplellminference_amd/csrc/gemv.h"
 
 using namespace sli;

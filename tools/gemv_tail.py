@@ -30,8 +30,11 @@ def main(path):
         ex = (st[:, :, 2] - t0) * 0.01
         steps = st[:, :, 3] & 0xFFFFFFFF
         xcd = (st[:, :, 3] >> 32) & 15
+        first = (st[:, :, 3] >> 36) * 0.01  # entry -> the first weight step issued
         pc = lambda a, q: float(np.percentile(a[live], q))
         name = NAMES[si % 100] + ("-i8" if si >= 100 else "")
+        print(f"{name:8s} R{r}: entry -> first weight request p10 {pc(first,10):5.2f} p50 {pc(first,50):5.2f} "
+              f"p90 {pc(first,90):5.2f} us")
         print(f"{name:8s} R{r}: entry p50 {pc(ent,50):5.2f} p99 {pc(ent,99):5.2f} max {pc(ent,100):5.2f} | "
               f"staged p50 {pc(stg,50):5.2f} p99 {pc(stg,99):5.2f} | exit p10 {pc(ex,10):5.2f} p50 {pc(ex,50):5.2f} "
               f"p90 {pc(ex,90):5.2f} p99 {pc(ex,99):5.2f} max {pc(ex,100):5.2f} us")
