@@ -193,6 +193,40 @@ int sli_embedding(int32_t token, const int32_t* token_dev, const void* table, in
 /* argmaxLayer::forward (source/op/argmax.cpp:7-17) on device: first index of the maximum. */
 int sli_argmax(const float* logits, int32_t n, int32_t* out_dev, sli_stream_t stream);
 
+/* Seeded temperature / top-k / top-p sampling (no reference counterpart: model.cpp:157-183 decodes greedily). The
+ * rule, for one row of fp32 logits l[0..V), the parameters below, a sequence id s and a position pos:
+ *  - Candidates. NaN and -inf logits are never candidates. If the row has no finite maximum (every logit NaN or -inf,
+ *    or a +inf present) the result is sli_argmax's for the row and nothing below applies.
+ *  - Top-k. top_k <= 0 or top_k >= V: off. Otherwise tau_k is the k-th largest logit counted with multiplicity (a NaN
+ *    counts as -inf) and C_k = {i : l_i >= tau_k}: ties at the boundary are all kept. The comparison is on the fp32
+ *    values, so -0 equals +0. The set is exact.
+ *  - Top-p over C_k. top_p = 1: off. Otherwise q_i = exp((l_i - m) / T) / Z with m the maximum and Z the sum over
+ *    C_k; tau_p is the largest logit value v with sum{q_i : i in C_k, l_i >= v} >= top_p, and C = {i in C_k :
+ *    l_i >= tau_p}: ties are kept. (Computed with fp32 exp and exact integer sums, csrc/sample.h: the set can differ
+ *    from an exact evaluation only where a cumulative mass lies within about 1e-5 of top_p.)
+ *  - The draw, Gumbel-max. h_i = sli_rng_u32(seed, (SLI_SAMPLE_STREAM << 16) | (s & 0xFFFF), ((uint64)pos << 32) | i)
+ *    (sli_synth.h); u_i = (2 (h_i >> 9) + 1) 2^-24, exact in fp32 and never 0 or 1; key_i = l_i / T - log(-log(u_i))
+ *    in fp32 (IEEE divide and subtract, the accurate logf). The token is the index of the largest key over C, the
+ *    first index among equal keys.
+ *  - The counter of the draw is the position, not a running count: the same (seed, s, pos, logits) always gives the
+ *    same token, bit for bit from run to run.
+ * temperature in [1e-2, 1e2], top_p in (0, 1], top_k >= 0; anything else (a NaN included) is SLI_ERR_ARG, decided
+ * before the device is touched. */
+typedef struct {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    uint32_t seed;
+} sli_sampling;
+enum { SLI_SAMPLE_STREAM = 12 }; /* the draw's stream kind, after sli_synth.h's tensor streams (1 .. 11) */
+
+/* One draw per row: out_dev[r] = the token of row r (logits + r * row_stride, `vocab` floats) drawn as sequence
+ * seq0 + r at position pos_dev[r * pos_stride]. The positions are read on the device, so the call is graph-capturable
+ * like sli_embedding. row_stride >= vocab, or 0: `rows` independent draws from one distribution. One launch of one
+ * workgroup per row, whose only scratch is LDS, so there is no workspace. `p` is a host pointer. pos_stride >= 0. */
+int sli_sample(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_sampling* p,
+               int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, int32_t* out_dev, sli_stream_t stream);
+
 /* ---------------------------------------------------------------- model level */
 typedef struct {
     int32_t vocab, dim, n_heads, n_kv_heads, head_dim, ffn, n_layers, max_len;
@@ -334,6 +368,23 @@ int sli_model_get_history(sli_model* m, int32_t seq, int32_t n, int32_t* out);
 enum { SLI_EXEC_LAUNCHES = 0, SLI_EXEC_PERSIST = 2 };
 int sli_model_set_exec(sli_model* m, int32_t mode);
 int sli_model_get_exec(sli_model* m, int32_t* mode);
+/* Sampling inside the step (the rule at sli_sample). p == NULL or p->temperature == 0: greedy, the default and the
+ * reference's behaviour. Otherwise every step draws one token per sequence from its logits, as sequence b (the row
+ * of the batch) at the position of the token just fed, between the LM head and the key reduce; past the prompt the
+ * drawn token is what the state feeds next and what the history records. Prompt tokens stay teacher-forced, and
+ * last_argmax goes on reporting the greedy argmax. The parameters live in device memory: changing them while
+ * sampling is on re-captures nothing; turning sampling on or off drops the step graph (as sli_model_set_exec does),
+ * and with sampling off the graph is the greedy one, node for node. Every weight and cache type, batch 1 .. 8, after
+ * sli_model_prefill too. SLI_ERR_STATE with the reason for tp_size > 1 and for the ranks of an in-process group
+ * (their logits are vocab-sharded) and under SLI_EXEC_PERSIST; sli_model_set_exec(SLI_EXEC_PERSIST) is refused the
+ * same way while sampling is on. Parameters out of range are SLI_ERR_ARG before the device is touched.
+ * sli_model_get_sampling: the parameters in force (temperature 0 while off).
+ * sli_model_get_sampled: the token sequence `seq` drew in the last step; -1 while sampling is off or before a step.
+ * sli_model_graph_captures: how many times the step graph has been captured since the model was created. */
+int sli_model_set_sampling(sli_model* m, const sli_sampling* p);
+int sli_model_get_sampling(sli_model* m, sli_sampling* out);
+int sli_model_get_sampled(sli_model* m, int32_t seq, int32_t* token);
+int sli_model_graph_captures(sli_model* m, int32_t* n);
 /* One decode step (hipGraph replay; captured on first use). Asynchronous on the model's stream. */
 int sli_model_step(sli_model* m);
 /* Host waits (sync, logits / state / history reads, predict, prefill, the timing probes) of a rank whose step

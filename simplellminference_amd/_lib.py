@@ -65,6 +65,10 @@ class BgemmEpilogue(ctypes.Structure):  # sli_bgemm_epilogue
                 ("logits", c_vp), ("keys_out", c_vp), ("vocab_off", c_i32), ("key_ld", c_i32)]
 
 
+class Sampling(ctypes.Structure):  # sli_sampling
+    _fields_ = [("temperature", c_f), ("top_k", c_i32), ("top_p", c_f), ("seed", c_u32)]
+
+
 class BgemmPlan(ctypes.Structure):  # sli_bgemm_plan
     _fields_ = [(n, c_i32) for n in ("tpw", "splits", "groups", "step_width", "lds_bytes")] + [("counter_off", c_i64)]
 
@@ -110,6 +114,7 @@ _SIGS = {
     "sli_add": (c_int, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "sli_embedding": (c_int, [c_i32, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "sli_argmax": (c_int, [c_vp, c_i32, c_vp, c_vp]),
+    "sli_sample": (c_int, [c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(Sampling), c_i32, c_vp, c_i32, c_vp, c_vp]),
     "sli_tp_plan": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(ShardWindow)]),
     "sli_tp_vocab": (c_int, [ctypes.POINTER(ModelConfig), P_i32, P_i32]),
     "sli_comm_id_bytes": (c_int, []),
@@ -135,6 +140,10 @@ _SIGS = {
     "sli_model_get_history": (c_int, [c_vp, c_i32, c_i32, c_vp]),
     "sli_model_set_exec": (c_int, [c_vp, c_i32]),
     "sli_model_get_exec": (c_int, [c_vp, P_i32]),
+    "sli_model_set_sampling": (c_int, [c_vp, ctypes.POINTER(Sampling)]),
+    "sli_model_get_sampling": (c_int, [c_vp, ctypes.POINTER(Sampling)]),
+    "sli_model_get_sampled": (c_int, [c_vp, c_i32, P_i32]),
+    "sli_model_graph_captures": (c_int, [c_vp, P_i32]),
     "sli_model_step": (c_int, [c_vp]),
     "sli_model_sync": (c_int, [c_vp]),
     "sli_model_get_logits": (c_int, [c_vp, c_vp, c_i32, P_i32]),

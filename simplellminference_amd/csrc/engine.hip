@@ -132,6 +132,12 @@ struct sli_model {
     char** os_peer_tab = nullptr;            // device copy of os_peer (oneshot.h EpiPush::peer_tab)
     size_t os_bytes = 0;
     int exec = SLI_EXEC_LAUNCHES;
+    // sampling inside the step (sli_model_set_sampling; sample.h): off = the greedy graph, node for node
+    bool sampling = false;
+    sli_sampling samp{};                // the parameters in force (temperature 0 while off)
+    sli_sampling* samp_dev = nullptr;   // their device copy, read by the sampler launch (no re-capture on a change)
+    int32_t* sampled = nullptr;         // [B] the token each sequence drew in the last step (-1: none)
+    int captures = 0;                   // step-graph captures so far (sli_model_graph_captures)
     // SLI_EXEC_PERSIST: the layer stack as one persistent launch (tp_layers.h); its granule arrays, weight table,
     // launch counter and the device table of every rank's exchange granules (in the one-shot comm buffers)
     struct Tl {
@@ -363,6 +369,19 @@ __global__ void __launch_bounds__(kKeyThreads) keyreduce_kernel(const unsigned l
 
 __global__ void finalize_kernel(DevState* st, const int32_t* __restrict__ prompt, int32_t* hist, int T) {
     finalize_state(st, prompt, hist, T);
+}
+
+// The state update of a sampling step, one thread per sequence: the argmax key (batch > 1: keys[b]; batch 1: already
+// in st->key) still names last_argmax, the token fed next past the prompt is the one the sampler drew.
+__global__ void finalize_sampled_kernel(DevState* st, const unsigned long long* __restrict__ keys,
+                                        const int32_t* __restrict__ sampled, const int32_t* __restrict__ prompt,
+                                        int32_t* hist, int T, int B) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    if (keys) st[b].key = keys[b];
+    st[b].last_argmax = (int)argmax_key_index(st[b].key);
+    st[b].key = 0;
+    advance_state(st + b, prompt + (size_t)b * (T + 1), hist + (size_t)b * (T + 1), T, sampled[b]);
 }
 
 // ---- batch > 1: one sequence per block / thread
@@ -1019,13 +1038,15 @@ struct StepRecorder {
         hipStream_t s = m->stream;
         if (m->B > 1) {
             SLI_TRY(b_lm(m));
+            SLI_TRY(record_sample(m));
             hipLaunchKernelGGL(keyreduce_batch_kernel, dim3(m->B), dim3(256), 0, s, m->keys, m->key_ld,
                                m->bp_lm.groups, m->bkeys);
             SLI_HIP(hipGetLastError());
             return SLI_OK;
         }
         SLI_TRY(gemv_lm(m));
-        if (exchange)
+        SLI_TRY(record_sample(m));
+        if (exchange || m->sampling)  // a sampling step updates the state in record_finalize
             hipLaunchKernelGGL(keyreduce_kernel<false>, dim3(1), dim3(kKeyThreads), 0, s, m->keys, lm_head_blocks(m),
                                m->st, m->prompt, m->hist, m->T);
         else
@@ -1034,10 +1055,20 @@ struct StepRecorder {
         SLI_HIP(hipGetLastError());
         return SLI_OK;
     }
+    // the draw of a sampling step (sample.h): row b of the logits as sequence b at the position just fed
+    static int record_sample(sli_model* m) {
+        if (!m->sampling) return SLI_OK;
+        SLI_HIP(launch_sample(m->logits, m->v_n, m->B, m->v_n, m->samp, m->samp_dev, 0, &m->st->pos, kPosStride,
+                              m->sampled, m->stream));
+        return SLI_OK;
+    }
     // state update after the (exchanged) argmax keys: position, next token, history (model.cpp:157-183)
     static int record_finalize(sli_model* m) {
         hipStream_t s = m->stream;
-        if (m->B > 1)
+        if (m->sampling)
+            hipLaunchKernelGGL(finalize_sampled_kernel, dim3(1), dim3(64), 0, s, m->st, m->B > 1 ? m->bkeys : nullptr,
+                               m->sampled, m->prompt, m->hist, m->T, m->B);
+        else if (m->B > 1)
             hipLaunchKernelGGL(finalize_batch_kernel, dim3(1), dim3(64), 0, s, m->st, m->bkeys, m->prompt, m->hist,
                                m->T, m->B);
         else
@@ -1067,7 +1098,7 @@ struct StepRecorder {
         }
         if (!m->collectives) {
             SLI_TRY(record_head(m, m->B > 1));
-            return m->B > 1 ? record_finalize(m) : SLI_OK;
+            return m->B > 1 || m->sampling ? record_finalize(m) : SLI_OK;
         }
         SLI_TRY(record_head(m, true));
         if (m->B > 1)
@@ -1334,6 +1365,7 @@ static int capture(sli_model* m) {
     if (m->comm_dead) return fail(SLI_ERR_COMM, "the RCCL communicator was aborted by an earlier bounded wait");
     SLI_TRY(bg_sync_tiles(m));
     if (m->exec == SLI_EXEC_PERSIST && !m->graph_exec) SLI_TRY(tpl_prepare(m));
+    if (!m->graph_exec) ++m->captures;
     return capture_graph(m->stream, m->graph, m->graph_exec, [&]() { return SLI_DISPATCH(m, record, m); });
 }
 
@@ -1392,6 +1424,16 @@ static int wait_event(sli_model* m, hipEvent_t e) {
         return SLI_OK;
     }
     return wait_bounded(m, [&] { return hipEventQuery(e); });
+}
+
+// the step graph is re-captured on the next step (after a change of what it records)
+static int drop_step_graph(sli_model* m) {
+    SLI_TRY(wait_stream(m));
+    if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
+    if (m->graph) (void)hipGraphDestroy(m->graph);
+    m->graph_exec = nullptr;
+    m->graph = nullptr;
+    return SLI_OK;
 }
 
 static int upload_states(sli_model* m, const std::vector<DevState>& h) {
@@ -1697,6 +1739,8 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     A((void**)&m->cos_t, sizeof(float) * (size_t)m->T * (hd / 2));
     A((void**)&m->keys, sizeof(unsigned long long) * B * m->key_ld);
     A((void**)&m->st, sizeof(DevState) * B);
+    A((void**)&m->samp_dev, sizeof(sli_sampling));
+    A((void**)&m->sampled, sizeof(int32_t) * B);
     A((void**)&m->prompt, sizeof(int32_t) * B * (m->T + 1));
     A((void**)&m->hist, sizeof(int32_t) * B * (m->T + 1));
     if (rc != SLI_OK) return bail(rc);
@@ -2114,16 +2158,65 @@ int sli_model_set_exec(sli_model* m, int32_t mode) {
     if (mode == SLI_EXEC_PERSIST) {
         std::string why;
         SLI_CHECK(tpl_check(m, &why), SLI_ERR_STATE, "persistent layers: " + why);
+        SLI_CHECK(!m->sampling, SLI_ERR_STATE,
+                  "persistent layers: not while sampling is on (sli_model_set_sampling(NULL) first)");
     }
     SLI_HIP(hipSetDevice(m->c.device));
     if (mode != m->exec) {  // re-capture the step graph on the next step
-        SLI_TRY(wait_stream(m));
-        if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
-        if (m->graph) (void)hipGraphDestroy(m->graph);
-        m->graph_exec = nullptr;
-        m->graph = nullptr;
+        SLI_TRY(drop_step_graph(m));
         m->exec = mode;
     }
+    return SLI_OK;
+}
+
+int sli_model_set_sampling(sli_model* m, const sli_sampling* p) {
+    SLI_CHECK(m, SLI_ERR_ARG, "null model");
+    const bool on = p && p->temperature != 0.0f;  // (a NaN temperature is "on" and fails the range check)
+    if (on) {
+        const char* why = sample_params_error(*p);
+        SLI_CHECK(!why, SLI_ERR_ARG, std::string("set_sampling: ") + (why ? why : ""));
+        SLI_CHECK(!m->group, SLI_ERR_STATE,
+                  "set_sampling: the ranks of an in-process tp group hold vocab shards of the logits (no distributed "
+                  "threshold yet)");
+        SLI_CHECK(m->c.tp_size <= 1, SLI_ERR_STATE,
+                  "set_sampling: tp_size > 1 shards the logits over the ranks (no distributed threshold yet)");
+        SLI_CHECK(m->exec != SLI_EXEC_PERSIST, SLI_ERR_STATE,
+                  "set_sampling: not under the persistent layers (sli_model_set_exec(SLI_EXEC_LAUNCHES) first)");
+    }
+    if (!on && !m->sampling) return SLI_OK;
+    SLI_HIP(hipSetDevice(m->c.device));
+    if (on != m->sampling) {  // the sampler launch joins or leaves the step graph
+        SLI_TRY(drop_step_graph(m));
+        SLI_HIP(hipMemsetAsync(m->sampled, 0xFF, sizeof(int32_t) * m->B, m->stream));
+        m->sampling = on;
+    }
+    m->samp = on ? *p : sli_sampling{};
+    if (on) {
+        SLI_HIP(hipMemcpyAsync(m->samp_dev, &m->samp, sizeof(sli_sampling), hipMemcpyHostToDevice, m->stream));
+        SLI_TRY(wait_stream(m));
+    }
+    return SLI_OK;
+}
+
+int sli_model_get_sampling(sli_model* m, sli_sampling* out) {
+    SLI_CHECK(m && out, SLI_ERR_ARG, "null argument");
+    *out = m->samp;
+    return SLI_OK;
+}
+
+int sli_model_get_sampled(sli_model* m, int32_t seq, int32_t* token) {
+    SLI_CHECK(m && token, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(seq >= 0 && seq < m->B, SLI_ERR_RANGE, "sequence index out of range");
+    *token = -1;
+    if (!m->sampling) return SLI_OK;
+    SLI_HIP(hipMemcpyAsync(token, m->sampled + seq, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+    SLI_TRY(wait_stream(m));
+    return SLI_OK;
+}
+
+int sli_model_graph_captures(sli_model* m, int32_t* n) {
+    SLI_CHECK(m && n, SLI_ERR_ARG, "null argument");
+    *n = m->captures;
     return SLI_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "gemv.h"
 #include "ops_internal.h"
 #include "rope_table.h"
+#include "sample.h"
 
 namespace sli {
 
@@ -683,6 +684,19 @@ int sli_argmax(const float* logits, int32_t n, int32_t* out_dev, sli_stream_t st
     SLI_CHECK(n > 0, SLI_ERR_SHAPE, "sli_argmax: n");
     hipLaunchKernelGGL(argmax_kernel, dim3(1), dim3(1024), 0, as_stream(stream), logits, n, out_dev);
     SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
+int sli_sample(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_sampling* p,
+               int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, int32_t* out_dev, sli_stream_t stream) {
+    SLI_CHECK(logits && p && pos_dev && out_dev, SLI_ERR_ARG, "sli_sample: null pointer");
+    SLI_CHECK(rows > 0 && vocab > 0, SLI_ERR_ARG, "sli_sample: rows and vocab must be positive");
+    SLI_CHECK(row_stride == 0 || row_stride >= vocab, SLI_ERR_ARG, "sli_sample: row_stride is 0 or at least vocab");
+    SLI_CHECK(pos_stride >= 0, SLI_ERR_ARG, "sli_sample: pos_stride < 0");
+    const char* why = sample_params_error(*p);
+    SLI_CHECK(!why, SLI_ERR_ARG, std::string("sli_sample: ") + (why ? why : ""));
+    SLI_HIP(launch_sample(logits, row_stride, rows, vocab, *p, nullptr, seq0, pos_dev, pos_stride, out_dev,
+                          as_stream(stream)));
     return SLI_OK;
 }
 

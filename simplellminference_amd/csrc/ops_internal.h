@@ -18,4 +18,11 @@ int attn_wg_positions(int kv_dtype, int head_dim);  // context positions per att
 int embedding_launch(int token, const int32_t* token_dev, const void* table, int dtype, const float* row_scale,
                      float* out, int vocab, int dim, hipStream_t s);
 
+// sample.h: the argument ranges of sli_sampling (null, or what is wrong), and one draw per row. pd != null: the
+// parameters are read from device memory when the kernel runs (pv is ignored).
+const char* sample_params_error(const sli_sampling& p);
+hipError_t launch_sample(const float* logits, long long row_stride, int rows, int V, const sli_sampling& pv,
+                         const sli_sampling* pd, int seq0, const int32_t* pos, int pos_stride, int32_t* out,
+                         hipStream_t s);
+
 }  // namespace sli

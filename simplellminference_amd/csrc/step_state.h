@@ -16,12 +16,9 @@ struct DevState {
     unsigned long long key;  // argmax key of the last step (0 between steps)
 };
 
-// model.cpp:157-183: next position; teacher-forced prompt token while inside the prompt, else greedy.
-__device__ __forceinline__ void finalize_state(DevState* st, const int32_t* prompt, int32_t* hist, int T) {
-    const unsigned long long k = st->key;
-    const int next = (int)argmax_key_index(k);
-    st->last_argmax = next;
-    st->key = 0;
+// model.cpp:157-183: next position; teacher-forced prompt token while inside the prompt, else `next` (the greedy
+// argmax, or the token a sampling step drew).
+__device__ __forceinline__ void advance_state(DevState* st, const int32_t* prompt, int32_t* hist, int T, int next) {
     if (st->advance) {
         const int p = st->pos + 1;
         if (p < T) {
@@ -30,6 +27,14 @@ __device__ __forceinline__ void finalize_state(DevState* st, const int32_t* prom
             hist[p] = st->token;
         }
     }
+}
+
+__device__ __forceinline__ void finalize_state(DevState* st, const int32_t* prompt, int32_t* hist, int T) {
+    const unsigned long long k = st->key;
+    const int next = (int)argmax_key_index(k);
+    st->last_argmax = next;
+    st->key = 0;
+    advance_state(st, prompt, hist, T, next);
 }
 
 }  // namespace sli

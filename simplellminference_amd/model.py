@@ -191,6 +191,39 @@ class LlamaModel:
         call("sli_model_get_exec", self._h, ctypes.byref(v))
         return {i: k for k, i in self.EXEC.items()}[v.value]
 
+    # ------------------------------------------------------------------ sampling (sli_model_set_sampling)
+    def set_sampling(self, temperature: float | None = None, top_k: int = 0, top_p: float = 1.0,
+                     seed: int = 0) -> "LlamaModel":
+        """Seeded temperature / top-k / top-p sampling inside the step (the rule: sli.h at sli_sample);
+        ``set_sampling(None)`` or temperature 0 goes back to greedy, the default. ``predict*`` follow the state: past
+        the prompt they feed what was drawn. Changing the parameters while sampling is on re-captures nothing."""
+        if temperature is None:
+            call("sli_model_set_sampling", self._h, None)
+        else:
+            prm = _lib.Sampling(temperature, top_k, top_p, seed & 0xFFFFFFFF)
+            call("sli_model_set_sampling", self._h, ctypes.byref(prm))
+        return self
+
+    def sampling(self) -> dict | None:
+        """The parameters in force, or None while decoding greedily."""
+        prm = _lib.Sampling()
+        call("sli_model_get_sampling", self._h, ctypes.byref(prm))
+        if prm.temperature == 0.0:
+            return None
+        return {"temperature": prm.temperature, "top_k": prm.top_k, "top_p": prm.top_p, "seed": prm.seed}
+
+    def sampled(self, seq: int = 0) -> int:
+        """The token sequence ``seq`` drew in the last step; -1 while sampling is off."""
+        v = ctypes.c_int32()
+        call("sli_model_get_sampled", self._h, seq, ctypes.byref(v))
+        return v.value
+
+    def graph_captures(self) -> int:
+        """How many times the step graph has been captured (sli_model_graph_captures)."""
+        v = ctypes.c_int32()
+        call("sli_model_graph_captures", self._h, ctypes.byref(v))
+        return v.value
+
     # ------------------------------------------------------------------ tensor-parallel all-reduce
     def comm_handle(self) -> bytes:
         """This rank's one-shot all-reduce buffer as an IPC handle (exchange it with the other ranks)."""

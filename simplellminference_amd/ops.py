@@ -506,3 +506,23 @@ def argmax(logits, out=None):
     _dev(logits, out)
     call("sli_argmax", _p(logits), logits.numel(), _p(out), _s())
     return out
+
+
+def sample(logits, temperature: float, top_k: int, top_p: float, seed: int, pos, seq0: int = 0, out=None):
+    """sli_sample: one seeded temperature / top-k / top-p draw per row (the rule: sli.h). logits [V] or [rows, V]
+    fp32, the rows ``logits.stride(0)`` floats apart (a row-padded view, or an ``expand``-ed row with stride 0: many
+    draws from one distribution). pos: int32 device tensor [rows] (spaced ``pos.stride(0)``), row r drawing as sequence
+    seq0 + r at position pos[r]. Returns the int32 tokens [rows]."""
+    if logits.dim() == 1:
+        logits = logits.unsqueeze(0)
+    rows, vocab = logits.shape
+    if not logits.is_cuda or logits.dtype != torch.float32 or (vocab > 1 and logits.stride(1) != 1):
+        raise ValueError("logits: fp32 device rows of contiguous elements")
+    if not pos.is_cuda or pos.dtype != torch.int32 or pos.dim() != 1 or pos.shape[0] < rows:
+        raise ValueError("pos: an int32 device tensor of one position per row")
+    out = torch.empty(rows, device=logits.device, dtype=torch.int32) if out is None else out
+    _dev(out)
+    prm = _lib.Sampling(temperature, top_k, top_p, seed & 0xFFFFFFFF)
+    call("sli_sample", _p(logits), logits.stride(0) if rows > 1 else vocab, rows, vocab, ctypes.byref(prm), seq0,
+         _p(pos), pos.stride(0) if rows > 1 else 1, _p(out), _s())
+    return out
