@@ -355,6 +355,44 @@ int sli_model_fused_qkv_attn(sli_model* m);
  * positions < n_prompt - 1 (not computed by the prefill) are NaN. */
 int sli_model_predict_prefill(sli_model* m, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                               int32_t* tokens_out, float* logits_out);
+/* Packed prompt prefill for batched models, and per-sequence admission.
+ *
+ * The packing rule (host only, no device is touched). Sequence seqs[i] with a prompt of lens[i] tokens contributes
+ * rows for its positions 0 .. lens[i]-2 (the last prompt token runs as an ordinary decode step), cut into groups of 16
+ * positions aligned on the sequence's own positions (p0 % 16 == 0), the last with nv = (lens[i]-1) % 16 valid rows, or
+ * 16 when that is zero; a length of 1 contributes nothing. The groups of the listed sequences are concatenated in list
+ * order, each sequence's in ascending position; chunks are consecutive runs of 16 groups (256 rows); the last chunk
+ * takes the smallest of 32 / 64 / 128 / 256 rows that holds its groups and is padded with groups of nv == 0, which
+ * compute and write nothing to the cache (they name the last real group's sequence at p0 = 0).
+ * groups receives the groups of all chunks, padding included (chunk c's start at 16 * c), chunk_rows each chunk's rows,
+ * *n_chunks their number. SLI_ERR_RANGE for a buffer that is too small and for lens[i] < 1. */
+typedef struct {
+    int32_t seq, p0, nv; /* 16 chunk rows: positions p0 .. p0+15 of sequence seq, the first nv valid */
+} sli_pf_group;
+int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, sli_pf_group* groups, int32_t cap_groups,
+                     int32_t* chunk_rows, int32_t cap_chunks, int32_t* n_chunks);
+/* Prefill the listed sequences (distinct, < batch; prompts [n_seqs][ld], lens[i] tokens of row i) of a model of any
+ * batch 1 .. 8 with their own prompts: chunks packed by the rule above run through the layers as the MFMA GEMMs of
+ * sli_model_prefill, the embedding, the q/k/v epilogue and the chunk attention reading a device-resident group table
+ * (prefill.h PfSegs) in place of one start position. Every other sequence's cache rows, state, prompt and history are
+ * untouched, so a finished sequence can be replaced inside a running batch. Afterwards sequence seqs[i] is at
+ * (token ids[n-1], position n-1, advancing, prompt = ids) and its history holds ids. Prompts are teacher-forced: the
+ * sampling state is not consulted. Takes fp16 / int8 / MXFP4 weights (MXFP4 at batch > 1: SLI_CREATE_MX_BATCH) with an
+ * fp16 or FP8 E4M3 cache, head_dim 64 / 128, projection depths that are multiples of 64, a single rank; it is not bound
+ * by sli_model_set_prefill, whose modes it ignores. SLI_ERR_STATE with the reason for fp32 weights, an fp32 cache,
+ * tp_size > 1, ranks of an in-process group and unsupported shapes (no fallback). Argument errors are decided before
+ * any state or device memory is touched: a duplicate or out-of-range sequence is SLI_ERR_ARG, a length outside
+ * [1, min(ld, max_len)] or a token outside the vocabulary SLI_ERR_RANGE. */
+int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                           const int32_t* lens, int32_t ld);
+int sli_model_prefill_seqs_ok(const sli_model* m); /* 1: the model takes sli_model_prefill_seqs */
+/* sli_model_predict_batch with every prompt prefilled (sli_model_prefill_seqs over all `batch` sequences), then
+ * max_length - min(lens) + 1 steps; sequence b waits at its last prompt position (idempotent steps) for the first
+ * lens[b] - min(lens) of them, so all sequences finish together at position max_length. max(lens) <= max_length <=
+ * max_len. tokens_out[b][t] as sli_model_predict_batch; logits_out [max_length][batch][local vocab] holds at (t, b) the
+ * logits of the step that fed position t, NaN for t < lens[b] - 1. */
+int sli_model_predict_batch_prefill(sli_model* m, const int32_t* prompts, const int32_t* lens, int32_t ld,
+                                    int32_t max_length, int32_t* tokens_out, float* logits_out);
 /* The tokens fed at positions [0, n) of sequence seq. */
 int sli_model_get_history(sli_model* m, int32_t seq, int32_t n, int32_t* out);
 /* Execution of the step: SLI_EXEC_LAUNCHES, one hipGraph of ~5 fused launches per layer (every configuration);
@@ -547,6 +585,28 @@ int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi,
 int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
                      int32_t rows_allocated, int32_t p0, int32_t hq, int32_t hkv, int32_t hd, int32_t T, void* state,
                      sli_stream_t stream);
+
+/* The same two stages under a group table (sli_model_prefill_seqs): groups is a host array of M / 16 entries, chunk
+ * rows 16 g .. 16 g + 15 being positions p0 .. p0 + 15 of sequence seq (p0 % 16 == 0, 0 <= p0 < T, 0 <= seq < B,
+ * 0 <= nv <= 16; nv == 0: a padding group); `table` is 192 bytes of device memory (4-byte aligned) that the call fills
+ * on the stream ahead of the launch (prefill.h PfSegs). kc / vc are one layer's cache of all B sequences,
+ * [B][hkv][T][hd], in SLI_DT_F16 or SLI_DT_F8E4M3 (an fp32 cache has no table form: SLI_ERR_ARG). The same pickers, so
+ * what runs here is what sli_model_prefill_seqs runs.
+ * sli_prefill_gemm_qkv_segs: the q/k/v GEMM (epi->role 0) with the table epilogue: q [M][hq * hd] gets every chunk
+ *   row, RoPE at p0 + r (clamped to T - 1); the K / V rows of group g go to sequence seq's cache at p0 + r for
+ *   r < nv and p0 + r < T only. _mxfp4: the MXFP4 twin (sli_prefill_gemm_mxfp4).
+ * sli_prefill_attn_segs: group g's 16 rows attend sequence seq's cache rows 0 .. p0 + r; the rows of a padding group
+ *   are left as they were. */
+int sli_prefill_gemm_qkv_segs(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo,
+                              int32_t N, int32_t K, int32_t M, const sli_pf_group* groups, int32_t B,
+                              const sli_pgemm_epilogue* epi, void* table, sli_pgemm_tiling* tiling, sli_stream_t stream);
+int sli_prefill_gemm_qkv_segs_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N,
+                                    int32_t K, int32_t M, const sli_pf_group* groups, int32_t B,
+                                    const sli_pgemm_epilogue* epi, void* table, sli_pgemm_tiling* tiling,
+                                    sli_stream_t stream);
+int sli_prefill_attn_segs(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
+                          const sli_pf_group* groups, int32_t B, int32_t hq, int32_t hkv, int32_t hd, int32_t T,
+                          void* table, sli_stream_t stream);
 
 /* ---------------------------------------------------------------- batched decode stages, for tests and labs
  * One projection launch of the batched decode step (csrc/bgemm.h bgemm_kernel, 2 .. 8 sequences in lockstep; B = 1

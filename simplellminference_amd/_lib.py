@@ -55,6 +55,10 @@ class PgemmEpilogue(ctypes.Structure):  # sli_pgemm_epilogue
                 ("y", c_vp), ("resid", c_vp), ("ld", c_i32)]
 
 
+class PfGroup(ctypes.Structure):  # sli_pf_group
+    _fields_ = [(n, c_i32) for n in ("seq", "p0", "nv")]
+
+
 class BgemmEpilogue(ctypes.Structure):  # sli_bgemm_epilogue
     _fields_ = [("role", c_i32),
                 ("q", c_vp), ("kc", c_vp), ("vc", c_vp), ("kv_dtype", c_i32), ("pos", c_vp), ("sin_t", c_vp),
@@ -168,6 +172,16 @@ _SIGS = {
                                  ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
     "sli_prefill_gemm_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
                                        ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_pack": (c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, P_i32]),
+    "sli_model_prefill_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32]),
+    "sli_model_prefill_seqs_ok": (c_int, [c_vp]),
+    "sli_model_predict_batch_prefill": (c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "sli_prefill_gemm_qkv_segs": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                          ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_gemm_qkv_segs_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                                ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_attn_segs": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                      c_i32, c_vp, c_vp]),
     "sli_model_set_prefill": (c_int, [c_vp, c_i32]),
     "sli_tp_group_set_prefill": (c_int, [c_vp, c_i32]),
     "sli_prefill_attn": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,

@@ -116,6 +116,11 @@ struct sli_model {
         sli::PfState* ps = nullptr;             // chunk start position + valid rows (device)
         hipGraph_t graph[4] = {};
         hipGraphExec_t exec[4] = {};
+        // sli_model_prefill_seqs: a chunk's rows are 16-row groups of several sequences; the group table (device) and
+        // the graphs of the table form, per chunk size
+        sli::PfSegs* segs = nullptr;
+        hipGraph_t sgraph[4] = {};
+        hipGraphExec_t sexec[4] = {};
         int mode = SLI_PREFILL_AUTO;  // sli_model_set_prefill
     } pf;
     // tensor-parallel all-reduce: SLI_ALLREDUCE_RCCL (ncclAllReduce) or SLI_ALLREDUCE_ONESHOT (oneshot.h)
@@ -1167,17 +1172,34 @@ struct StepRecorder {
     }
     static int prepare_prefill(sli_model* m) {
         SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
+        if constexpr (!std::is_same<KT, float>::value) SLI_TRY(allow_pg<PgEpiQKVSegs<KT>>(m));
         SLI_TRY(allow_pg<PgEpiResid>(m));
         SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
         return SLI_OK;
     }
+    // SEGS: the chunk's rows are 16-row groups of several sequences of a batched model (the table f.segs, prefill.h
+    // PfSegs; sli_model_prefill_seqs): the embedding, the q/k/v epilogue and the attention take the table and the
+    // cache's layer stride counts every sequence; the other launches are the same
+    template <bool SEGS = false>
     static int record_pf_phase(sli_model* m, int p, int M) {
+        if constexpr (SEGS && std::is_same<KT, float>::value) {
+            return fail(SLI_ERR_STATE, "prefill_seqs needs an fp16 or FP8 K/V cache");
+        } else {
+            return record_pf_phase_rm<SEGS>(m, p, M);
+        }
+    }
+    template <bool SEGS>
+    static int record_pf_phase_rm(sli_model* m, int p, int M) {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
         if (p == 0) {
-            hipLaunchKernelGGL(pf_embed_kernel<WT>, dim3(M), dim3(256), 0, s, f.ps, m->prompt, (const WT*)m->emb,
-                               (const void*)m->emb_s, f.x, D);
+            if constexpr (SEGS)
+                hipLaunchKernelGGL((pf_embed_kernel<WT, PfSegs>), dim3(M), dim3(256), 0, s, f.segs, m->prompt,
+                                   (const WT*)m->emb, (const void*)m->emb_s, f.x, D, m->T + 1);
+            else
+                hipLaunchKernelGGL((pf_embed_kernel<WT, PfState>), dim3(M), dim3(256), 0, s, f.ps, m->prompt,
+                                   (const WT*)m->emb, (const void*)m->emb_s, f.x, D, 0);
             SLI_HIP(hipGetLastError());
         }
         const int l = p / 2;
@@ -1190,13 +1212,20 @@ struct StepRecorder {
                            D, m->c.eps);
         SLI_HIP(hipGetLastError());
         if (p % 2 == 0) {
-            const size_t ls = (size_t)l * m->hkv * m->T * hd;
+            const size_t ls = (size_t)l * (SEGS ? m->B : 1) * m->hkv * m->T * hd;  // the cache is [L][B][hkv][T][hd]
             PgEpiQKV<KT> eq{f.q, (KT*)m->kc + ls, (KT*)m->vc + ls, rs(w.qkv_s), m->sin_t, m->cos_t, m->hq, m->hkv, hd,
                             m->T};
-            SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
             PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
                               1.0f / sqrtf((float)hd)};
-            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.ps, s));  // fp16 / FP8 cache: MFMA; fp32: VALU (prefill.h)
+            if constexpr (SEGS) {
+                SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, PgEpiQKVSegs<KT>{eq, f.segs},
+                           M, 0));
+                SLI_HIP(launch_pf_attn<KT>(aa, hd, M, (const PfSegs*)f.segs, s));
+            } else {
+                SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
+                // fp16 / FP8 cache: MFMA; fp32: VALU (prefill.h)
+                SLI_HIP(launch_pf_attn<KT>(aa, hd, M, (const PfState*)f.ps, s));
+            }
             er.rscale = rs(w.wo_s);
             return pg(m, w.wo, w.wo_s, D, QD, f.hhi, f.hlo, er, M, 2);
         }
@@ -1214,6 +1243,11 @@ struct StepRecorder {
             else if (m->partial)  // debug no-comm mode: keep the local partial as the residual stream
                 SLI_HIP(hipMemcpyAsync(m->pf.x, m->pf.xpart, sizeof(float) * n, hipMemcpyDeviceToDevice, m->stream));
         }
+        return SLI_OK;
+    }
+    // a chunk of sli_model_prefill_seqs (single-rank models: no exchange)
+    static int record_prefill_segs(sli_model* m, int M) {
+        for (int p = 0; p < 2 * m->L; ++p) SLI_TRY(record_pf_phase<true>(m, p, M));
         return SLI_OK;
     }
     static int record_group_prefill(sli_tp_group* g, int M) {
@@ -1488,6 +1522,8 @@ static void destroy(sli_model* m) {
     for (int b = 0; b < 4; ++b) {
         if (m->pf.exec[b]) (void)hipGraphExecDestroy(m->pf.exec[b]);
         if (m->pf.graph[b]) (void)hipGraphDestroy(m->pf.graph[b]);
+        if (m->pf.sexec[b]) (void)hipGraphExecDestroy(m->pf.sexec[b]);
+        if (m->pf.sgraph[b]) (void)hipGraphDestroy(m->pf.sgraph[b]);
     }
     if (m->comm) ncclCommDestroy(m->comm);
     for (int r = 0; r < sli::kOsMaxRanks; ++r)
@@ -1995,6 +2031,7 @@ static int pf_alloc(sli_model* m) {
     A((void**)&p.ahi, sizeof(__half) * M * m->Il);
     A((void**)&p.alo, sizeof(__half) * M * m->Il);
     A((void**)&p.ps, sizeof(PfState));
+    A((void**)&p.segs, sizeof(PfSegs));
     if (rc != SLI_OK) return rc;
     return SLI_DISPATCH(m, prepare_prefill, m);
 }
@@ -2111,6 +2148,164 @@ extern "C" int sli_model_predict_prefill(sli_model* m, const int32_t* prompt, in
         if (logits_out) SLI_TRY(sli_model_get_logits(m, logits_out + (size_t)t * per_step, (int32_t)per_step, nullptr));
     }
     SLI_HIP(hipMemcpyAsync(tokens_out, m->hist, sizeof(int32_t) * max_length, hipMemcpyDeviceToHost, m->stream));
+    SLI_TRY(wait_stream(m));
+    return check_device_errors(m);
+}
+
+// ---------------------------------------------------------------- packed prefill of a batched model's sequences
+// The packing rule (sli.h at sli_prefill_pack): each listed sequence's positions 0 .. n-2 cut into groups of 16
+// aligned on its own positions, the groups concatenated in list order, 16 groups (kPfMaxChunk rows) to a chunk, the
+// last chunk the smallest of kPfSizes that holds its groups, padded with nv == 0 groups. A padding group names the
+// sequence of the last real group at position 0: the rows' tokens and RoPE positions stay in range.
+struct PfPlan {
+    std::vector<sli_pf_group> groups;  // of all chunks, padding included
+    std::vector<int32_t> rows;         // per chunk
+};
+static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
+    PfPlan pl;
+    for (int i = 0; i < n_seqs; ++i)
+        for (int p0 = 0; p0 < lens[i] - 1; p0 += 16)
+            pl.groups.push_back(sli_pf_group{seqs[i], p0, std::min(16, lens[i] - 1 - p0)});
+    const int ng = (int)pl.groups.size();
+    for (int g0 = 0; g0 < ng; g0 += kPfGroups) {
+        const int rows = kPfSizes[pf_bucket(16 * std::min(kPfGroups, ng - g0))];
+        pl.rows.push_back(rows);
+    }
+    if (ng) {
+        const int total = (ng - 1) / kPfGroups * kPfGroups + pl.rows.back() / 16;
+        const int32_t pad_seq = pl.groups.back().seq;
+        pl.groups.resize(total, sli_pf_group{pad_seq, 0, 0});
+    }
+    return pl;
+}
+
+extern "C" int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, sli_pf_group* groups,
+                                int32_t cap_groups, int32_t* chunk_rows, int32_t cap_chunks, int32_t* n_chunks) {
+    SLI_CHECK(seqs && lens && n_chunks && (groups || cap_groups == 0) && (chunk_rows || cap_chunks == 0), SLI_ERR_ARG,
+              "sli_prefill_pack: null argument");
+    SLI_CHECK(n_seqs >= 0 && cap_groups >= 0 && cap_chunks >= 0, SLI_ERR_ARG, "sli_prefill_pack: negative count");
+    for (int i = 0; i < n_seqs; ++i) SLI_CHECK(lens[i] >= 1, SLI_ERR_RANGE, "sli_prefill_pack: a length below 1");
+    const PfPlan pl = pf_pack(seqs, lens, n_seqs);
+    SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
+              "sli_prefill_pack: the group or chunk buffer is too small");
+    std::copy(pl.groups.begin(), pl.groups.end(), groups);
+    std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
+    *n_chunks = (int32_t)pl.rows.size();
+    return SLI_OK;
+}
+
+// Why this model cannot take sli_model_prefill_seqs (null: it can). Not bound by sli_model_set_prefill's modes: an FP8
+// cache and MXFP4 weights qualify as they are.
+static const char* pf_seqs_why(const sli_model* m) {
+    if (m->group) return "prefill_seqs: not for the ranks of an in-process tp group";
+    if (m->c.tp_size > 1 || m->partial) return "prefill_seqs: single-rank models (no tensor parallelism)";
+    if (m->c.w_dtype == SLI_DT_F32) return "prefill_seqs: fp32 weights have no GEMM prefill";
+    if (m->c.kv_dtype == SLI_DT_F32) return "prefill_seqs: an fp32 K/V cache has no group-table attention";
+    if (!((m->hd == 64 || m->hd == 128) && m->D % 64 == 0 && m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0))
+        return "prefill_seqs: head_dim must be 64 / 128 and the projection depths multiples of 64 (dim <= 8192)";
+    return nullptr;
+}
+
+extern "C" int sli_model_prefill_seqs_ok(const sli_model* m) { return m && !pf_seqs_why(m) ? 1 : 0; }
+
+extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                                      const int32_t* lens, int32_t ld) {
+    SLI_CHECK(m && seqs && prompts && lens, SLI_ERR_ARG, "null argument");
+    if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    // every argument is judged before any state or device memory is touched
+    SLI_CHECK(n_seqs >= 1 && n_seqs <= m->B, SLI_ERR_ARG, "prefill_seqs: n_seqs must be in [1, batch]");
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(seqs[i] >= 0 && seqs[i] < m->B, SLI_ERR_ARG, "prefill_seqs: sequence index out of range");
+        for (int j = 0; j < i; ++j) SLI_CHECK(seqs[j] != seqs[i], SLI_ERR_ARG, "prefill_seqs: a sequence is listed twice");
+    }
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(lens[i] >= 1 && lens[i] <= std::min(ld, m->T), SLI_ERR_RANGE, "prompt length out of range");
+        for (int t = 0; t < lens[i]; ++t) {
+            const int32_t id = prompts[(size_t)i * ld + t];
+            SLI_CHECK(id >= 0 && id < m->V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
+        }
+    }
+    SLI_HIP(hipSetDevice(m->c.device));
+    for (int i = 0; i < n_seqs; ++i) {
+        const int32_t* ids = prompts + (size_t)i * ld;
+        SLI_TRY(set_prompt(m, seqs[i], ids, lens[i]));
+        SLI_HIP(hipMemcpyAsync(m->hist + (size_t)seqs[i] * (m->T + 1), ids, sizeof(int32_t) * lens[i],
+                               hipMemcpyHostToDevice, m->stream));
+    }
+    const PfPlan pl = pf_pack(seqs, lens, n_seqs);
+    if (!pl.rows.empty()) {
+        SLI_TRY(pf_alloc(m));
+        for (int rows : pl.rows) {  // capture before anything is enqueued behind the capture
+            const int b = pf_bucket(rows);
+            SLI_TRY(capture_graph(m->stream, m->pf.sgraph[b], m->pf.sexec[b],
+                                  [&]() { return SLI_DISPATCH(m, record_prefill_segs, m, kPfSizes[b]); }));
+        }
+        // each chunk's table (the groups it lacks: padding) and its graph, enqueued back to back
+        std::vector<PfSegs> tabs(pl.rows.size());
+        for (size_t c = 0; c < pl.rows.size(); ++c) {
+            const int pad_seq = pl.groups.back().seq;
+            for (int g = 0; g < kPfGroups; ++g) {
+                const size_t i = c * kPfGroups + g;
+                const sli_pf_group gr = i < pl.groups.size() ? pl.groups[i] : sli_pf_group{pad_seq, 0, 0};
+                tabs[c].seq[g] = gr.seq;
+                tabs[c].p0[g] = gr.p0;
+                tabs[c].nv[g] = gr.nv;
+            }
+        }
+        for (size_t c = 0; c < pl.rows.size(); ++c) {
+            SLI_HIP(hipMemcpyAsync(m->pf.segs, &tabs[c], sizeof(PfSegs), hipMemcpyHostToDevice, m->stream));
+            SLI_HIP(hipGraphLaunch(m->pf.sexec[pf_bucket(pl.rows[c])], m->stream));
+        }
+        SLI_TRY(wait_stream(m));
+    }
+    // each sequence's last prompt position is an ordinary decode step
+    for (int i = 0; i < n_seqs; ++i)
+        SLI_TRY(set_state(m, seqs[i], prompts[(size_t)i * ld + lens[i] - 1], lens[i] - 1, 1));
+    return SLI_OK;
+}
+
+extern "C" int sli_model_predict_batch_prefill(sli_model* m, const int32_t* prompts, const int32_t* lens, int32_t ld,
+                                               int32_t max_length, int32_t* tokens_out, float* logits_out) {
+    SLI_CHECK(m && prompts && lens && tokens_out, SLI_ERR_ARG, "null argument");
+    if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    const int B = m->B;
+    int lo = INT32_MAX, hi = 0;
+    for (int b = 0; b < B; ++b) {
+        lo = std::min(lo, lens[b]);
+        hi = std::max(hi, lens[b]);
+    }
+    SLI_CHECK(lo >= 1, SLI_ERR_RANGE, "prompt length out of range");
+    SLI_CHECK(max_length >= hi && max_length <= m->T, SLI_ERR_RANGE,
+              "max_length must be in [the longest prompt, max_len]");
+    std::vector<int32_t> seqs(B);
+    for (int b = 0; b < B; ++b) seqs[b] = b;
+    SLI_TRY(sli_model_prefill_seqs(m, seqs.data(), B, prompts, lens, ld));
+    // sequence b waits at its last prompt position (idempotent steps) until the shortest prompt has caught up: all
+    // sequences reach position max_length together, the final state of sli_model_predict_batch
+    for (int b = 0; b < B; ++b)
+        if (lens[b] > lo) SLI_TRY(set_state(m, b, prompts[(size_t)b * ld + lens[b] - 1], lens[b] - 1, 0));
+    const size_t vn = (size_t)m->v_n;
+    std::vector<float> step_logits(logits_out ? (size_t)B * vn : 0);
+    if (logits_out)  // positions the prefill computes no logits for
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < lens[b] - 1; ++t) std::fill_n(logits_out + ((size_t)t * B + b) * vn, vn, NAN);
+    const int steps = max_length - lo + 1;
+    for (int k = 0; k < steps; ++k) {
+        for (int b = 0; b < B; ++b)
+            if (lens[b] > lo && k == lens[b] - lo)
+                SLI_TRY(set_state(m, b, prompts[(size_t)b * ld + lens[b] - 1], lens[b] - 1, 1));
+        SLI_TRY(sli_model_step(m));
+        if (logits_out) {
+            SLI_TRY(sli_model_get_logits(m, step_logits.data(), (int32_t)step_logits.size(), nullptr));
+            for (int b = 0; b < B; ++b) {  // the position this step fed for sequence b
+                const int t = lens[b] - 1 + std::max(0, k - (lens[b] - lo));
+                std::copy_n(step_logits.data() + (size_t)b * vn, vn, logits_out + ((size_t)t * B + b) * vn);
+            }
+        }
+    }
+    for (int b = 0; b < B; ++b)
+        SLI_HIP(hipMemcpyAsync(tokens_out + (size_t)b * max_length, m->hist + (size_t)b * (m->T + 1),
+                               sizeof(int32_t) * max_length, hipMemcpyDeviceToHost, m->stream));
     SLI_TRY(wait_stream(m));
     return check_device_errors(m);
 }

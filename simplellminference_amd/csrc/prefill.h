@@ -29,6 +29,9 @@
 // applied to each k-block's tile in fp32 (PgMx).
 // The chunk's start position and valid count live in device memory (PfState), so one captured graph per
 // chunk size serves every chunk of every prompt.
+// A batched model's chunk carries 16-row groups of several sequences instead (PfSegs, a device-resident group table:
+// sli_model_prefill_seqs). The kernels that know a row's position (embedding, q/k/v epilogue, MFMA chunk attention) are
+// parameterised on that row map, PfState or PfSegs; everything else sees independent chunk rows either way.
 #pragma once
 #include <type_traits>
 
@@ -46,16 +49,38 @@ struct PfState {
     int32_t nv;  // valid chunk rows (the rest is padding: computed, never written to the cache)
 };
 
+// The row map of a packed chunk: chunk rows 16 g .. 16 g + 15 are positions p0[g] .. p0[g] + 15 of sequence seq[g]
+// (p0 % 16 == 0: a row keeps the 15 group-mates it has in a PfState chunk, so its attention tiles are the same), the
+// first nv[g] of them valid; nv[g] == 0 is a padding group, which writes nothing to the cache and skips its attention.
+constexpr int kPfGroups = kPfMaxChunk / 16;
+struct PfSegs {
+    int32_t seq[kPfGroups], p0[kPfGroups], nv[kPfGroups];
+};
+
+// group g of a chunk under either row map: its sequence, first position and valid rows (PfState: nv may be <= 0 or
+// > 16, only row < nv is asked of it)
+struct PfGrp {
+    int seq, p0, nv;
+};
+__device__ __forceinline__ PfGrp pf_grp(const PfState* ps, int g) { return PfGrp{0, ps->p0 + 16 * g, ps->nv - 16 * g}; }
+__device__ __forceinline__ PfGrp pf_grp(const PfSegs* ps, int g) { return PfGrp{ps->seq[g], ps->p0[g], ps->nv[g]}; }
+// where chunk row m's token lies in the prompt buffer ([sequence][pld]); padding rows repeat the last valid token
+__device__ __forceinline__ int pf_tok(const PfState* ps, int m, int) { return ps->p0 + min(m, ps->nv - 1); }
+__device__ __forceinline__ int pf_tok(const PfSegs* ps, int m, int pld) {
+    const int g = m >> 4;
+    return ps->seq[g] * pld + ps->p0[g] + min(m & 15, max(ps->nv[g] - 1, 0));
+}
+
 // ---------------------------------------------------------------- 1. embedding + RMSNorm / split
 // x[m] = emb[prompt[p0 + m]] (emb_kernel.cpp:4-21; padding rows repeat the last valid token). emb_s: the int8 table's
 // fp32 row scales (nullable), or the MXFP4 table's block scale bytes (mxfp4.h layout: a table decode per element)
-template <typename WT>
-__global__ void __launch_bounds__(256) pf_embed_kernel(const PfState* __restrict__ ps, const int32_t* __restrict__ prompt,
+// RM: the row map (PfState, or PfSegs: row m's token comes from its sequence's prompt row, pld ids apart).
+template <typename WT, class RM>
+__global__ void __launch_bounds__(256) pf_embed_kernel(const RM* __restrict__ ps, const int32_t* __restrict__ prompt,
                                                       const WT* __restrict__ emb, const void* __restrict__ emb_s,
-                                                      float* __restrict__ x, int D) {
+                                                      float* __restrict__ x, int D, int pld) {
     const int m = blockIdx.x;
-    const int nv = ps->nv;
-    const int tok = prompt[ps->p0 + min(m, nv - 1)];
+    const int tok = prompt[pf_tok(ps, m, pld)];
     if constexpr (is_mx<WT>::value) {
         const uint8_t *data = reinterpret_cast<const uint8_t*>(emb), *sc = static_cast<const uint8_t*>(emb_s);
         for (int i = threadIdx.x; i < D; i += 256) x[(size_t)m * D + i] = mx_element(data, sc, (size_t)tok, D, i);
@@ -532,8 +557,12 @@ struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows o
         return uh * hd + d + ((i & 2) ? half : 0);
     }
     __device__ void store(int t, int i0, int m, const float* v, const PfState* ps) const {
+        store_at(t, i0, m, v, ps->p0 + m, m < ps->nv, 0);
+    }
+    // pos: chunk row m's position; valid: its K / V rows are written (where pos < T); kv0: its sequence's offset in
+    // kc / vc (elements)
+    __device__ void store_at(int t, int i0, int m, const float* v, int pos, bool valid, size_t kv0) const {
         // units u, u + 1 (u even): d, d + 1 of one head (hd / 2 is even), so every store is a pair
-        const int nv = ps->nv, pos = ps->p0 + m;
         const int half = hd >> 1;
         const int u = t * 8 + (i0 >> 2) * 2;
         const int uh = u / half, d = u - uh * half;
@@ -558,13 +587,13 @@ struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows o
                 float* qr = q + (size_t)m * hq * hd + (size_t)uh * hd;
                 *reinterpret_cast<float2*>(qr + d) = make_float2(r0[0], r0[1]);
                 *reinterpret_cast<float2*>(qr + d + half) = make_float2(r1[0], r1[1]);
-            } else if (m < nv && pos < T) {
-                KT* kr = kc + ((size_t)(uh - hq) * T + pos) * hd;
+            } else if (valid && pos < T) {
+                KT* kr = kc + kv0 + ((size_t)(uh - hq) * T + pos) * hd;
                 store2(kr + d, r0);
                 store2(kr + d + half, r1);
             }
-        } else if (m < nv && pos < T) {
-            KT* vr = vc + ((size_t)(uh - hq - hkv) * T + pos) * hd;
+        } else if (valid && pos < T) {
+            KT* vr = vc + kv0 + ((size_t)(uh - hq - hkv) * T + pos) * hd;
             store2(vr + d, a0);
             store2(vr + d + half, a1);
         }
@@ -579,6 +608,20 @@ struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows o
         } else {
             *reinterpret_cast<float2*>(p) = make_float2(f[0], f[1]);
         }
+    }
+};
+
+// The q/k/v epilogue under the group table: kc / vc are one layer's cache of every sequence, [B][hkv][T][hd]; chunk row
+// m = 16 g + r is position p0[g] + r of sequence seq[g], written for r < nv[g]. The table travels with the epilogue
+// (pgemm_kernel's PfState argument is not read).
+template <typename KT>
+struct PgEpiQKVSegs {
+    PgEpiQKV<KT> e;
+    const PfSegs* segs;
+    __device__ int row(int t, int i) const { return e.row(t, i); }
+    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
+        const int g = m >> 4, r = m & 15;
+        e.store_at(t, i0, m, v, segs->p0[g] + r, r < segs->nv[g], (size_t)segs->seq[g] * e.hkv * e.T * e.hd);
     }
 };
 
@@ -811,8 +854,10 @@ struct PaGeo {
     static_assert(PIECES >= 2 && PIECES % 2 == 0 && 1024 % ROWB == 0, "whole 1-KiB pieces per K and per V image");
 };
 
-template <class F, int HD>
-__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F::KT> a, const PfState* __restrict__ ps) {
+// RM: the row map. PfState: workgroup x is rows 16 x .. of the chunk's one sequence. PfSegs: it is group x of the
+// table, kc / vc hold every sequence's rows ([B][hkv][T][hd]) and a padding group leaves at once, as a whole.
+template <class F, int HD, class RM>
+__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F::KT> a, const RM* __restrict__ ps) {
     using G = PaGeo<F, HD>;
     using KT = typename F::KT;
     constexpr int ND = HD / 32, NT = G::NT;  // 32-d blocks (S), 16-d tiles (O)
@@ -821,10 +866,12 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int g = lane >> 4, i16 = lane & 15;
     const int h = blockIdx.y, kvh = h / (a.hq / a.hkv);
-    const int p0 = ps->p0;
+    const PfGrp gr = pf_grp(ps, (int)blockIdx.x);
+    // (uniform: one table entry per workgroup; ahead of every barrier and DMA)
+    if (std::is_same<RM, PfSegs>::value && gr.nv == 0) return;
     const int mq = blockIdx.x * 16 + i16;  // this lane's query (chunk row)
-    const int pos = p0 + mq;
-    const int last = min(p0 + blockIdx.x * 16 + 15, a.T - 1);  // the group's last query position
+    const int pos = gr.p0 + i16;
+    const int last = min(gr.p0 + 15, a.T - 1);  // the group's last query position
     const int ntiles = last / 32 + 1;
     const size_t qs = (size_t)a.hq * HD;
     // Qᵀ as the B operand: lane l = query l & 15, d = 32 db + 8 g .. +8, fp32 -> hi + lo
@@ -847,8 +894,8 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
     char* kimg = sm + wave * G::WAVE;
     const unsigned kbase = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)kimg;
     const unsigned vbase = kbase + G::IMG;
-    const KT* kc = a.kc + (size_t)kvh * a.T * HD;
-    const KT* vc = a.vc + (size_t)kvh * a.T * HD;
+    const KT* kc = a.kc + ((size_t)gr.seq * a.hkv + kvh) * a.T * HD;
+    const KT* vc = a.vc + ((size_t)gr.seq * a.hkv + kvh) * a.T * HD;
     for (int tt = wave; tt < ntiles; tt += 4) {
         const int t0 = tt * 32;
         // K pieces 0 .. P/2-1, V pieces P/2 .. P-1; lane i of a piece: row (piece rows) + i / CPR, physical
@@ -962,18 +1009,20 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
 // The attention of M chunk rows (hd 64 or 128: the caller's check): an fp16 or FP8 cache on MFMA, 16 chunk rows per
 // workgroup; an fp32 cache on the VALU kernel, 64 chunk rows per workgroup, so at M = 32 it reads q and writes
 // ohi / olo for rows 32 .. 63 too (the buffers hold at least 64 rows). The engine and sli_prefill_attn launch
-// through here.
+// through here. Under a group table (PfSegs) the MFMA kernel alone.
 constexpr int pf_attn_rows(bool mfma_cache, int M) { return mfma_cache ? M : (M + kPaQB - 1) / kPaQB * kPaQB; }
 
-template <typename KT>
-hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const PfState* ps, hipStream_t s) {
+template <typename KT, class RM>
+hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const RM* ps, hipStream_t s) {
     if constexpr (!std::is_same<KT, float>::value) {
         using F = std::conditional_t<std::is_same<KT, f8e4m3>::value, AmF8, AmF16>;
         const dim3 ag(M / 16, aa.hq);
         if (hd == 128)
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 128>), ag, dim3(256), 0, s, aa, ps);
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 128, RM>), ag, dim3(256), 0, s, aa, ps);
         else
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 64>), ag, dim3(256), 0, s, aa, ps);
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 64, RM>), ag, dim3(256), 0, s, aa, ps);
+    } else if constexpr (!std::is_same<RM, PfState>::value) {
+        return hipErrorInvalidValue;  // the fp32-cache kernel has no group table (its callers refuse first)
     } else {
         const dim3 ag((M + kPaQB - 1) / kPaQB, aa.hq);
         if (hd == 128)

@@ -24,6 +24,31 @@ static int pf_set_state(void* state, int p0, int nv, hipStream_t s) {
     return SLI_OK;
 }
 
+// the group table of a packed chunk (prefill.h PfSegs), written on the stream: one dword per thread
+__global__ void pf_set_segs_kernel(PfSegs* dst, PfSegs v) {
+    reinterpret_cast<int32_t*>(dst)[threadIdx.x] = reinterpret_cast<const int32_t*>(&v)[threadIdx.x];
+}
+
+// groups: M / 16 host entries; the table's other entries are padding groups
+static int pf_set_segs(void* table, const sli_pf_group* groups, int M, int B, int T, hipStream_t s) {
+    SLI_CHECK(groups && table && (uintptr_t)table % 4 == 0, SLI_ERR_ARG, "prefill segs: null or misaligned group table");
+    SLI_CHECK(B >= 1 && T >= 1, SLI_ERR_ARG, "prefill segs: B and T must be positive");
+    PfSegs v{};
+    for (int g = 0; g < M / 16; ++g) {
+        const sli_pf_group& gr = groups[g];
+        SLI_CHECK(gr.seq >= 0 && gr.seq < B, SLI_ERR_ARG, "prefill segs: a group's sequence must be in [0, B)");
+        SLI_CHECK(gr.p0 >= 0 && gr.p0 < T && gr.p0 % 16 == 0, SLI_ERR_ARG,
+                  "prefill segs: a group's p0 must be a multiple of 16 in [0, T)");
+        SLI_CHECK(gr.nv >= 0 && gr.nv <= 16, SLI_ERR_ARG, "prefill segs: a group's nv must be in [0, 16]");
+        v.seq[g] = gr.seq;
+        v.p0[g] = gr.p0;
+        v.nv[g] = gr.nv;
+    }
+    hipLaunchKernelGGL(pf_set_segs_kernel, dim3(1), dim3(sizeof(PfSegs) / 4), 0, s, (PfSegs*)table, v);
+    SLI_HIP(hipGetLastError());
+    return SLI_OK;
+}
+
 static bool pf_chunk_size(int M) {
     for (int s : kPfSizes)
         if (M == s) return true;
@@ -73,6 +98,21 @@ static int pf_gemm_role(const void* w, const float* rs_in, const void* hi, const
     return pf_gemm_launch<PgEpiResid, WT>(w, ws, hi, lo, N, K, M, 2, r, ps, tiling, s);
 }
 
+// the q/k/v GEMM under a group table (sli_prefill_gemm_qkv_segs): rs_in as pf_gemm_role
+template <typename WT>
+static int pf_gemm_qkv_segs_launch(const void* w, const float* rs_in, const void* hi, const void* lo, int N, int K, int M,
+                                   const sli_pgemm_epilogue& e, const PfSegs* segs, sli_pgemm_tiling* tiling,
+                                   hipStream_t s) {
+    const void* ws = is_mx<WT>::value ? (const void*)rs_in : nullptr;
+    const float* rs = is_mx<WT>::value ? nullptr : rs_in;
+    if (e.kv_dtype == SLI_DT_F8E4M3) {
+        const PgEpiQKVSegs<f8e4m3> q{{e.q, (f8e4m3*)e.kc, (f8e4m3*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T}, segs};
+        return pf_gemm_launch<PgEpiQKVSegs<f8e4m3>, WT>(w, ws, hi, lo, N, K, M, 0, q, nullptr, tiling, s);
+    }
+    const PgEpiQKVSegs<__half> q{{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T}, segs};
+    return pf_gemm_launch<PgEpiQKVSegs<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, nullptr, tiling, s);
+}
+
 }  // namespace sli
 
 using namespace sli;
@@ -92,18 +132,16 @@ int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, i
     return SLI_OK;
 }
 
-// the checks of both GEMM entries and the launch; ws: mxfp4 block scales (w_dtype SLI_DT_MXFP4) or int8 row scales
-static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
-                         int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
-                         sli_pgemm_tiling* tiling, sli_stream_t stream) {
+// the checks every GEMM entry shares (the PfState and the group-table forms); ws: mxfp4 block scales (w_dtype
+// SLI_DT_MXFP4) or int8 row scales
+static int pf_gemm_check(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
+                         int32_t M, const sli_pgemm_epilogue* epi) {
     SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_gemm: M must be 32, 64, 128 or 256");
     SLI_CHECK(K >= 64 && K % 64 == 0, SLI_ERR_ARG, "sli_prefill_gemm: K must be a multiple of 64");
     SLI_CHECK(N >= 16 && N % 16 == 0, SLI_ERR_ARG, "sli_prefill_gemm: N must be a multiple of 16");
     SLI_CHECK((int64_t)N * K < ((int64_t)1 << 40) && K <= (1 << 20), SLI_ERR_ARG, "sli_prefill_gemm: shape too large");
-    SLI_CHECK(p0 >= 0 && p0 <= (1 << 30) && nv >= 1 && nv <= M, SLI_ERR_ARG,
-              "sli_prefill_gemm: p0 must be >= 0 and nv in [1, M]");
-    SLI_CHECK(al16(w) && (w_dtype == SLI_DT_MXFP4 || al16(ws)) && al16(hi) && al16(lo) && (uintptr_t)state % 8 == 0,
-              SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
+    SLI_CHECK(al16(w) && (w_dtype == SLI_DT_MXFP4 || al16(ws)) && al16(hi) && al16(lo), SLI_ERR_ARG,
+              "sli_prefill_gemm: 16-byte alignment");
     const sli_pgemm_epilogue& e = *epi;
     switch (e.role) {
         case 0:
@@ -132,6 +170,18 @@ static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void*
             break;
         default: return fail(SLI_ERR_ARG, "sli_prefill_gemm: role must be 0 (qkv), 1 (gate/up) or 2 (wo/down)");
     }
+    return SLI_OK;
+}
+
+// the checks of both PfState GEMM entries and the launch
+static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
+                         int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                         sli_pgemm_tiling* tiling, sli_stream_t stream) {
+    if (int rc = pf_gemm_check(w, w_dtype, ws, hi, lo, N, K, M, epi)) return rc;
+    SLI_CHECK(p0 >= 0 && p0 <= (1 << 30) && nv >= 1 && nv <= M, SLI_ERR_ARG,
+              "sli_prefill_gemm: p0 must be >= 0 and nv in [1, M]");
+    SLI_CHECK((uintptr_t)state % 8 == 0, SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
+    const sli_pgemm_epilogue& e = *epi;
     hipStream_t s = as_stream(stream);
     if (int rc = pf_set_state(state, p0, nv, s)) return rc;
     const PfState* ps = (const PfState*)state;
@@ -185,6 +235,67 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
     } else {
         const PfAttnArgs<float> aa{q, (const float*)kc, (const float*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
         SLI_HIP(launch_pf_attn<float>(aa, hd, M, ps, s));
+    }
+    return SLI_OK;
+}
+
+// ---- the group-table forms (sli_model_prefill_seqs)
+static int pf_gemm_qkv_segs_entry(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N,
+                                  int32_t K, int32_t M, const sli_pf_group* groups, int32_t B,
+                                  const sli_pgemm_epilogue* epi, void* table, sli_pgemm_tiling* tiling,
+                                  sli_stream_t stream) {
+    SLI_CHECK(epi->role == 0, SLI_ERR_ARG, "sli_prefill_gemm_qkv_segs: the q/k/v epilogue (role 0) only");
+    if (int rc = pf_gemm_check(w, w_dtype, ws, hi, lo, N, K, M, epi)) return rc;
+    SLI_CHECK(epi->kv_dtype != SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_gemm_qkv_segs: an fp16 or FP8 cache (fp32 has no table form)");
+    hipStream_t s = as_stream(stream);
+    if (int rc = pf_set_segs(table, groups, M, B, epi->T, s)) return rc;
+    const PfSegs* segs = (const PfSegs*)table;
+    const float* rs = (const float*)ws;
+    if (w_dtype == SLI_DT_MXFP4) return pf_gemm_qkv_segs_launch<mxfp4>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
+    if (w_dtype == SLI_DT_I8) return pf_gemm_qkv_segs_launch<int8_t>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
+    return pf_gemm_qkv_segs_launch<__half>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
+}
+
+int sli_prefill_gemm_qkv_segs(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo,
+                              int32_t N, int32_t K, int32_t M, const sli_pf_group* groups, int32_t B,
+                              const sli_pgemm_epilogue* epi, void* table, sli_pgemm_tiling* tiling, sli_stream_t stream) {
+    SLI_CHECK(w && hi && lo && epi && groups && table, SLI_ERR_ARG, "sli_prefill_gemm_qkv_segs: null pointer");
+    SLI_CHECK(w_dtype == SLI_DT_F16 || w_dtype == SLI_DT_I8, SLI_ERR_ARG,
+              "sli_prefill_gemm_qkv_segs: fp16 or int8 weights (MXFP4: sli_prefill_gemm_qkv_segs_mxfp4)");
+    return pf_gemm_qkv_segs_entry(w, w_dtype, w_row_scale, hi, lo, N, K, M, groups, B, epi, table, tiling, stream);
+}
+
+int sli_prefill_gemm_qkv_segs_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N,
+                                    int32_t K, int32_t M, const sli_pf_group* groups, int32_t B,
+                                    const sli_pgemm_epilogue* epi, void* table, sli_pgemm_tiling* tiling,
+                                    sli_stream_t stream) {
+    SLI_CHECK(data && scales && hi && lo && epi && groups && table, SLI_ERR_ARG,
+              "sli_prefill_gemm_qkv_segs_mxfp4: null pointer");
+    return pf_gemm_qkv_segs_entry(data, SLI_DT_MXFP4, scales, hi, lo, N, K, M, groups, B, epi, table, tiling, stream);
+}
+
+int sli_prefill_attn_segs(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int32_t M,
+                          const sli_pf_group* groups, int32_t B, int32_t hq, int32_t hkv, int32_t hd, int32_t T,
+                          void* table, sli_stream_t stream) {
+    SLI_CHECK(q && kc && vc && ohi && olo && groups && table, SLI_ERR_ARG, "sli_prefill_attn_segs: null pointer");
+    SLI_CHECK(kv_dtype == SLI_DT_F16 || kv_dtype == SLI_DT_F8E4M3, SLI_ERR_ARG,
+              "sli_prefill_attn_segs: an fp16 or FP8 cache (fp32 has no table form)");
+    SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_attn_segs: M must be 32, 64, 128 or 256");
+    SLI_CHECK(hd == 64 || hd == 128, SLI_ERR_ARG, "sli_prefill_attn_segs: head_dim must be 64 or 128");
+    SLI_CHECK(hq >= 1 && hkv >= 1 && hq % hkv == 0 && hq <= 65535, SLI_ERR_ARG,
+              "sli_prefill_attn_segs: hq must be a multiple of hkv");
+    SLI_CHECK(al16(q) && al16(kc) && al16(vc) && al16(ohi) && al16(olo), SLI_ERR_ARG,
+              "sli_prefill_attn_segs: 16-byte alignment");
+    hipStream_t s = as_stream(stream);
+    if (int rc = pf_set_segs(table, groups, M, B, T, s)) return rc;
+    const PfSegs* segs = (const PfSegs*)table;
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (kv_dtype == SLI_DT_F16) {
+        const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<__half>(aa, hd, M, segs, s));
+    } else {
+        const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, segs, s));
     }
     return SLI_OK;
 }

@@ -350,6 +350,42 @@ class LlamaModel:
              logits.ctypes.data_as(ctypes.c_void_p) if want_logits else None)
         return (toks, logits.transpose(1, 0, 2).copy()) if want_logits else toks
 
+    @staticmethod
+    def _ragged(prompts):
+        ld = max(1, max(len(p) for p in prompts))
+        P = np.zeros((len(prompts), ld), np.int32)
+        for b, p in enumerate(prompts):
+            P[b, :len(p)] = p
+        return P, np.array([len(p) for p in prompts], np.int32), ld
+
+    def prefill_batch_ok(self) -> bool:
+        """Whether this model takes prefill_batch (sli_model_prefill_seqs_ok)."""
+        return _lib.load().sli_model_prefill_seqs_ok(self._h) == 1
+
+    def prefill_batch(self, prompts, seqs=None):
+        """Prefill sequences ``seqs`` (default 0 .. len(prompts)-1; distinct, < batch) with their own prompts as packed
+        MFMA GEMM chunks (sli_model_prefill_seqs); the other sequences keep their cache rows and state. Each listed
+        sequence is left at its last prompt token, so the next step() yields its first generated token."""
+        seqs = np.arange(len(prompts), dtype=np.int32) if seqs is None else np.ascontiguousarray(seqs, np.int32)
+        if seqs.size != len(prompts) or not len(prompts):
+            raise ValueError("one prompt per listed sequence")
+        P, lens, ld = self._ragged(prompts)
+        call("sli_model_prefill_seqs", self._h, seqs.ctypes.data_as(ctypes.c_void_p), seqs.size,
+             P.ctypes.data_as(ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p), ld)
+
+    def predict_batch_prefill(self, prompts, max_length: int, want_logits: bool = False):
+        """predict_batch with the prompts prefilled (sli_model_predict_batch_prefill): tokens [batch, max_length],
+        logits [batch, max_length, local vocab] with NaN rows at positions < len(prompt) - 1."""
+        if len(prompts) != self.batch:
+            raise ValueError(f"need {self.batch} prompts")
+        P, lens, ld = self._ragged(prompts)
+        toks = np.empty((self.batch, max_length), np.int32)
+        logits = np.empty((max_length, self.batch, self.local_vocab), np.float32) if want_logits else None
+        call("sli_model_predict_batch_prefill", self._h, P.ctypes.data_as(ctypes.c_void_p),
+             lens.ctypes.data_as(ctypes.c_void_p), ld, max_length, toks.ctypes.data_as(ctypes.c_void_p),
+             logits.ctypes.data_as(ctypes.c_void_p) if want_logits else None)
+        return (toks, logits.transpose(1, 0, 2).copy()) if want_logits else toks
+
     def weight_shard(self, kind: int, index: int = 0) -> np.ndarray:
         """This rank's shard of a weight (sli_tp_plan window) read back as fp32."""
         from .tp import KINDS, shard_window

@@ -371,6 +371,100 @@ def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int, kv_dtyp
     return ohi, olo
 
 
+# ---- the packed prefill of a batched model's sequences (sli_model_prefill_seqs): the packing rule and the two stages
+# that read the group table
+def prefill_pack(lens, seqs=None):
+    """sli_prefill_pack (host only, no GPU): the chunks that prefill sequences ``seqs`` (default 0 .. len(lens)-1) with
+    prompts of ``lens`` tokens. Returns (groups, chunk_rows): groups an int32 array [n, 3] of (seq, p0, nv), 16 chunk
+    rows each, padding groups (nv == 0) included, chunk c's groups starting at 16 * c; chunk_rows the rows of each
+    chunk (32 / 64 / 128 / 256)."""
+    import numpy as np
+    lens = np.ascontiguousarray(lens, np.int32)
+    seqs = np.arange(lens.size, dtype=np.int32) if seqs is None else np.ascontiguousarray(seqs, np.int32)
+    if seqs.shape != lens.shape or lens.ndim != 1:
+        raise ValueError("prefill_pack: one length per sequence")
+    cap_g = int(np.maximum(lens, 1).sum() // 16 + lens.size + 16)
+    cap_c = cap_g // 16 + 1
+    groups = np.zeros((cap_g, 3), np.int32)
+    rows = np.zeros(cap_c, np.int32)
+    n = ctypes.c_int32()
+    call("sli_prefill_pack", seqs.ctypes.data_as(ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p), lens.size,
+         groups.ctypes.data_as(ctypes.c_void_p), cap_g, rows.ctypes.data_as(ctypes.c_void_p), cap_c, ctypes.byref(n))
+    rows = rows[:n.value].copy()
+    ng = 0 if n.value == 0 else 16 * (n.value - 1) + int(rows[-1]) // 16
+    return groups[:ng].copy(), rows
+
+
+def _pf_groups(groups, M):
+    """(seq, p0, nv) triples -> a host array of M / 16 sli_pf_group (short lists end in padding groups)."""
+    gs = [tuple(int(v) for v in g) for g in groups]
+    if len(gs) > max(M // 16, 0):
+        raise ValueError("more groups than the chunk holds")
+    gs += [(0, 0, 0)] * (M // 16 - len(gs))
+    arr = (_lib.PfGroup * max(len(gs), 1))()
+    for i, (s, p0, nv) in enumerate(gs):
+        arr[i] = _lib.PfGroup(s, p0, nv)
+    return arr
+
+
+def _pf_table(device):
+    return torch.empty(48, device=device, dtype=torch.int32)
+
+
+def prefill_gemm_qkv_segs(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, groups, row_scale=None,
+                          scales=None, kv_dtype=None):
+    """prefill_gemm_qkv under a group table: kc / vc are one layer's cache of B sequences [B, hkv, T, hd] (f16, or FP8
+    E4M3); groups a list of (seq, p0, nv), chunk rows 16 g .. being positions p0 .. p0 + 15 of sequence seq, the first
+    nv written to its cache (nv 0: a padding group; missing groups are padding). Returns the tiling that ran."""
+    if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.dim() != 4 or kc.shape[1] != hkv or kc.shape[3] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    B, T = kc.shape[0], kc.shape[2]
+    M = hi.shape[0]
+    if q.shape != (M, hq * hd) or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    if hi.shape != lo.shape or hi.dtype != torch.float16 or lo.dtype != torch.float16:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, sin_t, cos_t, hi, lo, w, row_scale, scales)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_kv_dt(kc, kv_dtype), sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
+                           hd=hd, T=T)
+    table = _pf_table(w.device)
+    tl = _lib.PgemmTiling()
+    gs = _pf_groups(groups, M)
+    if scales is not None:
+        if row_scale is not None:
+            raise ValueError("prefill GEMM: MXFP4 weights (scales=) take no row_scale")
+        N, K = w.shape[0], w.shape[1] * 2
+        if w.dtype != torch.uint8 or scales.dtype != torch.uint8 or scales.shape != (N, K // 32) or hi.shape != (M, K):
+            raise ValueError("Tensor with Wrong Dim!")
+        call("sli_prefill_gemm_qkv_segs_mxfp4", _p(w), _p(scales), _p(hi), _p(lo), N, K, M, gs, B, ctypes.byref(e),
+             _p(table), ctypes.byref(tl), _s())
+    else:
+        N, K = w.shape
+        if hi.shape != (M, K) or w.dtype not in (torch.float16, torch.int8):
+            raise ValueError("prefill GEMM takes fp16 or int8 weights [N, K] and hi / lo [M, K]")
+        call("sli_prefill_gemm_qkv_segs", _p(w), _DT[w.dtype], _p(row_scale), _p(hi), _p(lo), N, K, M, gs, B,
+             ctypes.byref(e), _p(table), ctypes.byref(tl), _s())
+    return {n: getattr(tl, n) for n, _ in tl._fields_}
+
+
+def prefill_attn_segs(q, kc, vc, groups, hq: int, hkv: int, hd: int, kv_dtype=None):
+    """prefill_attn under a group table: q [M, hq hd] fp32, kc / vc [B, hkv, T, hd] (f16 or FP8 E4M3); group g's 16
+    rows attend the cache rows 0 .. p0 + r of its sequence. Returns (ohi, olo) [M, hq hd] fp16; the rows of a padding
+    group stay zero."""
+    M = q.shape[0]
+    if q.shape != (M, hq * hd) or kc.shape != vc.shape or kc.dim() != 4 or kc.shape[1] != hkv or kc.shape[3] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    B, T = kc.shape[0], kc.shape[2]
+    ohi = torch.zeros(M, hq * hd, device=q.device, dtype=torch.float16)
+    olo = torch.zeros_like(ohi)
+    table = _pf_table(q.device)
+    _dev(q, kc, vc)
+    call("sli_prefill_attn_segs", _p(q), _p(kc), _p(vc), _kv_dt(kc, kv_dtype), _p(ohi), _p(olo), M, _pf_groups(groups, M),
+         B, hq, hkv, hd, T, _p(table), _s())
+    return ohi, olo
+
+
 BG_ROLE_QKV, BG_ROLE_GATE_UP, BG_ROLE_STORE, BG_ROLE_LOGITS = 0, 1, 2, 3
 
 
