@@ -227,6 +227,21 @@ enum { SLI_SAMPLE_STREAM = 12 }; /* the draw's stream kind, after sli_synth.h's 
 int sli_sample(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_sampling* p,
                int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, int32_t* out_dev, sli_stream_t stream);
 
+/* Scoring (no reference counterpart). The rule, for one row of V fp32 logits l and a target t:
+ *   lse = M + log(sum_j exp(l_j - M)) with M = max_j l_j;  logprob = l_t - lse;
+ *   top = the first index of the maximum in sli_argmax's order (-0 equals +0; a NaN never displaces the best so far,
+ *   a NaN at index 0 is never displaced);  top_logprob = l_top - lse.
+ * All of it in fp32, in a fixed summation order (csrc/score.h). -inf logits contribute 0. A target outside [0, V)
+ * gives logprob = NaN, and no address is ever formed from it. A row with a NaN logit gives NaN log-probabilities.
+ * The results are bitwise reproducible from run to run, and a row's result does not depend on the other rows of the
+ * launch: fixed-order merges, no floating-point atomics.
+ * sli_score_rows: M rows at logits + m * ld (ld >= V, ld % 4 == 0, logits 16-byte aligned; columns V .. ld - 1 are
+ * never used), targets int32 [M] on the device; logprob [M], top [M] and top_logprob [M] on the device, the last two
+ * nullable. One workgroup per row and one read of the rows: the launch is bound by M * V * 4 bytes. Bad arguments are
+ * SLI_ERR_ARG before the device is touched. */
+int sli_score_rows(const float* logits, int32_t M, int32_t V, int32_t ld, const int32_t* targets, float* logprob,
+                   int32_t* top, float* top_logprob, sli_stream_t stream);
+
 /* ---------------------------------------------------------------- model level */
 typedef struct {
     int32_t vocab, dim, n_heads, n_kv_heads, head_dim, ffn, n_layers, max_len;
@@ -386,6 +401,27 @@ int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, s
 int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
                            const int32_t* lens, int32_t ld);
 int sli_model_prefill_seqs_ok(const sli_model* m); /* 1: the model takes sli_model_prefill_seqs */
+/* Test hook (no device needed): the argument checks of sli_model_prefill_seqs and sli_model_score_seqs, in their order,
+ * as a model of `batch` sequences, max_len `max_len` and `vocab` tokens makes them. */
+int sli_debug_prefill_seqs_args(int32_t batch, int32_t max_len, int32_t vocab, const int32_t* seqs, int32_t n_seqs,
+                                const int32_t* prompts, const int32_t* lens, int32_t ld);
+/* Score prompts: sli_model_prefill_seqs, and the log-probability of every prompt token given the tokens before it (the
+ * rule at sli_score_rows). The same arguments, the same checks in the same order, the same refusals, the same packing;
+ * the K/V rows, state, prompt and history it leaves are bit for bit those of sli_model_prefill_seqs, every unlisted
+ * sequence untouched. After each chunk's last layer the chunk's rows run through the final RMSNorm, the LM head (the
+ * embedding table in the model's weight format: one GEMM over the chunk, role 3 of sli_prefill_gemm) and one
+ * sli_score_rows-style launch that reads the group table: the hidden state of position t scores token t + 1.
+ * Outputs are host arrays [n_seqs][ld]: entry (i, t), 1 <= t < lens[i], is about prompts[i][t]; entry (i, 0) and the
+ * entries at t >= lens[i] are NaN / -1 / NaN. top and top_logprob may be NULL. A prompt of length 1 scores nothing.
+ * The scoring chunks are captured graphs of their own, so sli_model_prefill_seqs replays what it always did. The
+ * logits chunk ([256][vocab rounded up to 4] fp32: 131 MB at a vocabulary of 128 256) and the result buffers are
+ * allocated at the first call and freed with the model; a failed allocation is SLI_ERR_NOMEM and touches no sequence.
+ * The sampling state is not consulted. Batch 1 .. 8, fp16 / int8 / MXFP4 weights, an fp16 or FP8 cache; a single
+ * rank only: under tensor parallelism the logits are vocab-sharded, so tp_size > 1 and the ranks of an in-process
+ * group are SLI_ERR_STATE with that reason. */
+int sli_model_score_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                         const int32_t* lens, int32_t ld, float* logprob, int32_t* top, float* top_logprob);
+int sli_model_score_seqs_ok(const sli_model* m); /* 1: the model takes sli_model_score_seqs */
 /* sli_model_predict_batch with every prompt prefilled (sli_model_prefill_seqs over all `batch` sequences), then
  * max_length - min(lens) + 1 steps; sequence b waits at its last prompt position (idempotent steps) for the first
  * lens[b] - min(lens) of them, so all sequences finish together at position max_length. max(lens) <= max_length <=
@@ -537,7 +573,11 @@ typedef struct {
  * role 1, gate/up: N = 2 * inter rows [gate; up]; sigmoid(g) * u (act_mode 0) or SiLU(g) * u (1) as fp16 hi / lo
  *   in ahi / alo [M][inter].
  * role 2, wo / down: y[m][r] = (resid ? resid[m][r] : 0) + sum * row scale, y and resid [M][ld] fp32, ld >= N,
- *   ld % 4 == 0 (resid may be y). */
+ *   ld % 4 == 0 (resid may be y).
+ * role 3, logits (the LM head over chunk rows): y[m][r] = sum * row scale for r < N, through role 2's y / ld fields;
+ *   no residual. N >= 16 need not be a multiple of 16 (the last tile's weight rows are clamped, the store and the row
+ *   scale load masked at N); columns N .. ld - 1 of y are never written. ld >= N, ld % 4 == 0. For N % 16 == 0 the
+ *   result is role 2's with a null resid, bit for bit. */
 typedef struct {
     int32_t role;
     /* role 0 */
@@ -560,7 +600,7 @@ typedef struct {
 
 /* One pgemm_kernel launch: sums[m][r] = sum_k W[r][k] * (hi[m][k] + lo[m][k]) in fp32 on MFMA, then the epilogue.
  * W [N][K] in w_dtype (SLI_DT_F16 / SLI_DT_I8), w_row_scale [N] or NULL, hi / lo [M][K] fp16, M one of 32, 64,
- * 128, 256, K % 64 == 0, N % 16 == 0, 0 <= p0, 1 <= nv <= M. *tiling (optional) receives the tiling that ran. */
+ * 128, 256, K % 64 == 0, N % 16 == 0 (role 3: N >= 16), 0 <= p0, 1 <= nv <= M. *tiling (optional) receives the tiling that ran. */
 int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
                      int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
                      sli_pgemm_tiling* tiling, sli_stream_t stream);

@@ -176,6 +176,10 @@ _SIGS = {
     "sli_model_prefill_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "sli_model_prefill_seqs_ok": (c_int, [c_vp]),
     "sli_model_predict_batch_prefill": (c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "sli_score_rows": (c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "sli_model_score_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sli_model_score_seqs_ok": (c_int, [c_vp]),
+    "sli_debug_prefill_seqs_args": (c_int, [c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "sli_prefill_gemm_qkv_segs": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
                                           ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
     "sli_prefill_gemm_qkv_segs_mxfp4": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,

@@ -34,6 +34,7 @@
 #include "prefill.h"
 #include "qkv_attn.h"
 #include "rope_table.h"
+#include "score.h"
 #include "step_state.h"
 #include "tp_layers.h"
 
@@ -121,6 +122,15 @@ struct sli_model {
         sli::PfSegs* segs = nullptr;
         hipGraph_t sgraph[4] = {};
         hipGraphExec_t sexec[4] = {};
+        // sli_model_score_seqs: a table chunk, then the final norm, the LM head over the chunk rows (role 3) and the
+        // score launch (score.h). Graphs of their own: sgraph / sexec above stay what they were, node for node. The
+        // logits chunk [chunk][vld] and the position-indexed results [B][T + 1] are allocated at the first scoring call.
+        hipGraph_t scgraph[4] = {};
+        hipGraphExec_t scexec[4] = {};
+        float* sc_logits = nullptr;
+        float *sc_lp = nullptr, *sc_tlp = nullptr;
+        int32_t* sc_top = nullptr;
+        bool sc_ready = false;
         int mode = SLI_PREFILL_AUTO;  // sli_model_set_prefill
     } pf;
     // tensor-parallel all-reduce: SLI_ALLREDUCE_RCCL (ncclAllReduce) or SLI_ALLREDUCE_ONESHOT (oneshot.h)
@@ -1250,6 +1260,24 @@ struct StepRecorder {
         for (int p = 0; p < 2 * m->L; ++p) SLI_TRY(record_pf_phase<true>(m, p, M));
         return SLI_OK;
     }
+    // a chunk of sli_model_score_seqs: the same launches, then the final norm (index 2L), the LM head over the chunk's
+    // rows (the embedding table in the model's weight format, role 3) and the group-table score launch (score.h): the
+    // hidden state of position t scores the prompt's token t + 1
+    static int score_vld(const sli_model* m) { return (m->V + 3) & ~3; }
+    static int record_score_segs(sli_model* m, int M) {
+        SLI_TRY(record_prefill_segs(m, M));
+        auto& f = m->pf;
+        hipLaunchKernelGGL(pf_norm_split_kernel, dim3(M), dim3(256), 0, m->stream, f.x,
+                           m->norms + (size_t)(2 * m->L) * m->D, f.hhi, f.hlo, m->D, m->c.eps);
+        SLI_HIP(hipGetLastError());
+        const int vld = score_vld(m);
+        const PgEpiLogits el{f.sc_logits, MX ? nullptr : m->emb_s, m->V, vld};
+        SLI_TRY(pg(m, m->emb, m->emb_s, pg_logits_n(m->V), m->D, f.hhi, f.hlo, el, M, 3));
+        SLI_HIP(launch_score_rows(f.sc_logits, M, m->V, vld, ScSegs{f.segs, m->prompt, m->T + 1}, f.sc_lp, f.sc_top,
+                                  f.sc_tlp, m->stream));
+        return SLI_OK;
+    }
+    static int prepare_score(sli_model* m) { return allow_pg<PgEpiLogits>(m); }
     static int record_group_prefill(sli_tp_group* g, int M) {
         sli_model* m0 = g->ranks[0];
         GroupSumArgs sa{};
@@ -1524,6 +1552,8 @@ static void destroy(sli_model* m) {
         if (m->pf.graph[b]) (void)hipGraphDestroy(m->pf.graph[b]);
         if (m->pf.sexec[b]) (void)hipGraphExecDestroy(m->pf.sexec[b]);
         if (m->pf.sgraph[b]) (void)hipGraphDestroy(m->pf.sgraph[b]);
+        if (m->pf.scexec[b]) (void)hipGraphExecDestroy(m->pf.scexec[b]);
+        if (m->pf.scgraph[b]) (void)hipGraphDestroy(m->pf.scgraph[b]);
     }
     if (m->comm) ncclCommDestroy(m->comm);
     for (int r = 0; r < sli::kOsMaxRanks; ++r)
@@ -2208,24 +2238,87 @@ static const char* pf_seqs_why(const sli_model* m) {
 
 extern "C" int sli_model_prefill_seqs_ok(const sli_model* m) { return m && !pf_seqs_why(m) ? 1 : 0; }
 
+// the argument checks of sli_model_prefill_seqs and sli_model_score_seqs for a model of batch B, max_len T and
+// vocabulary V, in their one order; host only
+static int pf_seqs_args(int B, int T, int V, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                        const int32_t* lens, int32_t ld) {
+    SLI_CHECK(n_seqs >= 1 && n_seqs <= B, SLI_ERR_ARG, "prefill_seqs: n_seqs must be in [1, batch]");
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(seqs[i] >= 0 && seqs[i] < B, SLI_ERR_ARG, "prefill_seqs: sequence index out of range");
+        for (int j = 0; j < i; ++j) SLI_CHECK(seqs[j] != seqs[i], SLI_ERR_ARG, "prefill_seqs: a sequence is listed twice");
+    }
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(lens[i] >= 1 && lens[i] <= std::min(ld, T), SLI_ERR_RANGE, "prompt length out of range");
+        for (int t = 0; t < lens[i]; ++t) {
+            const int32_t id = prompts[(size_t)i * ld + t];
+            SLI_CHECK(id >= 0 && id < V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
+        }
+    }
+    return SLI_OK;
+}
+
+extern "C" int sli_debug_prefill_seqs_args(int32_t batch, int32_t max_len, int32_t vocab, const int32_t* seqs,
+                                           int32_t n_seqs, const int32_t* prompts, const int32_t* lens, int32_t ld) {
+    SLI_CHECK(seqs && prompts && lens, SLI_ERR_ARG, "null argument");
+    return pf_seqs_args(batch, max_len, vocab, seqs, n_seqs, prompts, lens, ld);
+}
+
+// Why this model cannot take sli_model_score_seqs (null: it can): what refuses the packed prefill, with the reason a
+// tensor-parallel rank has of its own (its logits are vocab-sharded)
+static const char* score_seqs_why(const sli_model* m) {
+    if (m->group) return "score_seqs: not for the ranks of an in-process tp group (their logits are vocab-sharded)";
+    if (m->c.tp_size > 1 || m->partial) return "score_seqs: single-rank models (the logits are vocab-sharded under tensor parallelism)";
+    return pf_seqs_why(m);
+}
+
+// the logits chunk and the position-indexed result buffers, at the first scoring call (freed with the model)
+static int score_alloc(sli_model* m) {
+    auto& p = m->pf;
+    if (p.sc_ready) return SLI_OK;
+    const size_t vld = ((size_t)m->V + 3) & ~(size_t)3, slots = (size_t)m->B * (m->T + 1);
+    // (a call that failed half way is taken up where it stopped)
+    if (!p.sc_logits) SLI_TRY(model_alloc(m, (void**)&p.sc_logits, sizeof(float) * kPfMaxChunk * vld));
+    if (!p.sc_lp) SLI_TRY(model_alloc(m, (void**)&p.sc_lp, sizeof(float) * slots));
+    if (!p.sc_top) SLI_TRY(model_alloc(m, (void**)&p.sc_top, sizeof(int32_t) * slots));
+    if (!p.sc_tlp) SLI_TRY(model_alloc(m, (void**)&p.sc_tlp, sizeof(float) * slots));
+    SLI_TRY(SLI_DISPATCH(m, prepare_score, m));
+    p.sc_ready = true;
+    return SLI_OK;
+}
+
+// sli_model_prefill_seqs, and with `score` sli_model_score_seqs: the same packing and launches, the scoring chunks
+// through graphs of their own (record_score_segs)
+struct PfScoreOut {
+    float* logprob;
+    int32_t* top;
+    float* top_logprob;
+};
+static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts, const int32_t* lens,
+                       int32_t ld, const PfScoreOut* score);
+
 extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
                                       const int32_t* lens, int32_t ld) {
     SLI_CHECK(m && seqs && prompts && lens, SLI_ERR_ARG, "null argument");
     if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    return pf_seqs_run(m, seqs, n_seqs, prompts, lens, ld, nullptr);
+}
+
+extern "C" int sli_model_score_seqs_ok(const sli_model* m) { return m && !score_seqs_why(m) ? 1 : 0; }
+
+extern "C" int sli_model_score_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                                    const int32_t* lens, int32_t ld, float* logprob, int32_t* top, float* top_logprob) {
+    SLI_CHECK(m && seqs && prompts && lens && logprob, SLI_ERR_ARG, "null argument");
+    if (const char* why = score_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    const PfScoreOut out{logprob, top, top_logprob};
+    return pf_seqs_run(m, seqs, n_seqs, prompts, lens, ld, &out);
+}
+
+static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts, const int32_t* lens,
+                       int32_t ld, const PfScoreOut* score) {
     // every argument is judged before any state or device memory is touched
-    SLI_CHECK(n_seqs >= 1 && n_seqs <= m->B, SLI_ERR_ARG, "prefill_seqs: n_seqs must be in [1, batch]");
-    for (int i = 0; i < n_seqs; ++i) {
-        SLI_CHECK(seqs[i] >= 0 && seqs[i] < m->B, SLI_ERR_ARG, "prefill_seqs: sequence index out of range");
-        for (int j = 0; j < i; ++j) SLI_CHECK(seqs[j] != seqs[i], SLI_ERR_ARG, "prefill_seqs: a sequence is listed twice");
-    }
-    for (int i = 0; i < n_seqs; ++i) {
-        SLI_CHECK(lens[i] >= 1 && lens[i] <= std::min(ld, m->T), SLI_ERR_RANGE, "prompt length out of range");
-        for (int t = 0; t < lens[i]; ++t) {
-            const int32_t id = prompts[(size_t)i * ld + t];
-            SLI_CHECK(id >= 0 && id < m->V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
-        }
-    }
+    SLI_TRY(pf_seqs_args(m->B, m->T, m->V, seqs, n_seqs, prompts, lens, ld));
     SLI_HIP(hipSetDevice(m->c.device));
+    if (score) SLI_TRY(score_alloc(m));  // a failed allocation leaves the sequences as they were
     for (int i = 0; i < n_seqs; ++i) {
         const int32_t* ids = prompts + (size_t)i * ld;
         SLI_TRY(set_prompt(m, seqs[i], ids, lens[i]));
@@ -2237,8 +2330,12 @@ extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t
         SLI_TRY(pf_alloc(m));
         for (int rows : pl.rows) {  // capture before anything is enqueued behind the capture
             const int b = pf_bucket(rows);
-            SLI_TRY(capture_graph(m->stream, m->pf.sgraph[b], m->pf.sexec[b],
-                                  [&]() { return SLI_DISPATCH(m, record_prefill_segs, m, kPfSizes[b]); }));
+            if (score)
+                SLI_TRY(capture_graph(m->stream, m->pf.scgraph[b], m->pf.scexec[b],
+                                      [&]() { return SLI_DISPATCH(m, record_score_segs, m, kPfSizes[b]); }));
+            else
+                SLI_TRY(capture_graph(m->stream, m->pf.sgraph[b], m->pf.sexec[b],
+                                      [&]() { return SLI_DISPATCH(m, record_prefill_segs, m, kPfSizes[b]); }));
         }
         // each chunk's table (the groups it lacks: padding) and its graph, enqueued back to back
         std::vector<PfSegs> tabs(pl.rows.size());
@@ -2254,7 +2351,26 @@ extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t
         }
         for (size_t c = 0; c < pl.rows.size(); ++c) {
             SLI_HIP(hipMemcpyAsync(m->pf.segs, &tabs[c], sizeof(PfSegs), hipMemcpyHostToDevice, m->stream));
-            SLI_HIP(hipGraphLaunch(m->pf.sexec[pf_bucket(pl.rows[c])], m->stream));
+            SLI_HIP(hipGraphLaunch((score ? m->pf.scexec : m->pf.sexec)[pf_bucket(pl.rows[c])], m->stream));
+        }
+        SLI_TRY(wait_stream(m));
+    }
+    if (score) {  // entry (i, t), 1 <= t < lens[i]: slot (seqs[i], t) of the device buffers; everything else is empty
+        const size_t n = (size_t)n_seqs * ld;
+        std::fill_n(score->logprob, n, NAN);
+        if (score->top) std::fill_n(score->top, n, -1);
+        if (score->top_logprob) std::fill_n(score->top_logprob, n, NAN);
+        for (int i = 0; i < n_seqs; ++i) {
+            if (lens[i] < 2) continue;
+            const size_t src = (size_t)seqs[i] * (m->T + 1) + 1, dst = (size_t)i * ld + 1, cnt = (size_t)lens[i] - 1;
+            SLI_HIP(hipMemcpyAsync(score->logprob + dst, m->pf.sc_lp + src, sizeof(float) * cnt, hipMemcpyDeviceToHost,
+                                   m->stream));
+            if (score->top)
+                SLI_HIP(hipMemcpyAsync(score->top + dst, m->pf.sc_top + src, sizeof(int32_t) * cnt,
+                                       hipMemcpyDeviceToHost, m->stream));
+            if (score->top_logprob)
+                SLI_HIP(hipMemcpyAsync(score->top_logprob + dst, m->pf.sc_tlp + src, sizeof(float) * cnt,
+                                       hipMemcpyDeviceToHost, m->stream));
         }
         SLI_TRY(wait_stream(m));
     }

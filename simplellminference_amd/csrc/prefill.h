@@ -672,6 +672,36 @@ struct PgEpiResid {  // y[m][row] = resid[m][row] + sum * row scale (matmul_kern
     }
 };
 
+// The LM head over chunk rows (role 3, "logits"): y[m][row] = sum * row scale for row < nrows, and nothing else. nrows
+// need not be a multiple of 16 (the small presets have a vocabulary of 1000): the launch's N is nrows rounded up to 16,
+// the row map clamps the last tile's weight rows as PgEpiResid's does, and the store and the int8 row-scale load are
+// masked at nrows, so columns nrows .. ld - 1 are never written. A full 4-row group is PgEpiResid's store without a
+// residual, bit for bit.
+struct PgEpiLogits {
+    float* y;  // [M][ld], ld >= nrows, ld % 4 == 0
+    const float* rscale;
+    int nrows, ld;
+    __device__ int row(int t, int i) const { return min(t * 16 + i, nrows - 1); }
+    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
+        const int row = t * 16 + i0;
+        const size_t i = (size_t)m * ld + row;
+        if (row + 3 < nrows) {
+            float4 p = make_float4(v[0], v[1], v[2], v[3]);
+            if (rscale) {
+                const float4 sc = *reinterpret_cast<const float4*>(rscale + row);
+                p = make_float4(p.x * sc.x, p.y * sc.y, p.z * sc.z, p.w * sc.w);
+            }
+            *reinterpret_cast<float4*>(y + i) = p;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (row + e < nrows) y[i + e] = rscale ? v[e] * rscale[row + e] : v[e];
+        }
+    }
+};
+// the N a role-3 launch is given for nrows weight rows
+constexpr int pg_logits_n(int nrows) { return (nrows + 15) & ~15; }
+
 template <class Epi, class Cfg, typename WT>
 hipError_t launch_pgemm(const PgIn<WT>& in, const Epi& epi, const PfState* ps, hipStream_t s) {
     using Geo = PgGeo<Cfg, WT>;
@@ -692,11 +722,13 @@ hipError_t pgemm_allow_lds() {
 // the tools/pgemm_lab sweeps on the 7B shapes (profiles/r3_pgemm_lab.txt; round 6: the pipelined fragment reads,
 // 5-20 % faster at every tiling, the M = 128 choices, profiles/r6b_pg_pipe.txt, and the M = 256 ones re-timed with
 // the weights streamed from HBM as in the engine, profiles/r6b_pg_cold.txt).
-// role 0: qkv, 1: gate/up, 2: wo / down (N = D: few row blocks, so small chunk blocks for a full grid).
+// role 0: qkv, 1: gate/up, 2: wo / down (N = D: few row blocks, so small chunk blocks for a full grid), 3: logits
+// (N = V: many row blocks, as gate/up, whose cells it starts on; nobody has timed them at N = V yet).
 // f(PgCfg<...>{}) is called with the chosen tiling. The one table: the engine's launches, its LDS opt-in and the
 // kernel-level entry point (sli_prefill_gemm) all pick through it.
 template <typename WT, class F>
 int pg_pick(int M, int role, F&& f) {
+    if (role == 3) role = 1;
     if constexpr (is_mx<WT>::value) {
         // the fastest of tools/pgemm_lab's LAB_MX sweep per 7B shape and chunk size, weights rotated over four copies
         // (profiles/mxfp4_pgemm_lab.txt; PIPE is not yet measured for this format, SA is refused for it). wo / down
@@ -729,7 +761,7 @@ template <class Epi, typename WT>
 hipError_t pg_allow_lds_all() {
     hipError_t err = hipSuccess;
     for (int M : kPfSizes)
-        for (int role = 0; role < 3; ++role)
+        for (int role = 0; role < 4; ++role)
             pg_pick<WT>(M, role, [&](auto cfg) {
                 if (err == hipSuccess) err = pgemm_allow_lds<Epi, decltype(cfg), WT>();
                 return 0;

@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "prefill.h"
+#include "score.h"
 
 namespace sli {
 
@@ -94,6 +95,10 @@ static int pf_gemm_role(const void* w, const float* rs_in, const void* hi, const
         const PgEpiSwiGLU g{(__half*)e.ahi, (__half*)e.alo, rs, e.inter, e.act_mode};
         return pf_gemm_launch<PgEpiSwiGLU, WT>(w, ws, hi, lo, N, K, M, 1, g, ps, tiling, s);
     }
+    if (e.role == 3) {  // N weight rows, any N >= 16: the launch covers whole 16-row tiles, the epilogue masks at N
+        const PgEpiLogits g{e.y, rs, N, e.ld};
+        return pf_gemm_launch<PgEpiLogits, WT>(w, ws, hi, lo, pg_logits_n(N), K, M, 3, g, ps, tiling, s);
+    }
     const PgEpiResid r{e.y, e.resid, rs, N, e.ld};
     return pf_gemm_launch<PgEpiResid, WT>(w, ws, hi, lo, N, K, M, 2, r, ps, tiling, s);
 }
@@ -138,7 +143,8 @@ static int pf_gemm_check(const void* w, int w_dtype, const void* ws, const void*
                          int32_t M, const sli_pgemm_epilogue* epi) {
     SLI_CHECK(pf_chunk_size(M), SLI_ERR_ARG, "sli_prefill_gemm: M must be 32, 64, 128 or 256");
     SLI_CHECK(K >= 64 && K % 64 == 0, SLI_ERR_ARG, "sli_prefill_gemm: K must be a multiple of 64");
-    SLI_CHECK(N >= 16 && N % 16 == 0, SLI_ERR_ARG, "sli_prefill_gemm: N must be a multiple of 16");
+    SLI_CHECK(N >= 16 && (N % 16 == 0 || epi->role == 3), SLI_ERR_ARG,
+              "sli_prefill_gemm: N must be a multiple of 16 (role 3: at least 16)");
     SLI_CHECK((int64_t)N * K < ((int64_t)1 << 40) && K <= (1 << 20), SLI_ERR_ARG, "sli_prefill_gemm: shape too large");
     SLI_CHECK(al16(w) && (w_dtype == SLI_DT_MXFP4 || al16(ws)) && al16(hi) && al16(lo), SLI_ERR_ARG,
               "sli_prefill_gemm: 16-byte alignment");
@@ -168,7 +174,13 @@ static int pf_gemm_check(const void* w, int w_dtype, const void* ws, const void*
             SLI_CHECK(e.ld >= N && e.ld % 4 == 0, SLI_ERR_ARG, "sli_prefill_gemm: ld must be >= N and a multiple of 4");
             SLI_CHECK(al16(e.y) && al16(e.resid), SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
             break;
-        default: return fail(SLI_ERR_ARG, "sli_prefill_gemm: role must be 0 (qkv), 1 (gate/up) or 2 (wo/down)");
+        case 3:
+            SLI_CHECK(e.y, SLI_ERR_ARG, "sli_prefill_gemm: null y");
+            SLI_CHECK(e.ld >= N && e.ld % 4 == 0, SLI_ERR_ARG, "sli_prefill_gemm: ld must be >= N and a multiple of 4");
+            SLI_CHECK(al16(e.y), SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
+            break;
+        default:
+            return fail(SLI_ERR_ARG, "sli_prefill_gemm: role must be 0 (qkv), 1 (gate/up), 2 (wo/down) or 3 (logits)");
     }
     return SLI_OK;
 }
@@ -297,6 +309,17 @@ int sli_prefill_attn_segs(const float* q, const void* kc, const void* vc, int kv
         const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
         SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, segs, s));
     }
+    return SLI_OK;
+}
+
+// ---- scoring (score.h): the plain row map; sli_model_score_seqs launches the group-table one
+int sli_score_rows(const float* logits, int32_t M, int32_t V, int32_t ld, const int32_t* targets, float* logprob,
+                   int32_t* top, float* top_logprob, sli_stream_t stream) {
+    SLI_CHECK(logits && targets && logprob, SLI_ERR_ARG, "sli_score_rows: null pointer");
+    SLI_CHECK(M >= 1 && V >= 1, SLI_ERR_ARG, "sli_score_rows: M and V must be positive");
+    SLI_CHECK(ld >= V && ld % 4 == 0, SLI_ERR_ARG, "sli_score_rows: ld must be >= V and a multiple of 4");
+    SLI_CHECK(al16(logits), SLI_ERR_ARG, "sli_score_rows: logits must be 16-byte aligned");
+    SLI_HIP(launch_score_rows(logits, M, V, ld, ScPlain{targets}, logprob, top, top_logprob, as_stream(stream)));
     return SLI_OK;
 }
 

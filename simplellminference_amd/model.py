@@ -373,6 +373,38 @@ class LlamaModel:
         call("sli_model_prefill_seqs", self._h, seqs.ctypes.data_as(ctypes.c_void_p), seqs.size,
              P.ctypes.data_as(ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p), ld)
 
+    def score_ok(self) -> bool:
+        """Whether this model takes score() (sli_model_score_seqs_ok)."""
+        return _lib.load().sli_model_score_seqs_ok(self._h) == 1
+
+    def score(self, prompts, seqs=None):
+        """prefill_batch(prompts, seqs), and the log-probability of every prompt token given the tokens before it
+        (sli_model_score_seqs). One record per prompt: ``logprobs`` (float32), ``top`` (int32: the model's first-max
+        token at that place) and ``top_logprobs`` (float32), arrays of length len(prompt) - 1 whose entry t - 1 is
+        about prompt[t]. The cache rows, state and history are left as prefill_batch leaves them."""
+        seqs = np.arange(len(prompts), dtype=np.int32) if seqs is None else np.ascontiguousarray(seqs, np.int32)
+        if seqs.size != len(prompts) or not len(prompts):
+            raise ValueError("one prompt per listed sequence")
+        P, lens, ld = self._ragged(prompts)
+        lp = np.empty((len(prompts), ld), np.float32)
+        top = np.empty((len(prompts), ld), np.int32)
+        tlp = np.empty((len(prompts), ld), np.float32)
+        call("sli_model_score_seqs", self._h, seqs.ctypes.data_as(ctypes.c_void_p), seqs.size,
+             P.ctypes.data_as(ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p), ld,
+             lp.ctypes.data_as(ctypes.c_void_p), top.ctypes.data_as(ctypes.c_void_p),
+             tlp.ctypes.data_as(ctypes.c_void_p))
+        return [{"logprobs": lp[i, 1:n].copy(), "top": top[i, 1:n].copy(), "top_logprobs": tlp[i, 1:n].copy()}
+                for i, n in enumerate(int(x) for x in lens)]
+
+    def perplexity(self, prompts) -> float:
+        """exp(-sum of the prompts' token log-probabilities / number of scored tokens), accumulated in float64."""
+        recs = self.score(prompts)
+        total = sum(float(np.sum(r["logprobs"], dtype=np.float64)) for r in recs)
+        count = sum(len(r["logprobs"]) for r in recs)
+        if not count:
+            raise ValueError("no scored token: every prompt has length 1")
+        return float(np.exp(-total / count))
+
     def predict_batch_prefill(self, prompts, max_length: int, want_logits: bool = False):
         """predict_batch with the prompts prefilled (sli_model_predict_batch_prefill): tokens [batch, max_length],
         logits [batch, max_length, local vocab] with NaN rows at positions < len(prompt) - 1."""

@@ -262,7 +262,7 @@ def embedding(token, table, out=None, row_scale=None):
 
 
 # ---------------------------------------------------------------- prefill stages (sli.h "for tests and labs")
-PF_ROLE_QKV, PF_ROLE_GATE_UP, PF_ROLE_RESID = 0, 1, 2
+PF_ROLE_QKV, PF_ROLE_GATE_UP, PF_ROLE_RESID, PF_ROLE_LOGITS = 0, 1, 2, 3
 
 
 def _pf_state(device):
@@ -351,6 +351,41 @@ def prefill_gemm_resid(w, hi, lo, y, resid=None, row_scale=None, scales=None):
     e = _lib.PgemmEpilogue(role=PF_ROLE_RESID, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
                            ld=y.shape[1])
     return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
+
+
+def prefill_gemm_logits(w, hi, lo, y, row_scale=None, scales=None):
+    """One pgemm_kernel launch with the logits epilogue (role 3, the LM head over chunk rows): y [M, ld][:, :N] =
+    W (hi + lo) * row scale for W's N >= 16 rows (any N); columns N .. ld - 1 of y are not written."""
+    if y.shape[0] != hi.shape[0]:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_LOGITS, y=y.data_ptr(), ld=y.shape[1])
+    return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
+
+
+def score_rows(logits, targets, want_top: bool = True):
+    """sli_score_rows: per row of fp32 logits [M, V] (rows ``logits.stride(0)`` floats apart: a row-padded view is
+    taken as it is) and int32 target, the target's log-probability, the first-max token and its log-probability (the
+    rule: sli.h). Returns (logprob [M] fp32, top [M] int32, top_logprob [M] fp32), or logprob alone."""
+    if logits.dim() == 1:
+        logits = logits.unsqueeze(0)
+    M, V = logits.shape
+    if not logits.is_cuda or logits.dtype != torch.float32 or (V > 1 and logits.stride(1) != 1):
+        raise ValueError("logits: fp32 device rows of contiguous elements")
+    if not targets.is_cuda or targets.dtype != torch.int32 or targets.shape != (M,):
+        raise ValueError("targets: an int32 device tensor of one target per row")
+    _dev(targets)
+    ld = logits.stride(0)
+    if M == 1 or ld < V or ld % 4 or logits.data_ptr() % 16:  # the kernel reads whole float4: rows padded to 4 floats
+        ld = (V + 3) // 4 * 4
+        buf = torch.zeros(M, ld, device=logits.device, dtype=torch.float32)
+        buf[:, :V] = logits
+        logits = buf
+    lp = torch.empty(M, device=logits.device, dtype=torch.float32)
+    top = torch.empty(M, device=logits.device, dtype=torch.int32) if want_top else None
+    tlp = torch.empty(M, device=logits.device, dtype=torch.float32) if want_top else None
+    call("sli_score_rows", _p(logits), M, V, ld, _p(targets), _p(lp), _p(top), _p(tlp), _s())
+    return (lp, top, tlp) if want_top else lp
 
 
 def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int, kv_dtype=None):
