@@ -388,9 +388,9 @@ int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, s
                      int32_t* chunk_rows, int32_t cap_chunks, int32_t* n_chunks);
 /* Prefill the listed sequences (distinct, < batch; prompts [n_seqs][ld], lens[i] tokens of row i) of a model of any
  * batch 1 .. 8 with their own prompts: chunks packed by the rule above run through the layers as the MFMA GEMMs of
- * sli_model_prefill, the embedding, the q/k/v epilogue and the chunk attention reading a device-resident group table
- * (prefill.h PfSegs) in place of one start position. Every other sequence's cache rows, state, prompt and history are
- * untouched, so a finished sequence can be replaced inside a running batch. Afterwards sequence seqs[i] is at
+ * sli_model_prefill, the embedding, the q/k/v epilogue and the chunk attention reading the device-resident group table
+ * (prefill.h PfSegs) that sli_model_prefill's chunks read too, there with one sequence's groups. Every other
+ * sequence's cache rows, state, prompt and history are untouched, so a finished sequence can be replaced inside a running batch. Afterwards sequence seqs[i] is at
  * (token ids[n-1], position n-1, advancing, prompt = ids) and its history holds ids. Prompts are teacher-forced: the
  * sampling state is not consulted. Takes fp16 / int8 / MXFP4 weights (MXFP4 at batch > 1: SLI_CREATE_MX_BATCH) with an
  * fp16 or FP8 E4M3 cache, head_dim 64 / 128, projection depths that are multiples of 64, a single rank; it is not bound
@@ -548,11 +548,16 @@ int sli_debug_bounded_wait(int32_t mode, double deadline_ms, double* waited_ms);
  * stream, as sli_matmul. The tiling of the GEMM and the attention kernel are chosen by the functions the engine's
  * prefill uses (prefill.h pg_pick, launch_pf_attn), so what runs here is what sli_model_prefill runs. fp16 arrays
  * ("hi" / "lo" operands, fp16 caches) are IEEE binary16. Every device pointer is 16-byte aligned. Anything the
- * kernels cannot take is SLI_ERR_ARG. `state` is 8 bytes of device memory that the call fills on the stream with
- * the chunk's start position p0 and valid-row count nv (prefill.h PfState) ahead of the launch.
+ * kernels cannot take is SLI_ERR_ARG.
+ * One row map: which prompt position a chunk row is stands in a device-resident group table (prefill.h PfSegs), 16 rows
+ * to a group. `state` (the plain entries) and `table` (the *_segs entries) are SLI_PF_TABLE_BYTES of device memory that
+ * the call fills on the stream ahead of the launch. The plain entries take (p0, nv) and write the table of one sequence
+ * at consecutive positions: group g < M / 16 is {sequence 0, p0 + 16 g, clamp(nv - 16 g, 0, 16) valid rows}, any p0 >= 0;
+ * `state` is 8-byte aligned. The *_segs entries take the groups themselves.
  *
  * sli_prefill_norm_split: x [M][D] fp32 -> hi, lo [M][D] fp16: h = RMSNorm(x row) * w (w NULL: h = x),
  * hi = fp16(h), lo = fp16(h - hi). D % 4 == 0, D <= 8192, M >= 1. */
+#define SLI_PF_TABLE_BYTES 192 /* the group table: 3 int32 arrays (sequence, first position, valid rows) of 16 groups */
 int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, int32_t M, int32_t D, float eps,
                            sli_stream_t stream);
 
@@ -628,8 +633,8 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
 
 /* The same two stages under a group table (sli_model_prefill_seqs): groups is a host array of M / 16 entries, chunk
  * rows 16 g .. 16 g + 15 being positions p0 .. p0 + 15 of sequence seq (p0 % 16 == 0, 0 <= p0 < T, 0 <= seq < B,
- * 0 <= nv <= 16; nv == 0: a padding group); `table` is 192 bytes of device memory (4-byte aligned) that the call fills
- * on the stream ahead of the launch (prefill.h PfSegs). kc / vc are one layer's cache of all B sequences,
+ * 0 <= nv <= 16; nv == 0: a padding group); `table` is SLI_PF_TABLE_BYTES of device memory (4-byte aligned) that the call
+ * fills on the stream ahead of the launch. kc / vc are one layer's cache of all B sequences,
  * [B][hkv][T][hd], in SLI_DT_F16 or SLI_DT_F8E4M3 (an fp32 cache has no table form: SLI_ERR_ARG). The same pickers, so
  * what runs here is what sli_model_prefill_seqs runs.
  * sli_prefill_gemm_qkv_segs: the q/k/v GEMM (epi->role 0) with the table epilogue: q [M][hq * hd] gets every chunk

@@ -114,16 +114,13 @@ struct sli_model {
         float *x = nullptr, *xpart = nullptr, *q = nullptr;  // [chunk][D], [chunk][D] (TP partials), [chunk][hq hd]
         __half *hhi = nullptr, *hlo = nullptr;  // [chunk][max(D, hq hd)]: normed x / attention out, fp16 hi + lo
         __half *ahi = nullptr, *alo = nullptr;  // [chunk][Il]: SwiGLU out, fp16 hi + lo
-        sli::PfState* ps = nullptr;             // chunk start position + valid rows (device)
+        // a chunk's rows are 16-row groups of one sequence (sli_model_prefill) or of several (sli_model_prefill_seqs):
+        // the group table (device) and the graphs per chunk size
+        sli::PfSegs* segs = nullptr;
         hipGraph_t graph[4] = {};
         hipGraphExec_t exec[4] = {};
-        // sli_model_prefill_seqs: a chunk's rows are 16-row groups of several sequences; the group table (device) and
-        // the graphs of the table form, per chunk size
-        sli::PfSegs* segs = nullptr;
-        hipGraph_t sgraph[4] = {};
-        hipGraphExec_t sexec[4] = {};
-        // sli_model_score_seqs: a table chunk, then the final norm, the LM head over the chunk rows (role 3) and the
-        // score launch (score.h). Graphs of their own: sgraph / sexec above stay what they were, node for node. The
+        // sli_model_score_seqs: a chunk, then the final norm, the LM head over the chunk rows (role 3) and the
+        // score launch (score.h). Graphs of their own: graph / exec above stay what they were, node for node. The
         // logits chunk [chunk][vld] and the position-indexed results [B][T + 1] are allocated at the first scoring call.
         hipGraph_t scgraph[4] = {};
         hipGraphExec_t scexec[4] = {};
@@ -1170,7 +1167,7 @@ struct StepRecorder {
         } else {
             const PgIn<WT> in{(const WT*)W, hi, lo, N, K, M, MX ? (const uint8_t*)Ws : nullptr};
             return pg_pick<WT>(M, role, [&](auto cfg) -> int {
-                SLI_HIP((launch_pgemm<Epi, decltype(cfg), WT>(in, e, m->pf.ps, m->stream)));
+                SLI_HIP((launch_pgemm<Epi, decltype(cfg), WT>(in, e, m->stream)));
                 return SLI_OK;
             });
         }
@@ -1182,34 +1179,19 @@ struct StepRecorder {
     }
     static int prepare_prefill(sli_model* m) {
         SLI_TRY(allow_pg<PgEpiQKV<KT>>(m));
-        if constexpr (!std::is_same<KT, float>::value) SLI_TRY(allow_pg<PgEpiQKVSegs<KT>>(m));
         SLI_TRY(allow_pg<PgEpiResid>(m));
         SLI_TRY(allow_pg<PgEpiSwiGLU>(m));
         return SLI_OK;
     }
-    // SEGS: the chunk's rows are 16-row groups of several sequences of a batched model (the table f.segs, prefill.h
-    // PfSegs; sli_model_prefill_seqs): the embedding, the q/k/v epilogue and the attention take the table and the
-    // cache's layer stride counts every sequence; the other launches are the same
-    template <bool SEGS = false>
+    // The chunk's rows are the 16-row groups of the table f.segs (prefill.h PfSegs): the embedding, the q/k/v epilogue
+    // and the attention read it; the other launches see independent chunk rows.
     static int record_pf_phase(sli_model* m, int p, int M) {
-        if constexpr (SEGS && std::is_same<KT, float>::value) {
-            return fail(SLI_ERR_STATE, "prefill_seqs needs an fp16 or FP8 K/V cache");
-        } else {
-            return record_pf_phase_rm<SEGS>(m, p, M);
-        }
-    }
-    template <bool SEGS>
-    static int record_pf_phase_rm(sli_model* m, int p, int M) {
         auto& f = m->pf;
         hipStream_t s = m->stream;
         const int D = m->D, hd = m->hd, QD = m->hq * hd;
         if (p == 0) {
-            if constexpr (SEGS)
-                hipLaunchKernelGGL((pf_embed_kernel<WT, PfSegs>), dim3(M), dim3(256), 0, s, f.segs, m->prompt,
-                                   (const WT*)m->emb, (const void*)m->emb_s, f.x, D, m->T + 1);
-            else
-                hipLaunchKernelGGL((pf_embed_kernel<WT, PfState>), dim3(M), dim3(256), 0, s, f.ps, m->prompt,
-                                   (const WT*)m->emb, (const void*)m->emb_s, f.x, D, 0);
+            hipLaunchKernelGGL((pf_embed_kernel<WT>), dim3(M), dim3(256), 0, s, f.segs, m->prompt, (const WT*)m->emb,
+                               (const void*)m->emb_s, f.x, D, m->T + 1);
             SLI_HIP(hipGetLastError());
         }
         const int l = p / 2;
@@ -1222,20 +1204,14 @@ struct StepRecorder {
                            D, m->c.eps);
         SLI_HIP(hipGetLastError());
         if (p % 2 == 0) {
-            const size_t ls = (size_t)l * (SEGS ? m->B : 1) * m->hkv * m->T * hd;  // the cache is [L][B][hkv][T][hd]
+            const size_t ls = (size_t)l * m->B * m->hkv * m->T * hd;  // the cache is [L][B][hkv][T][hd]
             PgEpiQKV<KT> eq{f.q, (KT*)m->kc + ls, (KT*)m->vc + ls, rs(w.qkv_s), m->sin_t, m->cos_t, m->hq, m->hkv, hd,
-                            m->T};
+                            m->T, f.segs};
             PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
                               1.0f / sqrtf((float)hd)};
-            if constexpr (SEGS) {
-                SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, PgEpiQKVSegs<KT>{eq, f.segs},
-                           M, 0));
-                SLI_HIP(launch_pf_attn<KT>(aa, hd, M, (const PfSegs*)f.segs, s));
-            } else {
-                SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
-                // fp16 / FP8 cache: MFMA; fp32: VALU (prefill.h)
-                SLI_HIP(launch_pf_attn<KT>(aa, hd, M, (const PfState*)f.ps, s));
-            }
+            SLI_TRY(pg(m, w.qkv, w.qkv_s, (m->hq + 2 * m->hkv) * hd, D, f.hhi, f.hlo, eq, M, 0));
+            // fp16 / FP8 cache: MFMA; fp32: VALU, one sequence only (prefill.h; the packed routes refuse an fp32 cache)
+            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.segs, s));
             er.rscale = rs(w.wo_s);
             return pg(m, w.wo, w.wo_s, D, QD, f.hhi, f.hlo, er, M, 2);
         }
@@ -1244,6 +1220,7 @@ struct StepRecorder {
         er.rscale = rs(w.down_s);
         return pg(m, w.down, w.down_s, D, m->Il, f.ahi, f.alo, er, M, 2);
     }
+    // a chunk of any route but the in-process group's; a single-rank model has no exchange
     static int record_prefill(sli_model* m, int M) {
         for (int p = 0; p < 2 * m->L; ++p) {
             SLI_TRY(record_pf_phase(m, p, M));
@@ -1255,17 +1232,12 @@ struct StepRecorder {
         }
         return SLI_OK;
     }
-    // a chunk of sli_model_prefill_seqs (single-rank models: no exchange)
-    static int record_prefill_segs(sli_model* m, int M) {
-        for (int p = 0; p < 2 * m->L; ++p) SLI_TRY(record_pf_phase<true>(m, p, M));
-        return SLI_OK;
-    }
     // a chunk of sli_model_score_seqs: the same launches, then the final norm (index 2L), the LM head over the chunk's
     // rows (the embedding table in the model's weight format, role 3) and the group-table score launch (score.h): the
     // hidden state of position t scores the prompt's token t + 1
     static int score_vld(const sli_model* m) { return (m->V + 3) & ~3; }
     static int record_score_segs(sli_model* m, int M) {
-        SLI_TRY(record_prefill_segs(m, M));
+        SLI_TRY(record_prefill(m, M));
         auto& f = m->pf;
         hipLaunchKernelGGL(pf_norm_split_kernel, dim3(M), dim3(256), 0, m->stream, f.x,
                            m->norms + (size_t)(2 * m->L) * m->D, f.hhi, f.hlo, m->D, m->c.eps);
@@ -1550,8 +1522,6 @@ static void destroy(sli_model* m) {
     for (int b = 0; b < 4; ++b) {
         if (m->pf.exec[b]) (void)hipGraphExecDestroy(m->pf.exec[b]);
         if (m->pf.graph[b]) (void)hipGraphDestroy(m->pf.graph[b]);
-        if (m->pf.sexec[b]) (void)hipGraphExecDestroy(m->pf.sexec[b]);
-        if (m->pf.sgraph[b]) (void)hipGraphDestroy(m->pf.sgraph[b]);
         if (m->pf.scexec[b]) (void)hipGraphExecDestroy(m->pf.scexec[b]);
         if (m->pf.scgraph[b]) (void)hipGraphDestroy(m->pf.scgraph[b]);
     }
@@ -2014,11 +1984,14 @@ static int get_state(sli_model* m, int seq, int32_t* pos, int32_t* token, int32_
 // half last stage). A multi-process TP rank without an RCCL communicator (SLI_DEBUG_NOCOMM, with or without the
 // one-shot exchange) has no all-reduce for a chunk's M x D residual rows, so it prefills through the decode step,
 // whose exchange it does have; an in-process group sums the chunk rows itself (record_group_prefill).
+// the shapes the prefill kernels take (every route's predicate)
+static bool pf_shape_ok(const sli_model* m) {
+    return (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 && m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
+}
 static bool pf_supported(const sli_model* m, int mode) {
     if (m->partial && !m->collectives && !m->group) return false;
     if (m->c.kv_dtype == SLI_DT_F8E4M3 && mode != SLI_PREFILL_GEMM_KV8) return false;  // opt-in (sli.h)
-    return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && (m->hd == 64 || m->hd == 128) && m->D % 64 == 0 &&
-           m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0;
+    return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && pf_shape_ok(m);
 }
 // What the next prefill runs (sli_model_set_prefill): the chunks are captured graphs of the GEMM path alone and the
 // stepwise path replays the decode graph, so the mode only selects which of the two is launched; nothing captured
@@ -2060,17 +2033,67 @@ static int pf_alloc(sli_model* m) {
     A((void**)&p.hlo, sizeof(__half) * M * std::max(D, QD));
     A((void**)&p.ahi, sizeof(__half) * M * m->Il);
     A((void**)&p.alo, sizeof(__half) * M * m->Il);
-    A((void**)&p.ps, sizeof(PfState));
     A((void**)&p.segs, sizeof(PfSegs));
     if (rc != SLI_OK) return rc;
     return SLI_DISPATCH(m, prepare_prefill, m);
 }
 
-// chunk c of the prompt's n - 1 prefilled positions
-static std::vector<PfState> pf_chunks(int n) {
-    std::vector<PfState> cs;
-    for (int p0 = 0; p0 < n - 1; p0 += kPfMaxChunk) cs.push_back(PfState{p0, std::min(kPfMaxChunk, n - 1 - p0)});
-    return cs;
+// The packing rule (sli.h at sli_prefill_pack): each listed sequence's positions 0 .. n-2 cut into groups of 16
+// aligned on its own positions, the groups concatenated in list order, 16 groups (kPfMaxChunk rows) to a chunk, the
+// last chunk the smallest of kPfSizes that holds its groups, padded with nv == 0 groups. A padding group names the
+// sequence of the last real group at position 0: the rows' tokens and RoPE positions stay in range. The one planner:
+// a batch-1 prompt is the plan of the one sequence 0 (chunks of up to kPfMaxChunk consecutive positions).
+struct PfPlan {
+    std::vector<sli_pf_group> groups;  // of all chunks, padding included
+    std::vector<int32_t> rows;         // per chunk
+};
+// chunk c's table: its groups, the entries it lacks padding groups
+static PfSegs pf_table(const PfPlan& pl, size_t c) {
+    PfSegs t;
+    for (int g = 0; g < kPfGroups; ++g) {
+        const size_t i = c * kPfGroups + g;
+        const sli_pf_group gr = i < pl.groups.size() ? pl.groups[i] : sli_pf_group{pl.groups.back().seq, 0, 0};
+        t.seq[g] = gr.seq;
+        t.p0[g] = gr.p0;
+        t.nv[g] = gr.nv;
+    }
+    return t;
+}
+static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
+    PfPlan pl;
+    for (int i = 0; i < n_seqs; ++i)
+        for (int p0 = 0; p0 < lens[i] - 1; p0 += 16)
+            pl.groups.push_back(sli_pf_group{seqs[i], p0, std::min(16, lens[i] - 1 - p0)});
+    const int ng = (int)pl.groups.size();
+    for (int g0 = 0; g0 < ng; g0 += kPfGroups) {
+        const int rows = kPfSizes[pf_bucket(16 * std::min(kPfGroups, ng - g0))];
+        pl.rows.push_back(rows);
+    }
+    if (ng) {
+        const int total = (ng - 1) / kPfGroups * kPfGroups + pl.rows.back() / 16;
+        const int32_t pad_seq = pl.groups.back().seq;
+        pl.groups.resize(total, sli_pf_group{pad_seq, 0, 0});
+    }
+    return pl;
+}
+// Enqueues a plan on `stream`: a graph per chunk size it lacks (record(M): the launches of an M-row chunk), captured
+// before anything is enqueued behind the capture; then per chunk its table, copied to every entry of `dev` (an
+// in-process group: every rank's), and its graph, back to back. tabs holds the host tables: the caller keeps it until
+// it has waited for the stream.
+template <class Rec>
+static int pf_enqueue(const PfPlan& pl, std::vector<PfSegs>& tabs, hipStream_t stream, hipGraph_t* graph,
+                      hipGraphExec_t* exec, const std::vector<PfSegs*>& dev, Rec record) {
+    for (int rows : pl.rows) {
+        const int b = pf_bucket(rows);
+        SLI_TRY(capture_graph(stream, graph[b], exec[b], [&]() { return record(kPfSizes[b]); }));
+    }
+    tabs.resize(pl.rows.size());
+    for (size_t c = 0; c < pl.rows.size(); ++c) tabs[c] = pf_table(pl, c);
+    for (size_t c = 0; c < pl.rows.size(); ++c) {  // each copy reads its own element of tabs
+        for (PfSegs* d : dev) SLI_HIP(hipMemcpyAsync(d, &tabs[c], sizeof(PfSegs), hipMemcpyHostToDevice, stream));
+        SLI_HIP(hipGraphLaunch(exec[pf_bucket(pl.rows[c])], stream));
+    }
+    return SLI_OK;
 }
 
 extern "C" int sli_model_prefill_path(const sli_model* m) { return m && m->B == 1 && pf_use_gemm(m) ? 1 : 0; }
@@ -2110,16 +2133,10 @@ extern "C" int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n) {
     SLI_HIP(hipMemcpyAsync(m->hist, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, m->stream));
     if (n > 1 && pf_use_gemm(m)) {
         SLI_TRY(pf_alloc(m));
-        const std::vector<PfState> cs = pf_chunks(n);
-        for (const PfState& c : cs) {  // capture before anything is enqueued behind the capture
-            const int b = pf_bucket(c.nv);
-            SLI_TRY(capture_graph(m->stream, m->pf.graph[b], m->pf.exec[b],
-                                  [&]() { return SLI_DISPATCH(m, record_prefill, m, kPfSizes[b]); }));
-        }
-        for (const PfState& c : cs) {  // each copy reads its own element of cs: enqueued back to back
-            SLI_HIP(hipMemcpyAsync(m->pf.ps, &c, sizeof(PfState), hipMemcpyHostToDevice, m->stream));
-            SLI_HIP(hipGraphLaunch(m->pf.exec[pf_bucket(c.nv)], m->stream));
-        }
+        const int32_t seq0 = 0;
+        std::vector<PfSegs> tabs;
+        SLI_TRY(pf_enqueue(pf_pack(&seq0, &n, 1), tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
+                           [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
         SLI_TRY(wait_stream(m));
     } else {
         for (int p = 0; p < n - 1; ++p) {  // the decode step, teacher-forced (model.cpp:159-165)
@@ -2143,17 +2160,12 @@ extern "C" int sli_tp_group_prefill(sli_tp_group* g, const int32_t* ids, int32_t
     }
     if (n > 1 && pf_use_gemm(m0)) {
         for (sli_model* m : g->ranks) SLI_TRY(pf_alloc(m));
-        const std::vector<PfState> cs = pf_chunks(n);
-        for (const PfState& c : cs) {
-            const int b = pf_bucket(c.nv);
-            SLI_TRY(capture_graph(g->stream, g->pf_graph[b], g->pf_exec[b],
-                                  [&]() { return SLI_DISPATCH(m0, record_group_prefill, g, kPfSizes[b]); }));
-        }
-        for (const PfState& c : cs) {
-            for (sli_model* m : g->ranks)
-                SLI_HIP(hipMemcpyAsync(m->pf.ps, &c, sizeof(PfState), hipMemcpyHostToDevice, g->stream));
-            SLI_HIP(hipGraphLaunch(g->pf_exec[pf_bucket(c.nv)], g->stream));
-        }
+        const int32_t seq0 = 0;
+        std::vector<PfSegs> tabs;
+        std::vector<PfSegs*> dev;
+        for (sli_model* m : g->ranks) dev.push_back(m->pf.segs);
+        SLI_TRY(pf_enqueue(pf_pack(&seq0, &n, 1), tabs, g->stream, g->pf_graph, g->pf_exec, dev,
+                           [&](int M) { return SLI_DISPATCH(m0, record_group_prefill, g, M); }));
         SLI_HIP(hipStreamSynchronize(g->stream));
     } else {
         for (int p = 0; p < n - 1; ++p) {
@@ -2183,32 +2195,6 @@ extern "C" int sli_model_predict_prefill(sli_model* m, const int32_t* prompt, in
 }
 
 // ---------------------------------------------------------------- packed prefill of a batched model's sequences
-// The packing rule (sli.h at sli_prefill_pack): each listed sequence's positions 0 .. n-2 cut into groups of 16
-// aligned on its own positions, the groups concatenated in list order, 16 groups (kPfMaxChunk rows) to a chunk, the
-// last chunk the smallest of kPfSizes that holds its groups, padded with nv == 0 groups. A padding group names the
-// sequence of the last real group at position 0: the rows' tokens and RoPE positions stay in range.
-struct PfPlan {
-    std::vector<sli_pf_group> groups;  // of all chunks, padding included
-    std::vector<int32_t> rows;         // per chunk
-};
-static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
-    PfPlan pl;
-    for (int i = 0; i < n_seqs; ++i)
-        for (int p0 = 0; p0 < lens[i] - 1; p0 += 16)
-            pl.groups.push_back(sli_pf_group{seqs[i], p0, std::min(16, lens[i] - 1 - p0)});
-    const int ng = (int)pl.groups.size();
-    for (int g0 = 0; g0 < ng; g0 += kPfGroups) {
-        const int rows = kPfSizes[pf_bucket(16 * std::min(kPfGroups, ng - g0))];
-        pl.rows.push_back(rows);
-    }
-    if (ng) {
-        const int total = (ng - 1) / kPfGroups * kPfGroups + pl.rows.back() / 16;
-        const int32_t pad_seq = pl.groups.back().seq;
-        pl.groups.resize(total, sli_pf_group{pad_seq, 0, 0});
-    }
-    return pl;
-}
-
 extern "C" int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, sli_pf_group* groups,
                                 int32_t cap_groups, int32_t* chunk_rows, int32_t cap_chunks, int32_t* n_chunks) {
     SLI_CHECK(seqs && lens && n_chunks && (groups || cap_groups == 0) && (chunk_rows || cap_chunks == 0), SLI_ERR_ARG,
@@ -2231,7 +2217,7 @@ static const char* pf_seqs_why(const sli_model* m) {
     if (m->c.tp_size > 1 || m->partial) return "prefill_seqs: single-rank models (no tensor parallelism)";
     if (m->c.w_dtype == SLI_DT_F32) return "prefill_seqs: fp32 weights have no GEMM prefill";
     if (m->c.kv_dtype == SLI_DT_F32) return "prefill_seqs: an fp32 K/V cache has no group-table attention";
-    if (!((m->hd == 64 || m->hd == 128) && m->D % 64 == 0 && m->D <= 8192 && m->Il % 64 == 0 && (m->hq * m->hd) % 64 == 0))
+    if (!pf_shape_ok(m))
         return "prefill_seqs: head_dim must be 64 / 128 and the projection depths multiples of 64 (dim <= 8192)";
     return nullptr;
 }
@@ -2328,31 +2314,13 @@ static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const 
     const PfPlan pl = pf_pack(seqs, lens, n_seqs);
     if (!pl.rows.empty()) {
         SLI_TRY(pf_alloc(m));
-        for (int rows : pl.rows) {  // capture before anything is enqueued behind the capture
-            const int b = pf_bucket(rows);
-            if (score)
-                SLI_TRY(capture_graph(m->stream, m->pf.scgraph[b], m->pf.scexec[b],
-                                      [&]() { return SLI_DISPATCH(m, record_score_segs, m, kPfSizes[b]); }));
-            else
-                SLI_TRY(capture_graph(m->stream, m->pf.sgraph[b], m->pf.sexec[b],
-                                      [&]() { return SLI_DISPATCH(m, record_prefill_segs, m, kPfSizes[b]); }));
-        }
-        // each chunk's table (the groups it lacks: padding) and its graph, enqueued back to back
-        std::vector<PfSegs> tabs(pl.rows.size());
-        for (size_t c = 0; c < pl.rows.size(); ++c) {
-            const int pad_seq = pl.groups.back().seq;
-            for (int g = 0; g < kPfGroups; ++g) {
-                const size_t i = c * kPfGroups + g;
-                const sli_pf_group gr = i < pl.groups.size() ? pl.groups[i] : sli_pf_group{pad_seq, 0, 0};
-                tabs[c].seq[g] = gr.seq;
-                tabs[c].p0[g] = gr.p0;
-                tabs[c].nv[g] = gr.nv;
-            }
-        }
-        for (size_t c = 0; c < pl.rows.size(); ++c) {
-            SLI_HIP(hipMemcpyAsync(m->pf.segs, &tabs[c], sizeof(PfSegs), hipMemcpyHostToDevice, m->stream));
-            SLI_HIP(hipGraphLaunch((score ? m->pf.scexec : m->pf.sexec)[pf_bucket(pl.rows[c])], m->stream));
-        }
+        std::vector<PfSegs> tabs;
+        if (score)
+            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.scgraph, m->pf.scexec, {m->pf.segs},
+                               [&](int M) { return SLI_DISPATCH(m, record_score_segs, m, M); }));
+        else
+            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
+                               [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
         SLI_TRY(wait_stream(m));
     }
     if (score) {  // entry (i, t), 1 <= t < lens[i]: slot (seqs[i], t) of the device buffers; everything else is empty

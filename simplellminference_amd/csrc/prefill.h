@@ -27,11 +27,11 @@
 // weight type changes. int8 and MXFP4: stages of 128 k; a depth that is 64 mod 128 (e.g. Llama-2-7B int8 down at
 // TP 4, 2752) ends with a half stage. MXFP4: the ring carries a scale image per stage too, and the block scale is
 // applied to each k-block's tile in fp32 (PgMx).
-// The chunk's start position and valid count live in device memory (PfState), so one captured graph per
-// chunk size serves every chunk of every prompt.
-// A batched model's chunk carries 16-row groups of several sequences instead (PfSegs, a device-resident group table:
-// sli_model_prefill_seqs). The kernels that know a row's position (embedding, q/k/v epilogue, MFMA chunk attention) are
-// parameterised on that row map, PfState or PfSegs; everything else sees independent chunk rows either way.
+// Which prompt position a chunk row is stands in device memory (PfSegs, the group table: 16-row groups, each a run of
+// one sequence's positions), so one captured graph per chunk size serves every chunk of every prompt. A batch-1
+// prompt's chunk is the table of one sequence at consecutive positions; a batched model's packed chunk
+// (sli_model_prefill_seqs) carries groups of several sequences. The kernels that know a row's position (embedding,
+// q/k/v epilogue, chunk attention) read the table; everything else sees independent chunk rows.
 #pragma once
 #include <type_traits>
 
@@ -44,39 +44,29 @@ namespace sli {
 
 constexpr int kPfMaxChunk = 256;  // prompt positions per weight pass
 
-struct PfState {
-    int32_t p0;  // position of chunk row 0
-    int32_t nv;  // valid chunk rows (the rest is padding: computed, never written to the cache)
-};
-
-// The row map of a packed chunk: chunk rows 16 g .. 16 g + 15 are positions p0[g] .. p0[g] + 15 of sequence seq[g]
-// (p0 % 16 == 0: a row keeps the 15 group-mates it has in a PfState chunk, so its attention tiles are the same), the
-// first nv[g] of them valid; nv[g] == 0 is a padding group, which writes nothing to the cache and skips its attention.
+// The row map of a chunk: chunk rows 16 g .. 16 g + 15 are positions p0[g] .. p0[g] + 15 of sequence seq[g], the first
+// nv[g] of them valid (the rest is padding: computed, never written to the cache); nv[g] == 0 is a padding group,
+// which writes nothing to the cache and skips its attention. The engine's plans keep p0 % 16 == 0, so a row has the
+// same 15 group-mates, and so the same attention tiles, however its sequence is packed; the kernels
+// themselves take any p0.
 constexpr int kPfGroups = kPfMaxChunk / 16;
 struct PfSegs {
     int32_t seq[kPfGroups], p0[kPfGroups], nv[kPfGroups];
 };
 
-// group g of a chunk under either row map: its sequence, first position and valid rows (PfState: nv may be <= 0 or
-// > 16, only row < nv is asked of it)
-struct PfGrp {
-    int seq, p0, nv;
-};
-__device__ __forceinline__ PfGrp pf_grp(const PfState* ps, int g) { return PfGrp{0, ps->p0 + 16 * g, ps->nv - 16 * g}; }
-__device__ __forceinline__ PfGrp pf_grp(const PfSegs* ps, int g) { return PfGrp{ps->seq[g], ps->p0[g], ps->nv[g]}; }
-// where chunk row m's token lies in the prompt buffer ([sequence][pld]); padding rows repeat the last valid token
-__device__ __forceinline__ int pf_tok(const PfState* ps, int m, int) { return ps->p0 + min(m, ps->nv - 1); }
+// where chunk row m's token lies in the prompt buffer ([sequence][pld]); a group's padding rows repeat its last valid
+// token, a padding group its first
 __device__ __forceinline__ int pf_tok(const PfSegs* ps, int m, int pld) {
     const int g = m >> 4;
     return ps->seq[g] * pld + ps->p0[g] + min(m & 15, max(ps->nv[g] - 1, 0));
 }
 
 // ---------------------------------------------------------------- 1. embedding + RMSNorm / split
-// x[m] = emb[prompt[p0 + m]] (emb_kernel.cpp:4-21; padding rows repeat the last valid token). emb_s: the int8 table's
-// fp32 row scales (nullable), or the MXFP4 table's block scale bytes (mxfp4.h layout: a table decode per element)
-// RM: the row map (PfState, or PfSegs: row m's token comes from its sequence's prompt row, pld ids apart).
-template <typename WT, class RM>
-__global__ void __launch_bounds__(256) pf_embed_kernel(const RM* __restrict__ ps, const int32_t* __restrict__ prompt,
+// x[m] = emb[token of chunk row m] (emb_kernel.cpp:4-21; pf_tok: row m's token comes from its sequence's prompt row,
+// pld ids apart). emb_s: the int8 table's fp32 row scales (nullable), or the MXFP4 table's block scale bytes (mxfp4.h
+// layout: a table decode per element)
+template <typename WT>
+__global__ void __launch_bounds__(256) pf_embed_kernel(const PfSegs* __restrict__ ps, const int32_t* __restrict__ prompt,
                                                       const WT* __restrict__ emb, const void* __restrict__ emb_s,
                                                       float* __restrict__ x, int D, int pld) {
     const int m = blockIdx.x;
@@ -321,7 +311,7 @@ __device__ __forceinline__ void pg_wait_stages(int later) {
 }
 
 template <class Epi, class Cfg, typename WT>
-__global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi epi, const PfState* __restrict__ ps) {
+__global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi epi) {
     using Geo = PgGeo<Cfg, WT>;
     using F = typename Geo::F;
     constexpr int KBS = Geo::KBS, BM = Geo::BM, WR = Geo::WR, S = Geo::S, AT = Geo::AT, NA = Geo::NA, WPT = Geo::WPT;
@@ -533,7 +523,7 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
         for (int b = 0; b < WPT; ++b) {
             const int m = pb * BM + (wp * WPT + b) * 16 + r16;
             const float v[4] = {acc[a][b][0], acc[a][b][1], acc[a][b][2], acc[a][b][3]};
-            epi.store(t, i0, m, v, ps);
+            epi.store(t, i0, m, v);
         }
     }
 }
@@ -541,23 +531,31 @@ __global__ void __launch_bounds__(128 * Cfg::WR) pgemm_kernel(PgIn<WT> in, Epi e
 // ---- epilogues. Tiles hold 4-row groups {first(u), first(u + 1), second(u), second(u + 1)} where a pair is a
 // RoPE pair {d, d + hd/2} (q/k/v) or {gate u, up u}, so each lane's 4 rows are 2 complete pairs.
 template <typename KT>
-struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows of the cache at p0 + m (KT: float,
-                   // __half, or f8e4m3: codes)
+struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows of the cache at the row's position (KT:
+                   // float, __half, or f8e4m3: codes). Chunk row m = 16 g + r is position p0[g] + r of sequence seq[g],
+                   // written for r < nv[g].
     float* q;
-    KT* kc;  // this layer's cache base [hkv][T][hd]
+    KT* kc;  // this layer's cache of every sequence [B][hkv][T][hd] (a batch-1 model: B = 1)
     KT* vc;
     const float* rscale;  // int8 row scales (nullable)
     const float* sin_t;
     const float* cos_t;
     int hq, hkv, hd, T;
+    const PfSegs* segs;
     __device__ int row(int t, int i) const {
         const int half = hd >> 1;
         const int u = t * 8 + (i >> 2) * 2 + (i & 1);
         const int uh = u / half, d = u - uh * half;
         return uh * hd + d + ((i & 2) ? half : 0);
     }
-    __device__ void store(int t, int i0, int m, const float* v, const PfState* ps) const {
-        store_at(t, i0, m, v, ps->p0 + m, m < ps->nv, 0);
+    __device__ void store(int t, int i0, int m, const float* v) const {
+        // A wave's rows of one call are one group (pgemm_kernel: m = 16 * position tile + lane % 16), and nothing writes
+        // the table while a kernel runs. Said outright (the uniform index, the constant address space) the three reads
+        // are scalar loads that need not wait behind the stores of the call before; left to the compiler they were
+        // vector loads, one dependent round trip per call.
+        const int g = __builtin_amdgcn_readfirstlane(m >> 4), r = m & 15;
+        const auto* tb = (const __attribute__((address_space(4))) PfSegs*)segs;
+        store_at(t, i0, m, v, tb->p0[g] + r, r < tb->nv[g], (size_t)tb->seq[g] * hkv * T * hd);
     }
     // pos: chunk row m's position; valid: its K / V rows are written (where pos < T); kv0: its sequence's offset in
     // kc / vc (elements)
@@ -611,27 +609,13 @@ struct PgEpiQKV {  // model.cpp:52-67: q (fp32 [M][hq*hd]), rotated k / v rows o
     }
 };
 
-// The q/k/v epilogue under the group table: kc / vc are one layer's cache of every sequence, [B][hkv][T][hd]; chunk row
-// m = 16 g + r is position p0[g] + r of sequence seq[g], written for r < nv[g]. The table travels with the epilogue
-// (pgemm_kernel's PfState argument is not read).
-template <typename KT>
-struct PgEpiQKVSegs {
-    PgEpiQKV<KT> e;
-    const PfSegs* segs;
-    __device__ int row(int t, int i) const { return e.row(t, i); }
-    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
-        const int g = m >> 4, r = m & 15;
-        e.store_at(t, i0, m, v, segs->p0[g] + r, r < segs->nv[g], (size_t)segs->seq[g] * e.hkv * e.T * e.hd);
-    }
-};
-
 struct PgEpiSwiGLU {  // model.cpp:99-115: act = sigmoid(g) * u (or SiLU), stored as the down GEMM's hi / lo
     __half* ahi;
     __half* alo;
     const float* rscale;
     int inter, silu;
     __device__ int row(int t, int i) const { return t * 8 + (i >> 2) * 2 + (i & 1) + ((i & 2) ? inter : 0); }
-    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
+    __device__ void store(int t, int i0, int m, const float* v) const {
         const int u = t * 8 + (i0 >> 2) * 2;  // units u, u + 1: one 4-byte hi and lo store each
         __half hh[2], hl[2];
 #pragma unroll
@@ -656,7 +640,7 @@ struct PgEpiResid {  // y[m][row] = resid[m][row] + sum * row scale (matmul_kern
     const float* rscale;
     int nrows, ld;
     __device__ int row(int t, int i) const { return min(t * 16 + i, nrows - 1); }
-    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
+    __device__ void store(int t, int i0, int m, const float* v) const {
         const int row = t * 16 + i0;  // rows row .. row + 3 (nrows % 16 == 0: the host's check)
         const size_t i = (size_t)m * ld + row;
         float4 p = make_float4(v[0], v[1], v[2], v[3]);
@@ -682,7 +666,7 @@ struct PgEpiLogits {
     const float* rscale;
     int nrows, ld;
     __device__ int row(int t, int i) const { return min(t * 16 + i, nrows - 1); }
-    __device__ void store(int t, int i0, int m, const float* v, const PfState*) const {
+    __device__ void store(int t, int i0, int m, const float* v) const {
         const int row = t * 16 + i0;
         const size_t i = (size_t)m * ld + row;
         if (row + 3 < nrows) {
@@ -703,12 +687,12 @@ struct PgEpiLogits {
 constexpr int pg_logits_n(int nrows) { return (nrows + 15) & ~15; }
 
 template <class Epi, class Cfg, typename WT>
-hipError_t launch_pgemm(const PgIn<WT>& in, const Epi& epi, const PfState* ps, hipStream_t s) {
+hipError_t launch_pgemm(const PgIn<WT>& in, const Epi& epi, hipStream_t s) {
     using Geo = PgGeo<Cfg, WT>;
     const int nrb = (in.N + Geo::BN - 1) / Geo::BN;
     const int nrb8 = (nrb + 7) / 8 * 8;
     const dim3 grid(nrb8 * (in.M / Geo::BM));
-    hipLaunchKernelGGL((pgemm_kernel<Epi, Cfg, WT>), grid, dim3(Geo::THREADS), Geo::LDS, s, in, epi, ps);
+    hipLaunchKernelGGL((pgemm_kernel<Epi, Cfg, WT>), grid, dim3(Geo::THREADS), Geo::LDS, s, in, epi);
     return hipGetLastError();
 }
 
@@ -773,6 +757,9 @@ hipError_t pg_allow_lds_all() {
 // grid (M / 64, hq); 4 waves x 16 queries; lane l: query l & 15 of the wave, dims [c * HD/4, (c+1) * HD/4) with
 // c = l >> 4. Scores: the 4 lanes of a query add their quarter dot products (xor 16 / 32 exchanges); every lane
 // of a query keeps the same online-softmax state (m, l) and its quarter of o. Output attn / l as hi / lo.
+// A one-sequence kernel. Contract: the four groups of a 64-row block are consecutive positions of sequence 0, so the
+// block reads its start position from its first group, p0[4 * blockIdx.x], and never reads seq or nv. Every table
+// built for one sequence satisfies it (a padding group is computed like any other row; nothing reads its result).
 constexpr int kPaQB = 64;  // queries per workgroup
 constexpr int kPaKT = 64;  // keys per LDS tile
 
@@ -788,17 +775,18 @@ struct PfAttnArgs {
 };
 
 template <typename KT, int HD>
-__global__ void __launch_bounds__(256) pf_attn_kernel(PfAttnArgs<KT> a, const PfState* __restrict__ ps) {
+__global__ void __launch_bounds__(256) pf_attn_kernel(PfAttnArgs<KT> a, const PfSegs* __restrict__ ps) {
     constexpr int QD = HD / 4;  // dims per lane
     __shared__ __attribute__((aligned(16))) KT ks[kPaKT][HD];
     __shared__ __attribute__((aligned(16))) KT vs[kPaKT][HD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.y, G = a.hq / a.hkv, kvh = h / G;
-    const int p0 = ps->p0;
-    const int mi = blockIdx.x * kPaQB + wave * 16 + (lane & 15);  // this lane's query (chunk row)
+    const int p0 = ps->p0[(kPaQB / 16) * blockIdx.x];             // position of the block's row 0
+    const int mb = wave * 16 + (lane & 15);                       // this lane's row of the block
+    const int mi = blockIdx.x * kPaQB + mb;                       // its query (chunk row)
     const int c = lane >> 4;
-    const int pos = p0 + mi;                                      // its position
-    const int pos_max = p0 + blockIdx.x * kPaQB + kPaQB - 1;      // the block's last query position
+    const int pos = p0 + mb;                                      // its position
+    const int pos_max = p0 + kPaQB - 1;                           // the block's last query position
     const int nt = min(pos_max, a.T - 1) / kPaKT + 1;             // key tiles
     float qv[QD], o[QD];
 #pragma unroll
@@ -886,10 +874,10 @@ struct PaGeo {
     static_assert(PIECES >= 2 && PIECES % 2 == 0 && 1024 % ROWB == 0, "whole 1-KiB pieces per K and per V image");
 };
 
-// RM: the row map. PfState: workgroup x is rows 16 x .. of the chunk's one sequence. PfSegs: it is group x of the
-// table, kc / vc hold every sequence's rows ([B][hkv][T][hd]) and a padding group leaves at once, as a whole.
-template <class F, int HD, class RM>
-__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F::KT> a, const RM* __restrict__ ps) {
+// Workgroup x is group x of the table; kc / vc hold every sequence's rows ([B][hkv][T][hd]) and a padding group leaves
+// at once, as a whole.
+template <class F, int HD>
+__global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F::KT> a, const PfSegs* __restrict__ ps) {
     using G = PaGeo<F, HD>;
     using KT = typename F::KT;
     constexpr int ND = HD / 32, NT = G::NT;  // 32-d blocks (S), 16-d tiles (O)
@@ -898,12 +886,12 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int g = lane >> 4, i16 = lane & 15;
     const int h = blockIdx.y, kvh = h / (a.hq / a.hkv);
-    const PfGrp gr = pf_grp(ps, (int)blockIdx.x);
+    const int gseq = ps->seq[blockIdx.x], gp0 = ps->p0[blockIdx.x];
     // (uniform: one table entry per workgroup; ahead of every barrier and DMA)
-    if (std::is_same<RM, PfSegs>::value && gr.nv == 0) return;
+    if (ps->nv[blockIdx.x] == 0) return;
     const int mq = blockIdx.x * 16 + i16;  // this lane's query (chunk row)
-    const int pos = gr.p0 + i16;
-    const int last = min(gr.p0 + 15, a.T - 1);  // the group's last query position
+    const int pos = gp0 + i16;
+    const int last = min(gp0 + 15, a.T - 1);  // the group's last query position
     const int ntiles = last / 32 + 1;
     const size_t qs = (size_t)a.hq * HD;
     // Qᵀ as the B operand: lane l = query l & 15, d = 32 db + 8 g .. +8, fp32 -> hi + lo
@@ -926,8 +914,8 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
     char* kimg = sm + wave * G::WAVE;
     const unsigned kbase = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)kimg;
     const unsigned vbase = kbase + G::IMG;
-    const KT* kc = a.kc + ((size_t)gr.seq * a.hkv + kvh) * a.T * HD;
-    const KT* vc = a.vc + ((size_t)gr.seq * a.hkv + kvh) * a.T * HD;
+    const KT* kc = a.kc + ((size_t)gseq * a.hkv + kvh) * a.T * HD;
+    const KT* vc = a.vc + ((size_t)gseq * a.hkv + kvh) * a.T * HD;
     for (int tt = wave; tt < ntiles; tt += 4) {
         const int t0 = tt * 32;
         // K pieces 0 .. P/2-1, V pieces P/2 .. P-1; lane i of a piece: row (piece rows) + i / CPR, physical
@@ -1041,20 +1029,20 @@ __global__ void __launch_bounds__(256) pf_attn_mfma_kernel(PfAttnArgs<typename F
 // The attention of M chunk rows (hd 64 or 128: the caller's check): an fp16 or FP8 cache on MFMA, 16 chunk rows per
 // workgroup; an fp32 cache on the VALU kernel, 64 chunk rows per workgroup, so at M = 32 it reads q and writes
 // ohi / olo for rows 32 .. 63 too (the buffers hold at least 64 rows). The engine and sli_prefill_attn launch
-// through here. Under a group table (PfSegs) the MFMA kernel alone.
+// through here. The VALU kernel is a one-sequence kernel (its contract stands at pf_attn_kernel: the four groups of a
+// 64-row block are consecutive positions of sequence 0); a packed table of several sequences takes the MFMA kernel
+// alone, and the callers that build one refuse an fp32 cache first.
 constexpr int pf_attn_rows(bool mfma_cache, int M) { return mfma_cache ? M : (M + kPaQB - 1) / kPaQB * kPaQB; }
 
-template <typename KT, class RM>
-hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const RM* ps, hipStream_t s) {
+template <typename KT>
+hipError_t launch_pf_attn(const PfAttnArgs<KT>& aa, int hd, int M, const PfSegs* ps, hipStream_t s) {
     if constexpr (!std::is_same<KT, float>::value) {
         using F = std::conditional_t<std::is_same<KT, f8e4m3>::value, AmF8, AmF16>;
         const dim3 ag(M / 16, aa.hq);
         if (hd == 128)
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 128, RM>), ag, dim3(256), 0, s, aa, ps);
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 128>), ag, dim3(256), 0, s, aa, ps);
         else
-            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 64, RM>), ag, dim3(256), 0, s, aa, ps);
-    } else if constexpr (!std::is_same<RM, PfState>::value) {
-        return hipErrorInvalidValue;  // the fp32-cache kernel has no group table (its callers refuse first)
+            hipLaunchKernelGGL((pf_attn_mfma_kernel<F, 64>), ag, dim3(256), 0, s, aa, ps);
     } else {
         const dim3 ag((M + kPaQB - 1) / kPaQB, aa.hq);
         if (hd == 128)

@@ -14,20 +14,28 @@
 
 namespace sli {
 
-__global__ void pf_set_state_kernel(PfState* ps, int p0, int nv) {
-    ps->p0 = p0;
-    ps->nv = nv;
+static_assert(sizeof(PfSegs) == SLI_PF_TABLE_BYTES, "sli.h states the table's size");
+
+// the group table of a chunk (prefill.h PfSegs), written on the stream: one dword per thread
+__global__ void pf_set_segs_kernel(PfSegs* dst, PfSegs v) {
+    reinterpret_cast<int32_t*>(dst)[threadIdx.x] = reinterpret_cast<const int32_t*>(&v)[threadIdx.x];
 }
 
-static int pf_set_state(void* state, int p0, int nv, hipStream_t s) {
-    hipLaunchKernelGGL(pf_set_state_kernel, dim3(1), dim3(1), 0, s, (PfState*)state, p0, nv);
+static int pf_put_segs(void* table, const PfSegs& v, hipStream_t s) {
+    hipLaunchKernelGGL(pf_set_segs_kernel, dim3(1), dim3(sizeof(PfSegs) / 4), 0, s, (PfSegs*)table, v);
     SLI_HIP(hipGetLastError());
     return SLI_OK;
 }
 
-// the group table of a packed chunk (prefill.h PfSegs), written on the stream: one dword per thread
-__global__ void pf_set_segs_kernel(PfSegs* dst, PfSegs v) {
-    reinterpret_cast<int32_t*>(dst)[threadIdx.x] = reinterpret_cast<const int32_t*>(&v)[threadIdx.x];
+// the plain entries' table: M rows of one sequence from p0 on, the first nv valid (any p0: the kernels need no
+// alignment, only the packed route's bit-equality argument does)
+static int pf_set_run(void* table, int p0, int nv, int M, hipStream_t s) {
+    PfSegs v{};
+    for (int g = 0; g < M / 16; ++g) {
+        v.p0[g] = p0 + 16 * g;
+        v.nv[g] = std::min(std::max(nv - 16 * g, 0), 16);
+    }
+    return pf_put_segs(table, v, s);
 }
 
 // groups: M / 16 host entries; the table's other entries are padding groups
@@ -45,9 +53,7 @@ static int pf_set_segs(void* table, const sli_pf_group* groups, int M, int B, in
         v.p0[g] = gr.p0;
         v.nv[g] = gr.nv;
     }
-    hipLaunchKernelGGL(pf_set_segs_kernel, dim3(1), dim3(sizeof(PfSegs) / 4), 0, s, (PfSegs*)table, v);
-    SLI_HIP(hipGetLastError());
-    return SLI_OK;
+    return pf_put_segs(table, v, s);
 }
 
 static bool pf_chunk_size(int M) {
@@ -60,7 +66,7 @@ static bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 template <class Epi, typename WT>
 static int pf_gemm_launch(const void* w, const void* ws, const void* hi, const void* lo, int N, int K, int M, int role, const Epi& e,
-                          const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
+                          sli_pgemm_tiling* tiling, hipStream_t s) {
     SLI_HIP((pg_allow_lds_all<Epi, WT>()));
     return pg_pick<WT>(M, role, [&](auto cfg) -> int {
         using Cfg = decltype(cfg);
@@ -68,54 +74,68 @@ static int pf_gemm_launch(const void* w, const void* ws, const void* hi, const v
             *tiling = sli_pgemm_tiling{Cfg::BM, Cfg::WR, Cfg::S, Cfg::AT, Cfg::PIPE ? 1 : 0, Cfg::SA, PgGeo<Cfg, WT>::KS};
         // ws: the e8m0 block scales (mxfp4), else null
         const PgIn<WT> in{(const WT*)w, (const __half*)hi, (const __half*)lo, N, K, M, (const uint8_t*)ws};
-        SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, ps, s)));
+        SLI_HIP((launch_pgemm<Epi, Cfg, WT>(in, e, s)));
         return SLI_OK;
     });
 }
 
-// rs: int8 row scales for the epilogue (nullable); mxfp4: ws, the block scales for the GEMM, and no row scale
+// rs: int8 row scales for the epilogue (nullable); mxfp4: ws, the block scales for the GEMM, and no row scale. segs:
+// the chunk's table on the device (read by role 0 alone)
 template <typename WT>
 static int pf_gemm_role(const void* w, const float* rs_in, const void* hi, const void* lo, int N, int K, int M,
-                        const sli_pgemm_epilogue& e, const PfState* ps, sli_pgemm_tiling* tiling, hipStream_t s) {
+                        const sli_pgemm_epilogue& e, const PfSegs* segs, sli_pgemm_tiling* tiling, hipStream_t s) {
     const void* ws = is_mx<WT>::value ? (const void*)rs_in : nullptr;
     const float* rs = is_mx<WT>::value ? nullptr : rs_in;
     if (e.role == 0) {
         if (e.kv_dtype == SLI_DT_F8E4M3) {
-            const PgEpiQKV<f8e4m3> q{e.q, (f8e4m3*)e.kc, (f8e4m3*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
-            return pf_gemm_launch<PgEpiQKV<f8e4m3>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
+            const PgEpiQKV<f8e4m3> q{e.q, (f8e4m3*)e.kc, (f8e4m3*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T, segs};
+            return pf_gemm_launch<PgEpiQKV<f8e4m3>, WT>(w, ws, hi, lo, N, K, M, 0, q, tiling, s);
         }
         if (e.kv_dtype == SLI_DT_F16) {
-            const PgEpiQKV<__half> q{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
-            return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
+            const PgEpiQKV<__half> q{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T, segs};
+            return pf_gemm_launch<PgEpiQKV<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, tiling, s);
         }
-        const PgEpiQKV<float> q{e.q, (float*)e.kc, (float*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T};
-        return pf_gemm_launch<PgEpiQKV<float>, WT>(w, ws, hi, lo, N, K, M, 0, q, ps, tiling, s);
+        const PgEpiQKV<float> q{e.q, (float*)e.kc, (float*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T, segs};
+        return pf_gemm_launch<PgEpiQKV<float>, WT>(w, ws, hi, lo, N, K, M, 0, q, tiling, s);
     }
     if (e.role == 1) {
         const PgEpiSwiGLU g{(__half*)e.ahi, (__half*)e.alo, rs, e.inter, e.act_mode};
-        return pf_gemm_launch<PgEpiSwiGLU, WT>(w, ws, hi, lo, N, K, M, 1, g, ps, tiling, s);
+        return pf_gemm_launch<PgEpiSwiGLU, WT>(w, ws, hi, lo, N, K, M, 1, g, tiling, s);
     }
     if (e.role == 3) {  // N weight rows, any N >= 16: the launch covers whole 16-row tiles, the epilogue masks at N
         const PgEpiLogits g{e.y, rs, N, e.ld};
-        return pf_gemm_launch<PgEpiLogits, WT>(w, ws, hi, lo, pg_logits_n(N), K, M, 3, g, ps, tiling, s);
+        return pf_gemm_launch<PgEpiLogits, WT>(w, ws, hi, lo, pg_logits_n(N), K, M, 3, g, tiling, s);
     }
     const PgEpiResid r{e.y, e.resid, rs, N, e.ld};
-    return pf_gemm_launch<PgEpiResid, WT>(w, ws, hi, lo, N, K, M, 2, r, ps, tiling, s);
+    return pf_gemm_launch<PgEpiResid, WT>(w, ws, hi, lo, N, K, M, 2, r, tiling, s);
 }
 
-// the q/k/v GEMM under a group table (sli_prefill_gemm_qkv_segs): rs_in as pf_gemm_role
-template <typename WT>
-static int pf_gemm_qkv_segs_launch(const void* w, const float* rs_in, const void* hi, const void* lo, int N, int K, int M,
-                                   const sli_pgemm_epilogue& e, const PfSegs* segs, sli_pgemm_tiling* tiling,
-                                   hipStream_t s) {
-    const void* ws = is_mx<WT>::value ? (const void*)rs_in : nullptr;
-    const float* rs = is_mx<WT>::value ? nullptr : rs_in;
-    if (e.kv_dtype == SLI_DT_F8E4M3) {
-        const PgEpiQKVSegs<f8e4m3> q{{e.q, (f8e4m3*)e.kc, (f8e4m3*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T}, segs};
-        return pf_gemm_launch<PgEpiQKVSegs<f8e4m3>, WT>(w, ws, hi, lo, N, K, M, 0, q, nullptr, tiling, s);
+// one pgemm_kernel launch under the table the entry has just put on the stream; ws: mxfp4 block scales or int8 row scales
+static int pf_gemm_run(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int N, int K, int M,
+                       const sli_pgemm_epilogue& e, const void* table, sli_pgemm_tiling* tiling, hipStream_t s) {
+    const PfSegs* segs = (const PfSegs*)table;
+    const float* rs = (const float*)ws;
+    if (w_dtype == SLI_DT_MXFP4) return pf_gemm_role<mxfp4>(w, rs, hi, lo, N, K, M, e, segs, tiling, s);
+    if (w_dtype == SLI_DT_I8) return pf_gemm_role<int8_t>(w, rs, hi, lo, N, K, M, e, segs, tiling, s);
+    return pf_gemm_role<__half>(w, rs, hi, lo, N, K, M, e, segs, tiling, s);
+}
+
+// one attention launch under the table the entry has just put on the stream (an fp32 cache: the one-sequence kernel)
+static int pf_attn_run(const float* q, const void* kc, const void* vc, int kv_dtype, void* ohi, void* olo, int M, int hq,
+                       int hkv, int hd, int T, const void* table, hipStream_t s) {
+    const PfSegs* segs = (const PfSegs*)table;
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (kv_dtype == SLI_DT_F16) {
+        const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<__half>(aa, hd, M, segs, s));
+    } else if (kv_dtype == SLI_DT_F8E4M3) {  // every DMA piece is 16 bytes of a row: the entries' al16 check
+        const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, segs, s));
+    } else {
+        const PfAttnArgs<float> aa{q, (const float*)kc, (const float*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
+        SLI_HIP(launch_pf_attn<float>(aa, hd, M, segs, s));
     }
-    const PgEpiQKVSegs<__half> q{{e.q, (__half*)e.kc, (__half*)e.vc, rs, e.sin_t, e.cos_t, e.hq, e.hkv, e.hd, e.T}, segs};
-    return pf_gemm_launch<PgEpiQKVSegs<__half>, WT>(w, ws, hi, lo, N, K, M, 0, q, nullptr, tiling, s);
+    return SLI_OK;
 }
 
 }  // namespace sli
@@ -137,7 +157,7 @@ int sli_prefill_norm_split(const float* x, const float* w, void* hi, void* lo, i
     return SLI_OK;
 }
 
-// the checks every GEMM entry shares (the PfState and the group-table forms); ws: mxfp4 block scales (w_dtype
+// the checks every GEMM entry shares (the plain and the group-table forms); ws: mxfp4 block scales (w_dtype
 // SLI_DT_MXFP4) or int8 row scales
 static int pf_gemm_check(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
                          int32_t M, const sli_pgemm_epilogue* epi) {
@@ -185,7 +205,7 @@ static int pf_gemm_check(const void* w, int w_dtype, const void* ws, const void*
     return SLI_OK;
 }
 
-// the checks of both PfState GEMM entries and the launch
+// the checks of both plain GEMM entries, their table and the launch
 static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void* hi, const void* lo, int32_t N, int32_t K,
                          int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
                          sli_pgemm_tiling* tiling, sli_stream_t stream) {
@@ -193,14 +213,9 @@ static int pf_gemm_entry(const void* w, int w_dtype, const void* ws, const void*
     SLI_CHECK(p0 >= 0 && p0 <= (1 << 30) && nv >= 1 && nv <= M, SLI_ERR_ARG,
               "sli_prefill_gemm: p0 must be >= 0 and nv in [1, M]");
     SLI_CHECK((uintptr_t)state % 8 == 0, SLI_ERR_ARG, "sli_prefill_gemm: 16-byte alignment");
-    const sli_pgemm_epilogue& e = *epi;
     hipStream_t s = as_stream(stream);
-    if (int rc = pf_set_state(state, p0, nv, s)) return rc;
-    const PfState* ps = (const PfState*)state;
-    const float* rs = (const float*)ws;
-    if (w_dtype == SLI_DT_MXFP4) return pf_gemm_role<mxfp4>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
-    if (w_dtype == SLI_DT_I8) return pf_gemm_role<int8_t>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
-    return pf_gemm_role<__half>(w, rs, hi, lo, N, K, M, e, ps, tiling, s);
+    if (int rc = pf_set_run(state, p0, nv, M, s)) return rc;
+    return pf_gemm_run(w, w_dtype, ws, hi, lo, N, K, M, *epi, state, tiling, s);
 }
 
 int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo, int32_t N,
@@ -235,20 +250,8 @@ int sli_prefill_attn(const float* q, const void* kc, const void* vc, int kv_dtyp
     SLI_CHECK(al16(q) && al16(kc) && al16(vc) && al16(ohi) && al16(olo) && (uintptr_t)state % 8 == 0, SLI_ERR_ARG,
               "sli_prefill_attn: 16-byte alignment");
     hipStream_t s = as_stream(stream);
-    if (int rc = pf_set_state(state, p0, M, s)) return rc;
-    const PfState* ps = (const PfState*)state;
-    const float scale = 1.0f / sqrtf((float)hd);
-    if (kv_dtype == SLI_DT_F16) {
-        const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
-        SLI_HIP(launch_pf_attn<__half>(aa, hd, M, ps, s));
-    } else if (kv_dtype == SLI_DT_F8E4M3) {  // every DMA piece is 16 bytes of a row: the al16 check above
-        const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
-        SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, ps, s));
-    } else {
-        const PfAttnArgs<float> aa{q, (const float*)kc, (const float*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
-        SLI_HIP(launch_pf_attn<float>(aa, hd, M, ps, s));
-    }
-    return SLI_OK;
+    if (int rc = pf_set_run(state, p0, M, M, s)) return rc;
+    return pf_attn_run(q, kc, vc, kv_dtype, ohi, olo, M, hq, hkv, hd, T, state, s);
 }
 
 // ---- the group-table forms (sli_model_prefill_seqs)
@@ -261,11 +264,7 @@ static int pf_gemm_qkv_segs_entry(const void* w, int w_dtype, const void* ws, co
     SLI_CHECK(epi->kv_dtype != SLI_DT_F32, SLI_ERR_ARG, "sli_prefill_gemm_qkv_segs: an fp16 or FP8 cache (fp32 has no table form)");
     hipStream_t s = as_stream(stream);
     if (int rc = pf_set_segs(table, groups, M, B, epi->T, s)) return rc;
-    const PfSegs* segs = (const PfSegs*)table;
-    const float* rs = (const float*)ws;
-    if (w_dtype == SLI_DT_MXFP4) return pf_gemm_qkv_segs_launch<mxfp4>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
-    if (w_dtype == SLI_DT_I8) return pf_gemm_qkv_segs_launch<int8_t>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
-    return pf_gemm_qkv_segs_launch<__half>(w, rs, hi, lo, N, K, M, *epi, segs, tiling, s);
+    return pf_gemm_run(w, w_dtype, ws, hi, lo, N, K, M, *epi, table, tiling, s);
 }
 
 int sli_prefill_gemm_qkv_segs(const void* w, int w_dtype, const float* w_row_scale, const void* hi, const void* lo,
@@ -300,16 +299,7 @@ int sli_prefill_attn_segs(const float* q, const void* kc, const void* vc, int kv
               "sli_prefill_attn_segs: 16-byte alignment");
     hipStream_t s = as_stream(stream);
     if (int rc = pf_set_segs(table, groups, M, B, T, s)) return rc;
-    const PfSegs* segs = (const PfSegs*)table;
-    const float scale = 1.0f / sqrtf((float)hd);
-    if (kv_dtype == SLI_DT_F16) {
-        const PfAttnArgs<__half> aa{q, (const __half*)kc, (const __half*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
-        SLI_HIP(launch_pf_attn<__half>(aa, hd, M, segs, s));
-    } else {
-        const PfAttnArgs<f8e4m3> aa{q, (const f8e4m3*)kc, (const f8e4m3*)vc, (__half*)ohi, (__half*)olo, hq, hkv, T, scale};
-        SLI_HIP(launch_pf_attn<f8e4m3>(aa, hd, M, segs, s));
-    }
-    return SLI_OK;
+    return pf_attn_run(q, kc, vc, kv_dtype, ohi, olo, M, hq, hkv, hd, T, table, s);
 }
 
 // ---- scoring (score.h): the plain row map; sli_model_score_seqs launches the group-table one

@@ -13,7 +13,7 @@
 // atomics, no workspace. The target logit and the top logit are one extra load each by thread 0.
 // The launch is bound by one read of the chunk, M V 4 bytes (131 MB at 256 rows of a 128 256 vocabulary).
 //
-// One body, two row maps (in the manner of prefill.h PfState / PfSegs):
+// One body, two row maps:
 //   ScPlain  row m has target targets[m] and writes slot m;
 //   ScSegs   row m = 16 g + r is position p0[g] + r of sequence seq[g] (the group table of sli_model_prefill_seqs): its
 //            target is the NEXT prompt token, prompt[seq pld + p0 + r + 1], its slot (seq, p0 + r + 1) of

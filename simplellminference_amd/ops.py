@@ -265,8 +265,9 @@ def embedding(token, table, out=None, row_scale=None):
 PF_ROLE_QKV, PF_ROLE_GATE_UP, PF_ROLE_RESID, PF_ROLE_LOGITS = 0, 1, 2, 3
 
 
-def _pf_state(device):
-    return torch.empty(2, device=device, dtype=torch.int32)
+def _pf_table(device):
+    """SLI_PF_TABLE_BYTES of device memory: the group table every prefill entry fills on the stream."""
+    return torch.empty(48, device=device, dtype=torch.int32)
 
 
 def prefill_norm_split(x, w, eps: float):
@@ -287,7 +288,7 @@ def _prefill_gemm_mxfp4(w, scales, hi, lo, p0, nv, epi):
         raise ValueError("Tensor with Wrong Dim!")
     if hi.shape != (M, K) or lo.shape != (M, K) or hi.dtype != torch.float16 or lo.dtype != torch.float16:
         raise ValueError("Tensor with Wrong Dim!")
-    state = _pf_state(w.device)
+    state = _pf_table(w.device)
     _dev(w, scales, hi, lo)
     tl = _lib.PgemmTiling()
     call("sli_prefill_gemm_mxfp4", _p(w), _p(scales), _p(hi), _p(lo), N, K, M, p0, nv, ctypes.byref(epi), _p(state),
@@ -306,7 +307,7 @@ def _prefill_gemm(w, row_scale, hi, lo, p0, nv, epi, scales=None):
         raise ValueError("Tensor with Wrong Dim!")
     if w.dtype not in (torch.float16, torch.int8):
         raise ValueError("prefill GEMM takes fp16 or int8 weights")
-    state = _pf_state(w.device)
+    state = _pf_table(w.device)
     _dev(w, row_scale, hi, lo)
     tl = _lib.PgemmTiling()
     call("sli_prefill_gemm", _p(w), _DT[w.dtype], _p(row_scale), _p(hi), _p(lo), N, K, M, p0, nv, ctypes.byref(epi),
@@ -399,7 +400,7 @@ def prefill_attn(q, kc, vc, M: int, p0: int, hq: int, hkv: int, hd: int, kv_dtyp
     T = kc.shape[1]
     ohi = torch.zeros(rows, hq * hd, device=q.device, dtype=torch.float16)
     olo = torch.zeros_like(ohi)
-    state = _pf_state(q.device)
+    state = _pf_table(q.device)
     _dev(q, kc, vc)
     call("sli_prefill_attn", _p(q), _p(kc), _p(vc), _kv_dt(kc, kv_dtype), _p(ohi), _p(olo), M, rows, p0, hq, hkv, hd, T,
          _p(state), _s())
@@ -440,10 +441,6 @@ def _pf_groups(groups, M):
     for i, (s, p0, nv) in enumerate(gs):
         arr[i] = _lib.PfGroup(s, p0, nv)
     return arr
-
-
-def _pf_table(device):
-    return torch.empty(48, device=device, dtype=torch.int32)
 
 
 def prefill_gemm_qkv_segs(w, hi, lo, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, groups, row_scale=None,

@@ -220,7 +220,7 @@ def test_prefill_attn_f8_argument_checks(gpu):
     c8 = torch.zeros(hkv * T * hd + 64, dtype=torch.uint8, device="cuda")
     ohi = torch.zeros(M * hq * hd, dtype=torch.float16, device="cuda")
     olo = torch.zeros_like(ohi)
-    st = torch.zeros(2, dtype=torch.int32, device="cuda")
+    st = torch.zeros(48, dtype=torch.int32, device="cuda")  # SLI_PF_TABLE_BYTES
     p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)
     F8, ARG = _lib.DT_F8E4M3, 1
 

@@ -355,7 +355,7 @@ def test_entry_point_rejects_what_the_kernel_cannot_take(gpu):
     with pytest.raises(ValueError):  # a row scale beside block scales
         ops.prefill_gemm_resid(u8(64, 32), f16(32, 64), f16(32, 64), f32(32, 64), scales=u8(64, 2), row_scale=f32(64))
     # sli_prefill_gemm itself keeps refusing the dtype
-    y, state = f32(32, 64), torch.zeros(2, dtype=torch.int32, device="cuda")
+    y, state = f32(32, 64), torch.zeros(48, dtype=torch.int32, device="cuda")  # SLI_PF_TABLE_BYTES
     e = _lib.PgemmEpilogue(role=2, y=y.data_ptr(), resid=None, ld=64)
     with pytest.raises(SliError, match="MXFP4 have no GEMM prefill") as ei:
         _lib.call("sli_prefill_gemm", ops._p(u8(64, 32)), _lib.DT_MXFP4, None, ops._p(f16(32, 64)), ops._p(f16(32, 64)),

@@ -71,6 +71,24 @@ def test_prefill_long_prompts(gpu, oracle, n):
     _check(gtok, glog, otok, olog, n)
 
 
+def test_prefill_f32_cache_two_chunks(gpu, oracle):
+    """An fp32 cache past one chunk: 299 prefilled positions are a 256-row chunk and a 64-row chunk with 43 valid rows,
+    so the VALU attention (pf_attn_kernel, 64-row blocks) runs one block whose start position is 256, read from the
+    group table, and whose fourth group is padding.
+    The weight seed, chosen with the oracle alone on the CPU (no GPU result was consulted): of seeds 0 .. 23 the one
+    whose smallest top-2 logit gap over the computed positions 299 .. 311 of this prompt is largest, seed 6 with a
+    gap of 0.0594 (the next, seed 20: 0.0534), against the 1e-3 the logits are held to."""
+    n = 300
+    cfg, om, gm = _pair(oracle, "tiny-gqa", w="f16", kv="f32", seed=6, max_length=320)
+    assert gm.prefill_path() == "mfma"
+    prompt = _prompt(n, cfg.vocab_size)
+    otok, olog = om.predict(prompt, n + 12)
+    gtok, glog = gm.predict_prefill(prompt, n + 12, want_logits=True)
+    gm.close()
+    om.close()
+    _check(gtok, glog, otok, olog, n)
+
+
 @pytest.mark.parametrize("n", [21, 150])
 def test_prefill_kv_rows_match_oracle(gpu, oracle, n):
     cfg, om, gm = _pair(oracle, "tiny-gqa", max_length=160)

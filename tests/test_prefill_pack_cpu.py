@@ -81,6 +81,18 @@ def test_edge_cases():
     assert rows.tolist() == [64] and g.tolist() == [[0, 0, 1], [1, 0, 16], [1, 16, 16], [1, 32, 1]]
 
 
+def test_one_sequence_plan_is_the_batch_1_chunk_rule():
+    """sli_model_prefill and sli_tp_group_prefill run the plan of the one sequence 0. It is the chunking they always had:
+    chunks of up to 256 consecutive positions from 0, each the smallest size that holds its rows, the real groups the
+    16-row runs of positions 0 .. n - 2 in order."""
+    for n in range(1, 1101):
+        g, rows = _pack([n], [0])
+        old = [min(m for m in SIZES if m >= min(256, n - 1 - p0)) for p0 in range(0, n - 1, 256)]
+        assert rows.tolist() == old, n
+        real = [tuple(r) for r in g.tolist() if r[2] > 0]
+        assert real == [(0, 16 * k, min(16, n - 1 - 16 * k)) for k in range(-(-(n - 1) // 16))], n
+
+
 def test_refusals():
     from simplellminference_amd import _lib
     from simplellminference_amd._lib import SliError

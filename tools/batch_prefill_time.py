@@ -6,7 +6,8 @@ Reported per prompt length: every round, the median, the per-round spread (max -
 The speed-up is a record, not a promise.
 
 The bar: the group table must cost the batch-1 prefill nothing. A child process per build times the batch-1 512-token
-prefill (LlamaModel.prefill) of this build's library and of another build's (--baseline-variant NAME: libsli_NAME.so,
+prefill (LlamaModel.prefill, with --weights / --kv; MXFP4 under set_prefill("gemm"), an FP8 cache under "gemm-kv8") of
+this build's library and of another build's (--baseline-variant NAME: libsli_NAME.so,
 the parent commit's built with `python -m simplellminference_amd.build --variant NAME`, as tools/ab_variants.sh loads
 them), in the order baseline, this, this, baseline; the gap of the medians has to stay inside the spread (max - min) of
 the baseline's own rounds ("inside_baseline_spread").
@@ -82,7 +83,12 @@ def b1_child(a):
     from simplellminference_amd.model import LlamaModel, preset
     cfg = preset("llama3-8b", num_hidden_layers=a.layers, max_length=a.ctx)
     ids = _ids(a.b1_tokens, 0, cfg.vocab_size)
-    m = LlamaModel(config=cfg, w_dtype=a.weights, kv_dtype="f16", seed=1).init()
+    m = LlamaModel(config=cfg, w_dtype=a.weights, kv_dtype=a.kv, seed=1).init()
+    # where auto keeps the decode step (MXFP4 weights, an FP8 cache), the GEMM prefill is asked for
+    if a.kv == "f8":
+        m.set_prefill("gemm-kv8")
+    elif a.weights == "mxfp4":
+        m.set_prefill("gemm")
     assert m.prefill_path() == "mfma"
     ms = []
     for r in range(-1, a.rounds):
@@ -99,7 +105,7 @@ def _child(a, variant):
     if variant:
         env["SLI_LIB_VARIANT"] = variant
     cmd = [sys.executable, os.path.abspath(__file__), "--b1-child", "--rounds", str(a.b1_rounds), "--layers",
-           str(a.layers), "--ctx", str(a.ctx), "--weights", a.weights, "--b1-tokens", str(a.b1_tokens)]
+           str(a.layers), "--ctx", str(a.ctx), "--weights", a.weights, "--kv", a.kv, "--b1-tokens", str(a.b1_tokens)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         raise RuntimeError(f"child failed ({r.returncode}):\n{r.stdout}\n{r.stderr}")

@@ -139,7 +139,7 @@ def prefill_launches(cfg, w, iters):
     q = rnd(M, hq * hd)
     ohi = torch.zeros(M, hq * hd, device="cuda", dtype=torch.float16)
     olo = torch.zeros_like(ohi)
-    st = torch.zeros(2, device="cuda", dtype=torch.int32)
+    st = torch.zeros(48, device="cuda", dtype=torch.int32)  # SLI_PF_TABLE_BYTES
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     wdt = _lib.DT_I8 if w == "i8" else _lib.DT_F16
     out = {}

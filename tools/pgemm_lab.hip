@@ -39,7 +39,6 @@ struct Bufs {
     std::vector<uint8_t*> Sc;  // mxfp4: the block scales of each copy
     __half *hi, *lo;
     float* y;
-    PfState* ps;
     std::vector<WT> hW;  // mxfp4: data [N][K/2], two codes per byte
     std::vector<uint8_t> hS;  // mxfp4: scale bytes 120 .. 126
     std::vector<__half> hhi, hlo;
@@ -106,11 +105,8 @@ static void make(Bufs<WT>& b, int N, int K, int M) {
     CK(hipMalloc(&b.hi, 2 * b.hhi.size()));
     CK(hipMalloc(&b.lo, 2 * b.hlo.size()));
     CK(hipMalloc(&b.y, sizeof(float) * (size_t)M * N));
-    CK(hipMalloc(&b.ps, sizeof(PfState)));
     CK(hipMemcpy(b.hi, b.hhi.data(), 2 * b.hhi.size(), hipMemcpyHostToDevice));
     CK(hipMemcpy(b.lo, b.hlo.data(), 2 * b.hlo.size(), hipMemcpyHostToDevice));
-    PfState p{0, M};
-    CK(hipMemcpy(b.ps, &p, sizeof p, hipMemcpyHostToDevice));
 }
 
 template <typename WT>
@@ -120,7 +116,6 @@ static void release(Bufs<WT>& b) {
     CK(hipFree(b.hi));
     CK(hipFree(b.lo));
     CK(hipFree(b.y));
-    CK(hipFree(b.ps));
 }
 
 template <class Cfg, typename WT>
@@ -131,7 +126,7 @@ static void run(const char* tag, Bufs<WT>& b, const Shape& sh, int M) {
     PgIn<WT> in{b.Wc[0], b.hi, b.lo, sh.N, sh.K, M, b.Sc[0]};
     PgEpiResid e{b.y, nullptr, nullptr, sh.N, sh.N};
     CK(hipMemset(b.y, 0, sizeof(float) * (size_t)M * sh.N));
-    CK((launch_pgemm<PgEpiResid, Cfg, WT>(in, e, b.ps, 0)));
+    CK((launch_pgemm<PgEpiResid, Cfg, WT>(in, e, 0)));
     CK(hipDeviceSynchronize());
     // spot check (y[m][row] = sum_k W[row][k] (hi + lo)[m][k])
     std::vector<float> y((size_t)M * sh.N);
@@ -158,7 +153,7 @@ static void run(const char* tag, Bufs<WT>& b, const Shape& sh, int M) {
         PgIn<WT> ic = in;
         ic.W = b.Wc[i % b.Wc.size()];
         ic.Ws = b.Sc[i % b.Sc.size()];
-        CK((launch_pgemm<PgEpiResid, Cfg, WT>(ic, e, b.ps, 0)));
+        CK((launch_pgemm<PgEpiResid, Cfg, WT>(ic, e, 0)));
     }
     CK(hipEventRecord(e1, 0));
     CK(hipEventSynchronize(e1));
