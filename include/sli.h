@@ -749,6 +749,98 @@ int sli_batch_gemm_mxfp4(const float* x, const float* norm_w, float eps, const v
                          int32_t tiled, int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan,
                          void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
+/* ---------------------------------------------------------------- decode stages, for tests and labs
+ * One GEMV launch of the batch-1 decode step (csrc/gemv.h), without a model or a workspace (the GEMVs keep no
+ * counters): device pointers and a stream. The entry is compiled into the engine's translation unit over the engine's
+ * own template arguments, so it launches the very code objects a model step launches; role, input staging and RMSNorm
+ * are paired as the engine pairs them, and nothing else can be asked for.
+ *
+ * The launch: the input vector h [cols] is staged once per workgroup as fp32, then sum[r] = sum_k W[r][k] h[k] with
+ * fp32 accumulation, times the row scale (w_row_scale[r], NULL: none; MXFP4 has block scales instead), then the
+ * epilogue. With a norm, h[k] = fl(fl(x[k] * inv) * norm_w[k]), inv = 1 / sqrtf(sum(x^2) / cols + eps).
+ * SLI_GV_QKV      norm required. Rows [q heads; k heads; v heads] of hd (64 or 128) each, hq % hkv == 0. Rotate-half
+ *                 RoPE of the q and k rows at *pos with sin_t / cos_t [T][hd / 2]; q [hq hd] fp32; the k and v rows go
+ *                 to row *pos of kc / vc, one layer's cache [hkv][T][hd] in kv_dtype (SLI_DT_F32 / F16 / F8E4M3; not
+ *                 F8E4M3 with fp32 weights). pos is int32 ON THE DEVICE; 0 <= *pos < T is the caller's contract.
+ * SLI_GV_GATE_UP  norm required. Rows [gate (inter); up (inter)]: act [inter] fp32 = sigmoid(g) * u (act_mode 0) or
+ *                 SiLU(g) * u (1). np = 2 or 4: the staged input is x + parts[0] + ... + parts[np - 1] (parts [np][cols],
+ *                 added in that order, then normalised; cols <= 4096), the K-split wo's consumer.
+ * SLI_GV_WO       no norm. y[r] = (resid ? resid[r] : 0) + sum for r < nrows; y may be resid (the residual stream is
+ *                 updated in place) or not (a tensor-parallel rank). part == NULL: the input is x. part != NULL: the
+ *                 input is merged from the attention's split partials part [hq][max_splits][hd + 4] (o[hd], m, l, pad)
+ *                 while it is staged: over the ns = min(*pos / ppwg + 1, max_splits) live splits, in split order,
+ *                 h = (sum_s e^(m_s - M) o_s) / (sum_s e^(m_s - M) l_s), M = max m_s; cols == hq * hd; max_splits > 8
+ *                 takes the 16-split instantiation. ks = 2 or 4 (with part): the K-split wo, kpart[k][r] = the sum over
+ *                 column block k of row r (times the row scale), no residual; hq % ks == 0.
+ * SLI_GV_DOWN     no norm, input x. y[r] = (resid ? resid[r] : 0) + sum; np = 2 or 4: the residual is resid[r] +
+ *                 parts[0][r] + ... + parts[np - 1][r] (parts [np][nrows]), in that order.
+ * SLI_GV_LOGITS   norm required. logits[r] = sum for r < nrows; keys [key_ld] uint64 receives, per workgroup g <
+ *                 plan.grid, the largest key of the rows it owned: (orderable image of the fp32 logit) << 32 |
+ *                 (0xFFFFFFFF - (vocab_off + r)), 0 from a workgroup without rows. key_ld >= grid.
+ * Nothing else is written. The fields of the other roles are ignored. */
+enum { SLI_GV_QKV = 0, SLI_GV_GATE_UP = 1, SLI_GV_WO = 2, SLI_GV_DOWN = 3, SLI_GV_LOGITS = 4 };
+typedef struct {
+    int32_t role;
+    /* SLI_GV_GATE_UP and SLI_GV_DOWN: the K-split wo's partial sums */
+    const float* parts;
+    int32_t np;
+    /* SLI_GV_WO: the merged input and the K-split */
+    const float* part;
+    int32_t max_splits, ppwg, ks;
+    float* kpart;
+    /* SLI_GV_QKV (pos, hq, hd: SLI_GV_WO's merged input too) */
+    const int32_t* pos;
+    float* q;
+    void* kc;
+    void* vc;
+    int32_t kv_dtype;
+    const float* sin_t;
+    const float* cos_t;
+    int32_t hq, hkv, hd, T;
+    /* SLI_GV_GATE_UP */
+    float* act;
+    int32_t inter, act_mode;
+    /* SLI_GV_WO and SLI_GV_DOWN */
+    float* y;
+    const float* resid;
+    /* SLI_GV_WO, SLI_GV_DOWN and SLI_GV_LOGITS */
+    int32_t nrows;
+    /* SLI_GV_LOGITS */
+    float* logits;
+    uint64_t* keys;
+    int32_t vocab_off, key_ld;
+} sli_gemv_epilogue;
+
+/* The schedule of a launch, in / out. In: cus. 0: the device's compute units (what a model runs); otherwise the plan
+ * is made by the engine's own planners as if the chip had `cus` compute units, 1 <= cus <= the device's, so a matrix
+ * of a few hundred rows runs the schedule of a production one. Out, what ran: grid workgroups of 16 waves share
+ * `units` units (R rows each) in balanced consecutive runs; a unit's row is cut into chunks_per_row chunks of u
+ * 16-byte vectors per lane, masked_tail != 0 when the last chunk is partly past the row end; csplit column parts of
+ * chunks_per_part chunks per unit (1: the whole row per wave); cw of the 16 waves stream; nb register buffers; ns the
+ * split partials a thread holds in registers (merged input; 0 otherwise); lds_bytes the dynamic LDS. */
+typedef struct {
+    int32_t cus;
+    int32_t grid, units, csplit, u, chunks_per_row, chunks_per_part, cw, nb, ns, masked_tail, lds_bytes;
+} sli_gemv_plan;
+
+/* *plan resolved as sli_decode_gemv (w_dtype SLI_DT_MXFP4: sli_decode_gemv_mxfp4) would resolve it, nothing launched;
+ * only the shape fields of *epi are read, norm != 0 stands for norm_w. It needs no device when plan->cus != 0. */
+int sli_decode_gemv_plan(int w_dtype, int32_t cols, int32_t norm, const sli_gemv_epilogue* epi, sli_gemv_plan* plan);
+
+/* One launch. W [rows][cols] row-major in w_dtype (SLI_DT_F32 / F16 / I8), rows = (hq + 2 hkv) hd, 2 inter or nrows.
+ * Refused as SLI_ERR_ARG, each with its own message, before the device is touched: a device pointer that is not
+ * 16-byte aligned; cols not a multiple of the weight type's vector width (4, 8, 16; MXFP4 32) or above 16320; a role
+ * and norm / staging pairing the engine does not make; hd other than 64 or 128, hq % hkv != 0; merged input with cols
+ * != hq * hd; K-split with hq % ks != 0 or no grid that keeps every workgroup inside one column block; np > 0 at the
+ * gate/up launch with cols > 4096; cus above the device's; more than 64 KiB of LDS; key_ld < grid. */
+int sli_decode_gemv(const float* x, const float* norm_w, float eps, const void* w, int w_dtype, const float* w_row_scale,
+                    int32_t cols, const sli_gemv_epilogue* epi, sli_gemv_plan* plan, sli_stream_t stream);
+
+/* sli_decode_gemv from MXFP4 weights: `data` uint8 [rows][cols / 2] and `scales` uint8 [rows][cols / 32] in the public
+ * layout (sli_quant_mxfp4); no row scale. The contract is sli_decode_gemv's. */
+int sli_decode_gemv_mxfp4(const float* x, const float* norm_w, float eps, const void* data, const void* scales,
+                          int32_t cols, const sli_gemv_epilogue* epi, sli_gemv_plan* plan, sli_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,22 @@ class BgemmPlan(ctypes.Structure):  # sli_bgemm_plan
     _fields_ = [(n, c_i32) for n in ("tpw", "splits", "groups", "step_width", "lds_bytes")] + [("counter_off", c_i64)]
 
 
+class GemvEpilogue(ctypes.Structure):  # sli_gemv_epilogue
+    _fields_ = [("role", c_i32),
+                ("parts", c_vp), ("np", c_i32),
+                ("part", c_vp), ("max_splits", c_i32), ("ppwg", c_i32), ("ks", c_i32), ("kpart", c_vp),
+                ("pos", c_vp), ("q", c_vp), ("kc", c_vp), ("vc", c_vp), ("kv_dtype", c_i32), ("sin_t", c_vp),
+                ("cos_t", c_vp), ("hq", c_i32), ("hkv", c_i32), ("hd", c_i32), ("T", c_i32),
+                ("act", c_vp), ("inter", c_i32), ("act_mode", c_i32),
+                ("y", c_vp), ("resid", c_vp), ("nrows", c_i32),
+                ("logits", c_vp), ("keys", c_vp), ("vocab_off", c_i32), ("key_ld", c_i32)]
+
+
+class GemvPlan(ctypes.Structure):  # sli_gemv_plan
+    _fields_ = [(n, c_i32) for n in ("cus", "grid", "units", "csplit", "u", "chunks_per_row", "chunks_per_part", "cw",
+                                     "nb", "ns", "masked_tail", "lds_bytes")]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "sli_version": (c_int, []),
@@ -198,6 +214,11 @@ _SIGS = {
     "sli_batch_gemm_mxfp4_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmPlan)]),
     "sli_batch_gemm_mxfp4": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
                                      ctypes.POINTER(BgemmPlan), c_vp, c_sz, c_vp]),
+    "sli_decode_gemv_plan": (c_int, [c_int, c_i32, c_i32, ctypes.POINTER(GemvEpilogue), ctypes.POINTER(GemvPlan)]),
+    "sli_decode_gemv": (c_int, [c_vp, c_vp, c_f, c_vp, c_int, c_vp, c_i32, ctypes.POINTER(GemvEpilogue),
+                                ctypes.POINTER(GemvPlan), c_vp]),
+    "sli_decode_gemv_mxfp4": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, ctypes.POINTER(GemvEpilogue),
+                                      ctypes.POINTER(GemvPlan), c_vp]),
     "sli_tp_group_destroy": (c_int, [c_vp]),
     "sli_tp_group_rank": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
     "sli_tp_group_step": (c_int, [c_vp]),

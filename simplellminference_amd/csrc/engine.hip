@@ -3115,3 +3115,6 @@ int sli_tp_group_predict_batch(sli_tp_group* g, const int32_t* prompts, const in
 // likewise one batched decode projection (sli.h "batched decode stages, for tests and labs"): this translation
 // unit's copies of bgemm_kernel and bg_tile_kernel, the ones StepRecorder launches
 #include "bgemm_ops.h"
+// likewise one batch-1 decode GEMV (sli.h "decode stages, for tests and labs"): this translation unit's copies of the
+// gemv.h kernels, the ones StepRecorder launches
+#include "gemv_ops.h"

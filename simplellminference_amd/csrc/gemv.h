@@ -971,8 +971,9 @@ inline int gemv_max_blocks() {
 
 // Grid: enough workgroups for every (unit, column part) item to have a wave, capped at the persistent
 // size; the balanced schedule in gemv_block spreads the items over whatever grid this returns.
-inline int gemv_blocks(int units, int csplit = 1) {
-    const int maxb = gemv_max_blocks();
+// (maxb, here and in the planners and launch sites below: the workgroup cap, a host argument. Its default is the
+// chip's; sli_decode_gemv (gemv_ops.h) passes a smaller one to run a small matrix on a large one's schedule.)
+inline int gemv_blocks(int units, int csplit = 1, int maxb = gemv_max_blocks()) {
     const int items = units * csplit;
     int b = (items + (kGemvThreads / 64) - 1) / (kGemvThreads / 64);
     b = b < units ? b : units;  // every workgroup owns at least one unit
@@ -987,8 +988,8 @@ inline int gemv_blocks(int units, int csplit = 1) {
 // CU's share of the HBM stream stays under its per-CU fetch rate (gate/up: 230 workgroups, 31.4 -> 29.0 us,
 // C1 358 -> 368 tok/s; qkv at 1.5 units per wave would need 192 workgroups: measured slower, 17.9 -> 20.5 us;
 // profiles/r3_gemv_balance_ab.txt).
-inline int gemv_balanced_blocks(int units) {
-    const int b = gemv_blocks(units);
+inline int gemv_balanced_blocks(int units, int maxb = gemv_max_blocks()) {
+    const int b = gemv_blocks(units, 1, maxb);
     const int w = kGemvThreads / 64;
     const int k = (units + b * w - 1) / (b * w);  // most units of a wave at the full grid
     const int g = (units + k * w - 1) / (k * w);
@@ -1003,6 +1004,7 @@ inline int gemv_balanced_blocks(int units) {
 // Measured (profiles/r3_gemv_balance_ab.txt): int8 qkv 12.8 -> 12.4 us with 12 waves of 2 units, C3 +0.8 %;
 // fp16 qkv 18.1 -> 21.2 us (12 waves keep 3/4 of the bytes in flight per CU, and fp16 needs them) — so
 // int8 weights only (the launch sites pass the weight type).
+// (the cap reaches it through grid)
 template <typename WT>
 inline int gemv_wave_count(int units, int grid) {
     if (!std::is_same<WT, int8_t>::value) return kGemvThreads / 64;
@@ -1033,16 +1035,36 @@ inline void epi_prepare(EpiKPart& e) {
     e.d_m = d.m, e.d_sh = d.sh;
 }
 
+// What a launch site resolved, for the callers that report it (gemv_ops.h). dry: resolve only, launch nothing.
+struct GemvRan {
+    bool dry = false;
+    int grid = 0, units = 0, csplit = 1, u = 0, cpr = 0, cpp = 0, cw = 0, nb = 0, ns = 0, masked = 0;
+    size_t lds = 0;
+};
+// fills *ran (if any); true: the caller returns without launching
+template <typename WT, int U>
+inline bool gemv_ran(GemvRan* ran, const GemvIn& in, int units, int grid, int nb, int ns, size_t lds) {
+    if (!ran) return false;
+    const int nvec = in.cols / Vec16<WT>::N, cv = U * 64;
+    ran->grid = grid, ran->units = units, ran->csplit = in.csplit, ran->u = U, ran->cw = in.cw, ran->nb = nb, ran->ns = ns;
+    ran->cpr = (nvec + cv - 1) / cv;
+    ran->cpp = (ran->cpr + in.csplit - 1) / in.csplit;
+    ran->masked = nvec % cv != 0;
+    ran->lds = lds;
+    return ran->dry;
+}
+
 // the merge-staged launch of a prepared grid (launch_gemv_merge, launch_gemv_merge_ks)
 template <typename WT, int R, int U, bool NT, class Epi, int NS, int NB>
 hipError_t launch_gemv_merge_grid(const WT* W, const GemvIn& in_, const Epi& epi_, const AttnMergeIn& am, int units,
-                                  int grid, hipStream_t s) {
+                                  int grid, hipStream_t s, GemvRan* ran = nullptr) {
     GemvIn in = in_;
     in.cw = gemv_wave_count<WT>(units, grid);
     Epi epi = epi_;
     epi_prepare(epi);
     const GemvPart pt = gemv_part<WT, U>(in.cols, 1, units, grid, in.cw);
     const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
+    if (gemv_ran<WT, U>(ran, in, units, grid, NB, NS, lds)) return hipSuccess;
     hipLaunchKernelGGL((gemv_merge_kernel<WT, R, U, NT, Epi, NS, NB>), dim3(grid), dim3(kGemvThreads), lds, s, W,
                        am.part, am.pos_dev, in.cols, in.cw, pt.nunits, pt.tw_m, pt.cw_m, pt.sh, am.max_splits, am.hd, in,
                        epi, am);
@@ -1051,34 +1073,35 @@ hipError_t launch_gemv_merge_grid(const WT* W, const GemvIn& in_, const Epi& epi
 
 template <typename WT, int R, int U, bool NT, class Epi, int NS = 8, int NB = SLI_WO_NB>
 hipError_t launch_gemv_merge(const WT* W, const GemvIn& in_, const Epi& epi, const AttnMergeIn& am, int units,
-                             hipStream_t s) {
+                             hipStream_t s, int maxb = gemv_max_blocks(), GemvRan* ran = nullptr) {
     if (in_.csplit != 1) return hipErrorInvalidValue;  // the merge-staged wo GEMV runs unsplit
-    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, gemv_balanced_blocks(units), s);
+    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, gemv_balanced_blocks(units, maxb), s,
+                                                             ran);
 }
 
 // K-split wo: the grid must keep every workgroup's units inside one block k (gemv_block's partition b * N / g):
 // g = ks * m with m dividing D, so each workgroup holds D / m units of one k. 0 if no such grid fits the chip.
-inline int gemv_ksplit_grid(int D, int ks) {
-    const int maxb = gemv_max_blocks();
+inline int gemv_ksplit_grid(int D, int ks, int maxb = gemv_max_blocks()) {
     for (int m = maxb / ks; m >= 1; --m)
         if (D % m == 0) return ks * m;
     return 0;
 }
 template <typename WT, int R, int U, bool NT, class Epi, int NS = 8, int NB = SLI_WO_NB>
 hipError_t launch_gemv_merge_ks(const WT* W, const GemvIn& in_, const Epi& epi, const AttnMergeIn& am, int grid,
-                                hipStream_t s) {
+                                hipStream_t s, GemvRan* ran = nullptr) {
     const int units = am.ksplit * am.kunits;
     if (in_.csplit != 1 || grid <= 0 || grid % am.ksplit || am.kunits % (grid / am.ksplit)) return hipErrorInvalidValue;
-    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, grid, s);
+    return launch_gemv_merge_grid<WT, R, U, NT, Epi, NS, NB>(W, in_, epi, am, units, grid, s, ran);
 }
 template <typename WT, int R, int U, bool NT, class Epi, int NP, int NB = 2>
 hipError_t launch_gemv_sum(const WT* W, const GemvIn& in_, const Epi& epi_, const float* parts, int units,
-                           hipStream_t s) {
+                           hipStream_t s, int maxb = gemv_max_blocks(), GemvRan* ran = nullptr) {
     if (in_.csplit != 1 || in_.cols > 4 * kGemvThreads) return hipErrorInvalidValue;  // XStageSum: one round
     GemvIn in = in_;
-    const int grid = gemv_balanced_blocks(units);
+    const int grid = gemv_balanced_blocks(units, maxb);
     in.cw = gemv_wave_count<WT>(units, grid);
     const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R);
+    if (gemv_ran<WT, U>(ran, in, units, grid, NB, 0, lds)) return hipSuccess;
     Epi epi = epi_;
     epi_prepare(epi);
     const GemvPart pt = gemv_part<WT, U>(in.cols, 1, units, grid, in.cw);
@@ -1088,12 +1111,14 @@ hipError_t launch_gemv_sum(const WT* W, const GemvIn& in_, const Epi& epi_, cons
 }
 
 template <typename WT, int R, int U, bool NT, class Epi, int NB = 2, bool SPLIT = false>
-hipError_t launch_gemv(const WT* W, const GemvIn& in_, const Epi& epi_, int units, hipStream_t s) {
+hipError_t launch_gemv(const WT* W, const GemvIn& in_, const Epi& epi_, int units, hipStream_t s,
+                       int maxb = gemv_max_blocks(), GemvRan* ran = nullptr) {
     if (!SPLIT && in_.csplit != 1) return hipErrorInvalidValue;  // a split needs the SPLIT instantiation
     GemvIn in = in_;
-    const int grid = in.csplit == 1 ? gemv_balanced_blocks(units) : gemv_blocks(units, in.csplit);
+    const int grid = in.csplit == 1 ? gemv_balanced_blocks(units, maxb) : gemv_blocks(units, in.csplit, maxb);
     in.cw = in.csplit == 1 ? gemv_wave_count<WT>(units, grid) : kGemvThreads / 64;
     const size_t lds = gemv_lds_bytes(in.cols) + sizeof(float) * gemv_res_floats(units, grid, R, in.csplit);
+    if (gemv_ran<WT, U>(ran, in, units, grid, NB, 0, lds)) return hipSuccess;
     Epi epi = epi_;
     epi_prepare(epi);
     const GemvPart pt = gemv_part<WT, U>(in.cols, in.csplit, units, grid, in.cw);
@@ -1123,9 +1148,9 @@ constexpr int gemv_uw() {
     return std::is_same<WT, int8_t>::value && U >= 2 ? U / 2 : U;
 }
 template <typename WT, int U>
-inline GemvSplit gemv_split(int units, int cols) {
+inline GemvSplit gemv_split(int units, int cols, int maxb = gemv_max_blocks()) {
     constexpr int UW = gemv_uw<WT, U>();
-    const int waves = gemv_max_blocks() * (kGemvThreads / 64);
+    const int waves = maxb * (kGemvThreads / 64);
     int need = 1;
     while (need < 8 && units * need < waves) need *= 2;
     const int nvec = cols / Vec16<WT>::N;
@@ -1136,17 +1161,18 @@ inline GemvSplit gemv_split(int units, int cols) {
     return {std::max(1, std::min(need, cpr(1))), 1};
 }
 template <typename WT, int R, int U, bool NT, class Epi>
-hipError_t launch_gemv_u(const WT* W, const GemvIn& in_, const Epi& epi, int units, hipStream_t s) {
+hipError_t launch_gemv_u(const WT* W, const GemvIn& in_, const Epi& epi, int units, hipStream_t s,
+                         int maxb = gemv_max_blocks(), GemvRan* ran = nullptr) {
     constexpr int UW = gemv_uw<WT, U>();
     GemvIn in = in_;
-    const GemvSplit sp = gemv_split<WT, U>(units, in.cols);
+    const GemvSplit sp = gemv_split<WT, U>(units, in.cols, maxb);
     in.csplit = sp.cs;
-    if (sp.cs == 1) return launch_gemv<WT, R, UW, NT>(W, in, epi, units, s);
-    if (sp.u == UW) return launch_gemv<WT, R, UW, NT, Epi, 2, true>(W, in, epi, units, s);
+    if (sp.cs == 1) return launch_gemv<WT, R, UW, NT>(W, in, epi, units, s, maxb, ran);
+    if (sp.u == UW) return launch_gemv<WT, R, UW, NT, Epi, 2, true>(W, in, epi, units, s, maxb, ran);
     if constexpr (UW > 2) {
-        if (sp.u == 2) return launch_gemv<WT, R, 2, NT, Epi, 2, true>(W, in, epi, units, s);
+        if (sp.u == 2) return launch_gemv<WT, R, 2, NT, Epi, 2, true>(W, in, epi, units, s, maxb, ran);
     }
-    return launch_gemv<WT, R, 1, NT, Epi, 2, true>(W, in, epi, units, s);
+    return launch_gemv<WT, R, 1, NT, Epi, 2, true>(W, in, epi, units, s, maxb, ran);
 }
 
 }  // namespace sli

@@ -626,6 +626,160 @@ def batch_gemm_logits(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int
     return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, w.shape[0], plan, ws, scales)
 
 
+GV_ROLE_QKV, GV_ROLE_GATE_UP, GV_ROLE_WO, GV_ROLE_DOWN, GV_ROLE_LOGITS = 0, 1, 2, 3, 4
+
+
+def _gv_plan_dict(p):
+    return {n: getattr(p, n) for n, _ in p._fields_}
+
+
+def decode_gemv_plan(role: int, w_dtype: int, cols: int, cus: int = 0, norm=None, **shape):
+    """The schedule sli_decode_gemv would run (sli_gemv_plan as a dict), nothing launched; no device is needed when
+    cus != 0. shape: the integer fields of sli_gemv_epilogue the role reads (hq, hkv, hd, T, kv_dtype, inter, act_mode,
+    nrows, np, max_splits, ppwg, ks, key_ld, vocab_off); merged=True stands for a non-null `part` (wo). norm: whether a
+    norm weight is passed (default: as the role requires)."""
+    merged = shape.pop("merged", False) or shape.get("ks", 1) > 1
+    e = _lib.GemvEpilogue(role=role, **shape)
+    if merged:
+        e.part = 16  # only its presence is read
+    if norm is None:
+        norm = role in (GV_ROLE_QKV, GV_ROLE_GATE_UP, GV_ROLE_LOGITS)
+    p = _lib.GemvPlan(cus=cus)
+    call("sli_decode_gemv_plan", w_dtype, cols, int(norm), ctypes.byref(e), ctypes.byref(p))
+    return _gv_plan_dict(p)
+
+
+def _decode_gemv(x, norm_w, eps, w, row_scale, scales, epi, rows, cus):
+    """sli_decode_gemv / sli_decode_gemv_mxfp4 (scales given: w is the uint8 data [rows, cols / 2]). Returns the plan
+    that ran as a dict."""
+    mx = scales is not None
+    if mx:
+        if row_scale is not None:
+            raise ValueError("MXFP4 weights have block scales, not a row scale: pass scales or row_scale, not both")
+        cols = w.shape[1] * 2
+        if w.dtype != torch.uint8 or scales.dtype != torch.uint8 or w.shape[0] != rows or cols % 32 or \
+                scales.shape != (rows, cols // 32):
+            raise ValueError("Tensor with Wrong Dim!")
+    else:
+        cols = w.shape[1]
+        if w.dim() != 2 or w.shape[0] != rows or w.dtype not in (torch.float32, torch.float16, torch.int8):
+            raise ValueError("Tensor with Wrong Dim!")
+        if row_scale is not None and (row_scale.numel() != rows or row_scale.dtype != torch.float32):
+            raise ValueError("Tensor with Wrong Dim!")
+    for t in (x, norm_w):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError("Tensor with Wrong Dim!")
+    _dev(x, norm_w, w, row_scale, scales)
+    p = _lib.GemvPlan(cus=cus)
+    if mx:
+        call("sli_decode_gemv_mxfp4", _p(x), _p(norm_w), eps, _p(w), _p(scales), cols, ctypes.byref(epi), ctypes.byref(p),
+             _s())
+    else:
+        call("sli_decode_gemv", _p(x), _p(norm_w), eps, _p(w), _DT[w.dtype], _p(row_scale), cols, ctypes.byref(epi),
+             ctypes.byref(p), _s())
+    return _gv_plan_dict(p)
+
+
+def _gv_cols(w, scales):
+    return w.shape[1] * (2 if scales is not None else 1)
+
+
+# With `scales` given, every decode_gemv_* below runs MXFP4 weights, as the batch_gemm_* wrappers do. cus: sli_gemv_plan.
+def decode_gemv_qkv(x, norm_w, eps: float, w, q, kc, vc, pos, sin_t, cos_t, hq: int, hkv: int, hd: int, row_scale=None,
+                    scales=None, kv_dtype=None, cus: int = 0):
+    """One batch-1 q/k/v GEMV launch (fused RMSNorm, row scale, RoPE, K/V cache write): x [K] fp32, W [(hq + 2 hkv) hd,
+    K]; q [hq hd] fp32; kc / vc one layer's cache [hkv, T, hd]; pos int32 [1] on the device, 0 <= pos < T."""
+    if kc.shape != vc.shape or kc.dtype != vc.dtype or kc.dim() != 3 or kc.shape[0] != hkv or kc.shape[2] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[1]
+    K = _gv_cols(w, scales)
+    if x.numel() != K or norm_w.numel() != K or q.numel() != hq * hd or q.dtype != torch.float32 or \
+            sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2) or pos.dtype != torch.int32 or pos.numel() != 1:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, pos, sin_t, cos_t)
+    e = _lib.GemvEpilogue(role=GV_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                          kv_dtype=_kv_dt(kc, kv_dtype), pos=pos.data_ptr(), sin_t=sin_t.data_ptr(),
+                          cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv, hd=hd, T=T)
+    return _decode_gemv(x, norm_w, eps, w, row_scale, scales, e, (hq + 2 * hkv) * hd, cus)
+
+
+def decode_gemv_gate_up(x, norm_w, eps: float, w, act, act_mode: int = 0, parts=None, row_scale=None, scales=None,
+                        cus: int = 0):
+    """One batch-1 gate/up GEMV launch: W [2 inter, K] = [gate; up]; act [inter] fp32. parts [np, K] (np 2 or 4): the
+    staged input is x + parts[0] + ... (the K-split wo's consumer), then normalised."""
+    inter = w.shape[0] // 2
+    K = _gv_cols(w, scales)
+    if x.numel() != K or norm_w.numel() != K or act.numel() < inter or act.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if parts is not None and (parts.dim() != 2 or parts.shape[1] != K or parts.dtype != torch.float32):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(act, parts)
+    e = _lib.GemvEpilogue(role=GV_ROLE_GATE_UP, act=act.data_ptr(), inter=inter, act_mode=act_mode,
+                          parts=parts.data_ptr() if parts is not None else None,
+                          np=parts.shape[0] if parts is not None else 0)
+    return _decode_gemv(x, norm_w, eps, w, row_scale, scales, e, 2 * inter, cus)
+
+
+def decode_gemv_wo(w, y=None, x=None, resid=None, part=None, pos=None, ppwg: int = 0, hd: int = 0, ks: int = 1,
+                   kpart=None, row_scale=None, scales=None, cus: int = 0):
+    """One batch-1 wo GEMV launch. x given: a plain input, y [>= nrows] = (resid or 0) + W x. part [heads, max_splits,
+    hd + 4] given (with pos int32 [1], ppwg, hd): the input is merged from the attention's split partials. ks 2 or 4:
+    the K-split launch, kpart [ks, nrows] gets the per-column-block sums and y / resid are not used."""
+    nrows = w.shape[0]
+    K = _gv_cols(w, scales)
+    e = _lib.GemvEpilogue(role=GV_ROLE_WO, nrows=nrows, ks=ks)
+    if part is not None:
+        if part.dim() != 3 or part.dtype != torch.float32 or part.shape[2] != hd + 4 or part.shape[0] * hd != K or \
+                pos is None or pos.dtype != torch.int32 or pos.numel() != 1 or x is not None:
+            raise ValueError("Tensor with Wrong Dim!")
+        e.part, e.pos, e.max_splits, e.ppwg, e.hq, e.hd = part.data_ptr(), pos.data_ptr(), part.shape[1], ppwg, \
+            part.shape[0], hd
+    elif x is None or x.numel() != K:
+        raise ValueError("Tensor with Wrong Dim!")
+    if ks > 1:
+        if kpart is None or kpart.shape != (ks, nrows) or kpart.dtype != torch.float32:
+            raise ValueError("Tensor with Wrong Dim!")
+        e.kpart = kpart.data_ptr()
+    else:
+        if y is None or y.numel() < nrows or y.dtype != torch.float32 or (resid is not None and resid.numel() < nrows):
+            raise ValueError("Tensor with Wrong Dim!")
+        e.y = y.data_ptr()
+        e.resid = resid.data_ptr() if resid is not None else None
+    _dev(y, resid, part, pos, kpart)
+    return _decode_gemv(x, None, 0.0, w, row_scale, scales, e, nrows, cus)
+
+
+def decode_gemv_down(x, w, y, resid=None, parts=None, row_scale=None, scales=None, cus: int = 0):
+    """One batch-1 down GEMV launch: y [>= nrows] = (resid or 0) + W x; parts [np, nrows] (np 2 or 4): the residual
+    is resid + parts[0] + ... in that order (the K-split wo's consumer)."""
+    nrows = w.shape[0]
+    if x.numel() != _gv_cols(w, scales) or y.numel() < nrows or y.dtype != torch.float32 or \
+            (resid is not None and resid.numel() < nrows):
+        raise ValueError("Tensor with Wrong Dim!")
+    if parts is not None and (parts.dim() != 2 or parts.shape[1] != nrows or parts.dtype != torch.float32):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid, parts)
+    e = _lib.GemvEpilogue(role=GV_ROLE_DOWN, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                          nrows=nrows, parts=parts.data_ptr() if parts is not None else None,
+                          np=parts.shape[0] if parts is not None else 0)
+    return _decode_gemv(x, None, 0.0, w, row_scale, scales, e, nrows, cus)
+
+
+def decode_gemv_logits(x, norm_w, eps: float, w, logits, keys, vocab_off: int = 0, row_scale=None, scales=None,
+                       cus: int = 0):
+    """One batch-1 LM-head GEMV launch: logits [>= nrows] fp32 of the RMS-normalised x and, in keys [key_ld] (int64
+    holding the uint64 keys), each workgroup's largest argmax key."""
+    nrows = w.shape[0]
+    K = _gv_cols(w, scales)
+    if x.numel() != K or norm_w.numel() != K or logits.numel() < nrows or logits.dtype != torch.float32 or \
+            keys.dtype != torch.int64 or keys.dim() != 1:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(logits, keys)
+    e = _lib.GemvEpilogue(role=GV_ROLE_LOGITS, logits=logits.data_ptr(), keys=keys.data_ptr(), nrows=nrows,
+                          vocab_off=vocab_off, key_ld=keys.numel())
+    return _decode_gemv(x, norm_w, eps, w, row_scale, scales, e, nrows, cus)
+
+
 def argmax(logits, out=None):
     """argmaxLayer::forward (argmax.cpp:7-17) on device: first index of the maximum."""
     out = torch.empty(1, device=logits.device, dtype=torch.int32) if out is None else out
