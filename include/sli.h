@@ -429,6 +429,66 @@ int sli_model_score_seqs_ok(const sli_model* m); /* 1: the model takes sli_model
  * logits of the step that fed position t, NaN for t < lens[b] - 1. */
 int sli_model_predict_batch_prefill(sli_model* m, const int32_t* prompts, const int32_t* lens, int32_t ld,
                                     int32_t max_length, int32_t* tokens_out, float* logits_out);
+/* Continuing sequences: prefill and score from a start position.
+ *
+ * The packing rule with a start (host only). Sequence seqs[i] contributes rows for its positions starts[i] ..
+ * starts[i] + counts[i] - 2 (its last token is left for an ordinary decode step). Its first group runs from the start
+ * to the next 16-boundary of its own positions: {seq, s, min(16 - s % 16, counts[i] - 1)}; every later group is aligned
+ * (p0 % 16 == 0) as in sli_prefill_pack; a count of 1 contributes nothing. Concatenation in list order, 16 groups to a
+ * chunk, the last chunk's size bucket and the padding groups are sli_prefill_pack's, and with every start 0 and counts =
+ * lens the output is sli_prefill_pack's entry for entry (one planner serves both). A row at or past the first boundary
+ * keeps the group-mates it has in the from-zero plan; a row of a partial first group only meets key tiles that are
+ * masked for it. SLI_ERR_RANGE for a buffer that is too small, a count below 1, a start below 0. */
+int sli_prefill_pack_from(const int32_t* seqs, const int32_t* starts, const int32_t* counts, int32_t n_seqs,
+                          sli_pf_group* groups, int32_t cap_groups, int32_t* chunk_rows, int32_t cap_chunks,
+                          int32_t* n_chunks);
+/* Extend the listed sequences of a model of batch 1 .. 8 from a start position each: tokens is [n_seqs][ld], tokens[i][j]
+ * the token at position starts[i] + j, counts[i] of them; starts == NULL means each sequence's current position. Rows
+ * [0, pos_i) of a sequence's cache are taken as valid, pos_i its state position (a fresh or reset sequence: 0). The
+ * chunks, packed by the rule above, replay the graphs sli_model_prefill_seqs captured (one per chunk size); the same
+ * models, the same SLI_ERR_STATE refusals, sli_model_set_prefill ignored. Afterwards sequence seqs[i] is at (token
+ * tokens[i][counts[i]-1], position starts[i] + counts[i] - 1), n_forced = starts[i] + counts[i]; its prompt and history
+ * hold the tokens at [start, start + count), history below the start is kept; cache rows below the start and every
+ * unlisted sequence's rows, state, prompt and history are untouched. advance == 1 leaves the sequences advancing, as
+ * sli_model_prefill_seqs does; advance == 0 leaves them waiting (idempotent steps) while the rest of the batch steps: a
+ * partly admitted prompt. A start below the position is a rollback: rows from the start on are overwritten as they are
+ * recomputed, rows past the new end stay stale and are never read. On a fresh model a call with every start 0 is
+ * sli_model_prefill_seqs bit for bit.
+ * The arguments are judged before any state or device memory is touched, each condition over every listed sequence
+ * before the next: n_seqs outside [1, batch], a sequence out of range or listed twice: SLI_ERR_ARG; then SLI_ERR_RANGE
+ * for counts[i] outside [1, ld]; starts[i] + counts[i] > max_len; a token outside the vocabulary; starts[i] outside
+ * [0, pos_i]. */
+int sli_model_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                          const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance);
+/* sli_model_extend_seqs through the scoring graphs of sli_model_score_seqs (the same models as that call). Outputs are
+ * host arrays [n_seqs][ld]: entry (i, j), 1 <= j < counts[i], is about tokens[i][j] given everything before it; entry
+ * (i, 0) and the entries at j >= counts[i] are NaN / -1 / NaN. top and top_logprob may be NULL. What it leaves behind
+ * is bit for bit what sli_model_extend_seqs leaves. */
+int sli_model_score_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                                const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance,
+                                float* logprob, int32_t* top, float* top_logprob);
+/* The one-sequence route of a batch-1 model, beside sli_model_prefill: tokens[j] is the token at position start + j
+ * (start == -1: the current position), the checks of sli_model_extend_seqs in their order. It follows
+ * sli_model_set_prefill as sli_model_prefill does: on the GEMM path the group table is filled by the rule above,
+ * otherwise the tokens are teacher-forced through the decode step from the start. An fp32 K/V cache always continues
+ * through the decode step when start > 0 (its chunk attention takes consecutive 64-row blocks only). The sequence is left
+ * advancing at its last token. */
+int sli_model_extend(sli_model* m, const int32_t* tokens, int32_t start, int32_t count);
+/* Test hook (no device needed): the argument checks of the extend calls, in their order, as a model of `batch`
+ * sequences standing at pos[0 .. batch), max_len `max_len` and `vocab` tokens makes them. starts may be NULL. */
+int sli_debug_extend_seqs_args(int32_t batch, int32_t max_len, int32_t vocab, const int32_t* pos, const int32_t* seqs,
+                               int32_t n_seqs, const int32_t* tokens, const int32_t* starts, const int32_t* counts,
+                               int32_t ld);
+/* Prefix copy between sequences (csrc/kv_copy.h): K and V rows [0, n) of every layer and kv head from sequence src to
+ * sequence dst, one launch of 16-byte vector copies on the stream. kc / vc: [L][B][hkv][T][hd] of elem_bytes (1, 2 or
+ * 4) bytes per element, 16-byte aligned; a row (hd * elem_bytes) at least 64 bytes and a multiple of 16; src != dst,
+ * both < B; 0 <= n <= T (0: nothing is launched). Every other byte of both caches is untouched. */
+int sli_kv_copy_prefix(void* kc, void* vc, int32_t elem_bytes, int32_t L, int32_t B, int32_t hkv, int32_t T, int32_t hd,
+                       int32_t src, int32_t dst, int32_t n, sli_stream_t stream);
+/* The same on a model's own cache, with history [0, n]: src != dst (SLI_ERR_ARG), 0 <= n <= src's position
+ * (SLI_ERR_RANGE). dst is left waiting at (src's token at position n, position n, not advancing), so it can be extended
+ * from any start <= n; src and every other sequence are untouched. */
+int sli_model_copy_prefix(sli_model* m, int32_t src, int32_t dst, int32_t n);
 /* The tokens fed at positions [0, n) of sequence seq. */
 int sli_model_get_history(sli_model* m, int32_t seq, int32_t n, int32_t* out);
 /* Execution of the step: SLI_EXEC_LAUNCHES, one hipGraph of ~5 fused launches per layer (every configuration);
@@ -516,6 +576,11 @@ int sli_tp_group_predict_prefill(sli_tp_group* g, const int32_t* prompt, int32_t
                                  int32_t* tokens_out, float* logits_out);
 /* sli_model_set_prefill for every rank of the group. */
 int sli_tp_group_set_prefill(sli_tp_group* g, int32_t mode);
+/* sli_model_extend over the group (batch-1 groups): every rank continues from the start in lockstep, on the GEMM
+ * chunks or teacher-forced through the group's decode step as sli_tp_group_prefill chooses. */
+int sli_tp_group_extend(sli_tp_group* g, const int32_t* tokens, int32_t start, int32_t count);
+/* sli_model_copy_prefix on every rank's shard of the cache. */
+int sli_tp_group_copy_prefix(sli_tp_group* g, int32_t src, int32_t dst, int32_t n);
 
 /* Roofline probe: replays the step's weight-streaming (GEMV) kernels `iters` times between HIP events
  * on the model's stream; returns mean device time per GEMV launch, algorithmic bytes per launch and

@@ -226,6 +226,15 @@ _SIGS = {
     "sli_tp_group_predict_batch": (c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "sli_tp_group_prefill": (c_int, [c_vp, c_vp, c_i32]),
     "sli_tp_group_predict_prefill": (c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "sli_prefill_pack_from": (c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, P_i32]),
+    "sli_model_extend_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32]),
+    "sli_model_score_extend_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sli_model_extend": (c_int, [c_vp, c_vp, c_i32, c_i32]),
+    "sli_debug_extend_seqs_args": (c_int, [c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32]),
+    "sli_kv_copy_prefix": (c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "sli_model_copy_prefix": (c_int, [c_vp, c_i32, c_i32, c_i32]),
+    "sli_tp_group_extend": (c_int, [c_vp, c_vp, c_i32, c_i32]),
+    "sli_tp_group_copy_prefix": (c_int, [c_vp, c_i32, c_i32, c_i32]),
 }
 
 _lib = None

@@ -29,6 +29,7 @@
 #include "comm_wait.h"
 #include "common.h"
 #include "gemv.h"
+#include "kv_copy.h"
 #include "oneshot.h"
 #include "ops_internal.h"
 #include "prefill.h"
@@ -2059,11 +2060,16 @@ static PfSegs pf_table(const PfPlan& pl, size_t c) {
     }
     return t;
 }
-static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
+// With a start (sli.h at sli_prefill_pack_from): sequence i's positions starts[i] .. starts[i] + counts[i] - 2, its
+// first group from the start to the next 16-boundary of its positions, every later one aligned as above. starts ==
+// nullptr: every start 0, the rule above (lens = counts).
+static PfPlan pf_pack_from(const int32_t* seqs, const int32_t* starts, const int32_t* counts, int n_seqs) {
     PfPlan pl;
-    for (int i = 0; i < n_seqs; ++i)
-        for (int p0 = 0; p0 < lens[i] - 1; p0 += 16)
-            pl.groups.push_back(sli_pf_group{seqs[i], p0, std::min(16, lens[i] - 1 - p0)});
+    for (int i = 0; i < n_seqs; ++i) {
+        const int s = starts ? starts[i] : 0, end = s + counts[i] - 1;  // rows for positions [s, end)
+        for (int p0 = s; p0 < end; p0 = (p0 / 16 + 1) * 16)
+            pl.groups.push_back(sli_pf_group{seqs[i], p0, std::min((p0 / 16 + 1) * 16, end) - p0});
+    }
     const int ng = (int)pl.groups.size();
     for (int g0 = 0; g0 < ng; g0 += kPfGroups) {
         const int rows = kPfSizes[pf_bucket(16 * std::min(kPfGroups, ng - g0))];
@@ -2075,6 +2081,9 @@ static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
         pl.groups.resize(total, sli_pf_group{pad_seq, 0, 0});
     }
     return pl;
+}
+static PfPlan pf_pack(const int32_t* seqs, const int32_t* lens, int n_seqs) {
+    return pf_pack_from(seqs, nullptr, lens, n_seqs);
 }
 // Enqueues a plan on `stream`: a graph per chunk size it lacks (record(M): the launches of an M-row chunk), captured
 // before anything is enqueued behind the capture; then per chunk its table, copied to every entry of `dev` (an
@@ -2204,6 +2213,26 @@ extern "C" int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_
     const PfPlan pl = pf_pack(seqs, lens, n_seqs);
     SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
               "sli_prefill_pack: the group or chunk buffer is too small");
+    std::copy(pl.groups.begin(), pl.groups.end(), groups);
+    std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
+    *n_chunks = (int32_t)pl.rows.size();
+    return SLI_OK;
+}
+
+extern "C" int sli_prefill_pack_from(const int32_t* seqs, const int32_t* starts, const int32_t* counts, int32_t n_seqs,
+                                     sli_pf_group* groups, int32_t cap_groups, int32_t* chunk_rows, int32_t cap_chunks,
+                                     int32_t* n_chunks) {
+    SLI_CHECK(seqs && starts && counts && n_chunks && (groups || cap_groups == 0) && (chunk_rows || cap_chunks == 0),
+              SLI_ERR_ARG, "sli_prefill_pack_from: null argument");
+    SLI_CHECK(n_seqs >= 0 && cap_groups >= 0 && cap_chunks >= 0, SLI_ERR_ARG, "sli_prefill_pack_from: negative count");
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(counts[i] >= 1, SLI_ERR_RANGE, "sli_prefill_pack_from: a count below 1");
+        SLI_CHECK(starts[i] >= 0 && starts[i] <= (1 << 30) && counts[i] <= (1 << 30), SLI_ERR_RANGE,
+                  "sli_prefill_pack_from: a start below 0, or a start or count above 2^30");
+    }
+    const PfPlan pl = pf_pack_from(seqs, starts, counts, n_seqs);
+    SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
+              "sli_prefill_pack_from: the group or chunk buffer is too small");
     std::copy(pl.groups.begin(), pl.groups.end(), groups);
     std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
     *n_chunks = (int32_t)pl.rows.size();
@@ -2345,6 +2374,259 @@ static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const 
     // each sequence's last prompt position is an ordinary decode step
     for (int i = 0; i < n_seqs; ++i)
         SLI_TRY(set_state(m, seqs[i], prompts[(size_t)i * ld + lens[i] - 1], lens[i] - 1, 1));
+    return SLI_OK;
+}
+
+// ---------------------------------------------------------------- continuing sequences from a start position
+// The argument checks of the extend calls for a model of batch B, max_len T and vocabulary V whose sequences stand at
+// pos[0 .. B), in their one order (sli.h at sli_model_extend_seqs): each condition over every listed sequence before the
+// next condition. starts == nullptr: each sequence's own position. Host only.
+static int ext_args(int B, int T, int V, const int32_t* pos, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                    const int32_t* starts, const int32_t* counts, int32_t ld) {
+    SLI_CHECK(n_seqs >= 1 && n_seqs <= B, SLI_ERR_ARG, "extend_seqs: n_seqs must be in [1, batch]");
+    for (int i = 0; i < n_seqs; ++i) {
+        SLI_CHECK(seqs[i] >= 0 && seqs[i] < B, SLI_ERR_ARG, "extend_seqs: sequence index out of range");
+        for (int j = 0; j < i; ++j) SLI_CHECK(seqs[j] != seqs[i], SLI_ERR_ARG, "extend_seqs: a sequence is listed twice");
+    }
+    auto start = [&](int i) { return (int64_t)(starts ? starts[i] : pos[seqs[i]]); };
+    for (int i = 0; i < n_seqs; ++i)
+        SLI_CHECK(counts[i] >= 1 && counts[i] <= ld, SLI_ERR_RANGE, "extend_seqs: a count outside [1, ld]");
+    for (int i = 0; i < n_seqs; ++i)
+        SLI_CHECK(start(i) + counts[i] <= T, SLI_ERR_RANGE, "extend_seqs: start + count exceeds max_len");
+    for (int i = 0; i < n_seqs; ++i)
+        for (int t = 0; t < counts[i]; ++t) {
+            const int32_t id = tokens[(size_t)i * ld + t];
+            SLI_CHECK(id >= 0 && id < V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
+        }
+    for (int i = 0; i < n_seqs; ++i)
+        SLI_CHECK(start(i) >= 0 && start(i) <= pos[seqs[i]], SLI_ERR_RANGE,
+                  "extend_seqs: a start outside [0, the sequence's position]");
+    return SLI_OK;
+}
+
+extern "C" int sli_debug_extend_seqs_args(int32_t batch, int32_t max_len, int32_t vocab, const int32_t* pos,
+                                          const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                                          const int32_t* starts, const int32_t* counts, int32_t ld) {
+    SLI_CHECK(pos && seqs && tokens && counts, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(batch >= 1, SLI_ERR_ARG, "extend_seqs: batch");
+    return ext_args(batch, max_len, vocab, pos, seqs, n_seqs, tokens, starts, counts, ld);
+}
+
+// the tokens of positions [start, start + count) of sequence seq, into its prompt and its history
+static int ext_put_tokens(sli_model* m, int seq, const int32_t* ids, int start, int count) {
+    const size_t off = (size_t)seq * (m->T + 1) + start;
+    SLI_HIP(hipMemcpyAsync(m->prompt + off, ids, sizeof(int32_t) * count, hipMemcpyHostToDevice, m->stream));
+    SLI_HIP(hipMemcpyAsync(m->hist + off, ids, sizeof(int32_t) * count, hipMemcpyHostToDevice, m->stream));
+    return SLI_OK;
+}
+
+// what an extend leaves of the listed sequences' states (h: the states as downloaded before the call)
+static int ext_put_states(sli_model* m, std::vector<DevState>& h, const int32_t* seqs, int n_seqs, const int32_t* tokens,
+                          const int32_t* starts, const int32_t* counts, int ld, int advance) {
+    for (int i = 0; i < n_seqs; ++i) {
+        DevState& d = h[seqs[i]];
+        d.token = tokens[(size_t)i * ld + counts[i] - 1];
+        d.pos = starts[i] + counts[i] - 1;
+        d.n_forced = starts[i] + counts[i];
+        d.advance = advance ? 1 : 0;
+        d.key = 0;
+        d.error = 0;
+    }
+    return upload_states(m, h);
+}
+
+static int ext_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens, const int32_t* starts,
+                        const int32_t* counts, int32_t ld, int32_t advance, const PfScoreOut* score) {
+    SLI_HIP(hipSetDevice(m->c.device));
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m, h));  // a read: every argument is judged before any state or device memory is touched
+    std::vector<int32_t> pos(m->B);
+    for (int b = 0; b < m->B; ++b) pos[b] = h[b].pos;
+    SLI_TRY(ext_args(m->B, m->T, m->V, pos.data(), seqs, n_seqs, tokens, starts, counts, ld));
+    std::vector<int32_t> st(n_seqs);
+    for (int i = 0; i < n_seqs; ++i) st[i] = starts ? starts[i] : pos[seqs[i]];
+    if (score) SLI_TRY(score_alloc(m));  // a failed allocation leaves the sequences as they were
+    for (int i = 0; i < n_seqs; ++i) SLI_TRY(ext_put_tokens(m, seqs[i], tokens + (size_t)i * ld, st[i], counts[i]));
+    const PfPlan pl = pf_pack_from(seqs, st.data(), counts, n_seqs);
+    if (!pl.rows.empty()) {
+        SLI_TRY(pf_alloc(m));
+        std::vector<PfSegs> tabs;
+        if (score)
+            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.scgraph, m->pf.scexec, {m->pf.segs},
+                               [&](int M) { return SLI_DISPATCH(m, record_score_segs, m, M); }));
+        else
+            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
+                               [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
+        SLI_TRY(wait_stream(m));
+    }
+    if (score) {  // entry (i, j), 1 <= j < counts[i]: slot (seqs[i], start + j) of the device buffers
+        const size_t n = (size_t)n_seqs * ld;
+        std::fill_n(score->logprob, n, NAN);
+        if (score->top) std::fill_n(score->top, n, -1);
+        if (score->top_logprob) std::fill_n(score->top_logprob, n, NAN);
+        for (int i = 0; i < n_seqs; ++i) {
+            if (counts[i] < 2) continue;
+            const size_t src = (size_t)seqs[i] * (m->T + 1) + st[i] + 1, dst = (size_t)i * ld + 1;
+            const size_t cnt = (size_t)counts[i] - 1;
+            SLI_HIP(hipMemcpyAsync(score->logprob + dst, m->pf.sc_lp + src, sizeof(float) * cnt, hipMemcpyDeviceToHost,
+                                   m->stream));
+            if (score->top)
+                SLI_HIP(hipMemcpyAsync(score->top + dst, m->pf.sc_top + src, sizeof(int32_t) * cnt,
+                                       hipMemcpyDeviceToHost, m->stream));
+            if (score->top_logprob)
+                SLI_HIP(hipMemcpyAsync(score->top_logprob + dst, m->pf.sc_tlp + src, sizeof(float) * cnt,
+                                       hipMemcpyDeviceToHost, m->stream));
+        }
+        SLI_TRY(wait_stream(m));
+    }
+    // each sequence's last token is an ordinary decode step (or waits: advance == 0)
+    return ext_put_states(m, h, seqs, n_seqs, tokens, st.data(), counts, ld, advance);
+}
+
+extern "C" int sli_model_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                                     const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance) {
+    SLI_CHECK(m && seqs && tokens && counts, SLI_ERR_ARG, "null argument");
+    if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    return ext_seqs_run(m, seqs, n_seqs, tokens, starts, counts, ld, advance, nullptr);
+}
+
+extern "C" int sli_model_score_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                                           const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance,
+                                           float* logprob, int32_t* top, float* top_logprob) {
+    SLI_CHECK(m && seqs && tokens && counts && logprob, SLI_ERR_ARG, "null argument");
+    if (const char* why = score_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    const PfScoreOut out{logprob, top, top_logprob};
+    return ext_seqs_run(m, seqs, n_seqs, tokens, starts, counts, ld, advance, &out);
+}
+
+// The one-sequence routes (batch-1 models and groups): ranks = the model, or every rank of the group; step() one decode
+// step of them; enqueue(plan, tabs) the GEMM chunks of a plan and the wait for them. start == -1: the current position.
+template <class Step, class Enqueue>
+static int ext_one(const std::vector<sli_model*>& ranks, const int32_t* tokens, int32_t start, int32_t count, Step step,
+                   Enqueue enqueue) {
+    sli_model* m0 = ranks[0];
+    std::vector<DevState> h0;
+    SLI_TRY(download_states(m0, h0));
+    const int32_t seq0 = 0, pos0 = h0[0].pos;
+    const int32_t s = start == -1 ? pos0 : start;
+    SLI_TRY(ext_args(1, m0->T, m0->V, &pos0, &seq0, 1, tokens, &s, &count, std::max(count, 1)));
+    for (sli_model* m : ranks) SLI_TRY(ext_put_tokens(m, 0, tokens, s, count));
+    // an fp32 cache continues through the decode step: pf_attn_kernel's 64-row blocks are consecutive positions from
+    // their first group's p0, which a partial first group is not
+    const bool gemm = count > 1 && pf_use_gemm(m0) && (s == 0 || m0->c.kv_dtype != SLI_DT_F32);
+    if (gemm) {
+        for (sli_model* m : ranks) SLI_TRY(pf_alloc(m));
+        std::vector<PfSegs> tabs;
+        SLI_TRY(enqueue(pf_pack_from(&seq0, &s, &count, 1), tabs));
+    } else {
+        for (int j = 0; j < count - 1; ++j) {  // the decode step, teacher-forced
+            for (sli_model* m : ranks) SLI_TRY(set_state(m, 0, tokens[j], s + j, 0));
+            SLI_TRY(step());
+        }
+    }
+    for (sli_model* m : ranks) {
+        std::vector<DevState> h;
+        SLI_TRY(download_states(m, h));
+        SLI_TRY(ext_put_states(m, h, &seq0, 1, tokens, &s, &count, count, 1));
+    }
+    return SLI_OK;
+}
+
+extern "C" int sli_model_extend(sli_model* m, const int32_t* tokens, int32_t start, int32_t count) {
+    SLI_CHECK(m && tokens, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(m->B == 1, SLI_ERR_STATE, "extend: batch-1 models (a batch extends through sli_model_extend_seqs)");
+    SLI_CHECK(!m->group, SLI_ERR_STATE, "extend: ranks of an in-process group extend through sli_tp_group_extend");
+    SLI_CHECK(!m->comm_dead, SLI_ERR_COMM, "the RCCL communicator was aborted by an earlier bounded wait");
+    SLI_HIP(hipSetDevice(m->c.device));
+    return ext_one({m}, tokens, start, count, [&] { return sli_model_step(m); },
+                   [&](const PfPlan& pl, std::vector<PfSegs>& tabs) -> int {
+                       SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
+                                          [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
+                       return wait_stream(m);
+                   });
+}
+
+extern "C" int sli_tp_group_extend(sli_tp_group* g, const int32_t* tokens, int32_t start, int32_t count) {
+    SLI_CHECK(g && tokens, SLI_ERR_ARG, "null argument");
+    sli_model* m0 = g->ranks[0];
+    SLI_CHECK(m0->B == 1, SLI_ERR_STATE, "extend: batch-1 groups");
+    SLI_HIP(hipSetDevice(g->device));
+    return ext_one(g->ranks, tokens, start, count, [&] { return sli_tp_group_step(g); },
+                   [&](const PfPlan& pl, std::vector<PfSegs>& tabs) -> int {
+                       std::vector<PfSegs*> dev;
+                       for (sli_model* m : g->ranks) dev.push_back(m->pf.segs);
+                       SLI_TRY(pf_enqueue(pl, tabs, g->stream, g->pf_graph, g->pf_exec, dev,
+                                          [&](int M) { return SLI_DISPATCH(m0, record_group_prefill, g, M); }));
+                       SLI_HIP(hipStreamSynchronize(g->stream));
+                       return SLI_OK;
+                   });
+}
+
+// ---------------------------------------------------------------- prefix copy between sequences (kv_copy.h)
+static int copy_prefix_rank(sli_model* m, int src, int dst, int n, int32_t tok) {
+    KvCopyArgs a{(char*)m->kc, (char*)m->vc, m->B, m->hkv, m->T, (int)(m->hd * m->kvbytes), src, dst, n};
+    SLI_HIP(launch_kv_copy_prefix(a, m->L, m->stream));
+    const size_t ld = (size_t)m->T + 1;
+    SLI_HIP(hipMemcpyAsync(m->hist + dst * ld, m->hist + src * ld, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToDevice,
+                           m->stream));
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m, h));
+    DevState& d = h[dst];
+    d.token = tok;
+    d.pos = n;
+    d.n_forced = n + 1;
+    d.advance = 0;
+    d.key = 0;
+    d.error = 0;
+    return upload_states(m, h);
+}
+
+// the checks, and src's token at position n (its history entry: n <= pos_src, and the pending token stands at pos_src)
+static int copy_prefix_args(sli_model* m, int src, int dst, int n, int32_t* tok) {
+    SLI_CHECK(src >= 0 && src < m->B && dst >= 0 && dst < m->B, SLI_ERR_ARG, "copy_prefix: sequence index out of range");
+    SLI_CHECK(src != dst, SLI_ERR_ARG, "copy_prefix: src and dst must differ");
+    SLI_CHECK((m->hd * m->kvbytes) % 16 == 0 && (int64_t)m->L * m->hkv * 2 <= 65535, SLI_ERR_STATE,
+              "copy_prefix: a cache row must be a multiple of 16 bytes (and layers * kv heads <= 32767)");
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m, h));
+    SLI_CHECK(n >= 0 && n <= h[src].pos, SLI_ERR_RANGE, "copy_prefix: n must be in [0, the source's position]");
+    SLI_HIP(hipMemcpyAsync(tok, m->hist + (size_t)src * (m->T + 1) + n, sizeof(int32_t), hipMemcpyDeviceToHost,
+                           m->stream));
+    return wait_stream(m);
+}
+
+extern "C" int sli_kv_copy_prefix(void* kc, void* vc, int32_t elem_bytes, int32_t L, int32_t B, int32_t hkv, int32_t T,
+                                  int32_t hd, int32_t src, int32_t dst, int32_t n, sli_stream_t stream) {
+    SLI_CHECK(kc && vc, SLI_ERR_ARG, "sli_kv_copy_prefix: null pointer");
+    SLI_CHECK(((uintptr_t)kc | (uintptr_t)vc) % 16 == 0, SLI_ERR_ARG, "sli_kv_copy_prefix: kc / vc must be 16-byte aligned");
+    SLI_CHECK(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, SLI_ERR_ARG, "sli_kv_copy_prefix: elem_bytes must be 1, 2 or 4");
+    SLI_CHECK(L >= 1 && B >= 1 && hkv >= 1 && T >= 1 && hd >= 1 && hd <= 4096 && (int64_t)L * hkv * 2 <= 65535,
+              SLI_ERR_SHAPE, "sli_kv_copy_prefix: L, B, hkv, T, hd must be positive (hd <= 4096, L * hkv <= 32767)");
+    SLI_CHECK(hd * elem_bytes >= 64 && hd * elem_bytes % 16 == 0, SLI_ERR_SHAPE,
+              "sli_kv_copy_prefix: a row (hd * elem_bytes) must be at least 64 bytes and a multiple of 16");
+    SLI_CHECK(src >= 0 && src < B && dst >= 0 && dst < B, SLI_ERR_ARG, "sli_kv_copy_prefix: sequence index out of range");
+    SLI_CHECK(src != dst, SLI_ERR_ARG, "sli_kv_copy_prefix: src and dst must differ");
+    SLI_CHECK(n >= 0 && n <= T, SLI_ERR_RANGE, "sli_kv_copy_prefix: n must be in [0, T]");
+    const KvCopyArgs a{(char*)kc, (char*)vc, B, hkv, T, hd * elem_bytes, src, dst, n};
+    SLI_HIP(launch_kv_copy_prefix(a, L, as_stream(stream)));
+    return SLI_OK;
+}
+
+extern "C" int sli_model_copy_prefix(sli_model* m, int32_t src, int32_t dst, int32_t n) {
+    SLI_CHECK(m, SLI_ERR_ARG, "null model");
+    SLI_CHECK(!m->group, SLI_ERR_STATE, "copy_prefix: ranks of an in-process group copy through sli_tp_group_copy_prefix");
+    SLI_HIP(hipSetDevice(m->c.device));
+    int32_t tok = 0;
+    SLI_TRY(copy_prefix_args(m, src, dst, n, &tok));
+    return copy_prefix_rank(m, src, dst, n, tok);
+}
+
+extern "C" int sli_tp_group_copy_prefix(sli_tp_group* g, int32_t src, int32_t dst, int32_t n) {
+    SLI_CHECK(g, SLI_ERR_ARG, "null argument");
+    SLI_HIP(hipSetDevice(g->device));
+    int32_t tok = 0;
+    SLI_TRY(copy_prefix_args(g->ranks[0], src, dst, n, &tok));
+    for (sli_model* m : g->ranks) SLI_TRY(copy_prefix_rank(m, src, dst, n, tok));
     return SLI_OK;
 }
 

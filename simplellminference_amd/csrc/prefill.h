@@ -47,8 +47,9 @@ constexpr int kPfMaxChunk = 256;  // prompt positions per weight pass
 // The row map of a chunk: chunk rows 16 g .. 16 g + 15 are positions p0[g] .. p0[g] + 15 of sequence seq[g], the first
 // nv[g] of them valid (the rest is padding: computed, never written to the cache); nv[g] == 0 is a padding group,
 // which writes nothing to the cache and skips its attention. The engine's plans keep p0 % 16 == 0, so a row has the
-// same 15 group-mates, and so the same attention tiles, however its sequence is packed; the kernels
-// themselves take any p0.
+// same 15 group-mates, and so the same attention tiles, however its sequence is packed; the one exception
+// is the first group of a sequence continued from a start position (pf_pack_from), which runs from the start to the
+// next 16-boundary: its rows only gain key tiles that are masked for them. The kernels themselves take any p0.
 constexpr int kPfGroups = kPfMaxChunk / 16;
 struct PfSegs {
     int32_t seq[kPfGroups], p0[kPfGroups], nv[kPfGroups];

@@ -405,6 +405,103 @@ class LlamaModel:
             raise ValueError("no scored token: every prompt has length 1")
         return float(np.exp(-total / count))
 
+    # ------------------------------------------------------------------ continuing sequences from a start position
+    def _extend_args(self, tokens, seqs, starts):
+        if seqs is None and self.batch == 1 and len(tokens) and np.ndim(tokens[0]) == 0:
+            tokens = [tokens]  # one flat list for the one sequence of a batch-1 model
+        seqs = np.arange(len(tokens), dtype=np.int32) if seqs is None else np.ascontiguousarray(seqs, np.int32)
+        if seqs.size != len(tokens) or not len(tokens):
+            raise ValueError("one token list per listed sequence")
+        if starts is not None:
+            starts = np.ascontiguousarray(starts, np.int32)
+            if starts.shape != seqs.shape:
+                raise ValueError("one start per listed sequence")
+        P, counts, ld = self._ragged(tokens)
+        return tokens, seqs, starts, P, counts, ld
+
+    def extend(self, tokens, seqs=None, starts=None, advance: bool = True):
+        """Continue sequences ``seqs`` (default 0 .. len(tokens)-1) from positions ``starts`` (default: each sequence's
+        current position): tokens[i][j] is the token at position starts[i] + j. Rows below a sequence's position are
+        taken from its cache, the new rows run as packed MFMA GEMM chunks, and the sequence is left at its last token
+        (sli_model_extend_seqs; the models prefill_batch takes). ``advance=False`` leaves the sequences waiting while
+        the rest of the batch steps. A batch-1 model outside the packed route (fp32 weights or cache, a TP rank)
+        continues through extend_one, which follows set_prefill."""
+        tokens, seqs, starts, P, counts, ld = self._extend_args(tokens, seqs, starts)
+        call("sli_model_extend_seqs", self._h, seqs.ctypes.data_as(ctypes.c_void_p), seqs.size,
+             P.ctypes.data_as(ctypes.c_void_p), starts.ctypes.data_as(ctypes.c_void_p) if starts is not None else None,
+             counts.ctypes.data_as(ctypes.c_void_p), ld, 1 if advance else 0)
+
+    def extend_one(self, tokens, start: int | None = None):
+        """sli_model_extend: the one-sequence route of a batch-1 model, following set_prefill (the GEMM chunks, or the
+        tokens teacher-forced through the decode step from ``start``; default: the current position)."""
+        p = np.ascontiguousarray(tokens, np.int32)
+        call("sli_model_extend", self._h, p.ctypes.data_as(ctypes.c_void_p), -1 if start is None else int(start), p.size)
+
+    def append(self, tokens, seqs=None):
+        """The chat-turn call: append ``tokens[i]`` behind sequence ``seqs[i]``'s pending token. Each sequence's pending
+        token and position are read, and the sequence is extended from there with (pending token, *tokens[i]); it is
+        left advancing at the last appended token."""
+        tokens, seqs, _, _, _, _ = self._extend_args(tokens, seqs, None)
+        turn = []
+        for s, t in zip(seqs.tolist(), tokens):
+            turn.append([self.state(s)["token"], *[int(v) for v in t]])
+        self.extend(turn, seqs)
+
+    def score_extend(self, tokens, seqs=None, starts=None):
+        """extend(tokens, seqs, starts), and the log-probability of every token but each list's first given everything
+        before it (sli_model_score_extend_seqs). Records shaped like score()'s: arrays of length len(tokens[i]) - 1
+        whose entry j - 1 is about tokens[i][j]."""
+        tokens, seqs, starts, P, counts, ld = self._extend_args(tokens, seqs, starts)
+        lp = np.empty((len(tokens), ld), np.float32)
+        top = np.empty((len(tokens), ld), np.int32)
+        tlp = np.empty((len(tokens), ld), np.float32)
+        call("sli_model_score_extend_seqs", self._h, seqs.ctypes.data_as(ctypes.c_void_p), seqs.size,
+             P.ctypes.data_as(ctypes.c_void_p), starts.ctypes.data_as(ctypes.c_void_p) if starts is not None else None,
+             counts.ctypes.data_as(ctypes.c_void_p), ld, 1, lp.ctypes.data_as(ctypes.c_void_p),
+             top.ctypes.data_as(ctypes.c_void_p), tlp.ctypes.data_as(ctypes.c_void_p))
+        return [{"logprobs": lp[i, 1:n].copy(), "top": top[i, 1:n].copy(), "top_logprobs": tlp[i, 1:n].copy()}
+                for i, n in enumerate(int(x) for x in counts)]
+
+    def fork(self, src: int, dst: int, n: int | None = None):
+        """Copy the first ``n`` cache rows (default: all of src's, its position) and history [0, n] of sequence ``src``
+        to sequence ``dst`` (sli_model_copy_prefix): dst waits at (src's token at position n, position n) and can be
+        extended or appended to from there; src is untouched."""
+        call("sli_model_copy_prefix", self._h, src, dst, self.state(src)["pos"] if n is None else n)
+
+    def admit(self, prompts, seqs, max_tokens: int, between=None):
+        """Admit ``prompts`` into sequences ``seqs`` of a running batch in calls of at most ``max_tokens`` tokens per
+        sequence: extend() from position 0 on, the sequences waiting (advance=False) after every call but the last,
+        ``between()`` called after every call but the last (the running sequences' decode steps go there). A call that
+        is not a prompt's last ends one token past a multiple of 16 positions, so every call's rows are whole groups."""
+        if max_tokens < 2:
+            raise ValueError("max_tokens must be at least 2 (a call re-feeds the token the call before left pending)")
+        seqs = [int(s) for s in seqs]
+        prompts = [[int(v) for v in p] for p in prompts]
+        if len(prompts) != len(seqs) or not seqs or any(not p for p in prompts):
+            raise ValueError("one non-empty prompt per listed sequence")
+        # a call over tokens [lo, hi) fills rows lo .. hi - 2 and leaves token hi - 1 pending: the next call starts there.
+        # Where the prompt goes on, hi - 1 is brought down to a multiple of 16, so that the next call's first group is a
+        # whole one and a call's groups are not one more than its rows need (a 17th group is a second chunk).
+        def end(p, a):
+            hi = min(len(p), a + max_tokens)
+            cut = (hi - 1) // 16 * 16 + 1
+            return cut if hi < len(p) and cut - a >= 2 else hi
+
+        lo, first = [0] * len(seqs), True
+        while True:
+            hi = [end(p, a) for p, a in zip(prompts, lo)]
+            last = all(h == len(p) for h, p in zip(hi, prompts))
+            # a sequence whose prompt ended in an earlier call waits (one token from its position changes nothing) and
+            # is listed again in the last call, which releases every sequence together
+            live = [i for i in range(len(seqs)) if first or last or hi[i] - lo[i] > 1]
+            self.extend([prompts[i][lo[i]:hi[i]] for i in live], [seqs[i] for i in live], [lo[i] for i in live],
+                        advance=last)
+            if last:
+                return
+            lo, first = [h - 1 for h in hi], False
+            if between is not None:
+                between()
+
     def predict_batch_prefill(self, prompts, max_length: int, want_logits: bool = False):
         """predict_batch with the prompts prefilled (sli_model_predict_batch_prefill): tokens [batch, max_length],
         logits [batch, max_length, local vocab] with NaN rows at positions < len(prompt) - 1."""
@@ -584,6 +681,17 @@ class TPGroup:
         """sli_tp_group_prefill: the ranks' prefill chunks in lockstep (batch-1 groups)."""
         p = np.ascontiguousarray(prompt_ids, np.int32)
         call("sli_tp_group_prefill", self._g, p.ctypes.data_as(ctypes.c_void_p), p.size)
+
+    def extend(self, tokens, start: int | None = None):
+        """sli_tp_group_extend: continue the group's sequence from ``start`` (default: its current position) with
+        ``tokens``, tokens[j] at position start + j, on the route prefill() takes (batch-1 groups)."""
+        p = np.ascontiguousarray(tokens, np.int32)
+        call("sli_tp_group_extend", self._g, p.ctypes.data_as(ctypes.c_void_p), -1 if start is None else int(start),
+             p.size)
+
+    def fork(self, src: int, dst: int, n: int | None = None):
+        """LlamaModel.fork on every rank's shard of the cache (sli_tp_group_copy_prefix)."""
+        call("sli_tp_group_copy_prefix", self._g, src, dst, self.ranks[0].state(src)["pos"] if n is None else n)
 
     def predict_prefill(self, prompt_ids, max_length: int, want_logits: bool = False):
         """predict() with the prompt prefilled; logits [max_length, vocab], rows < len(prompt) - 1 NaN."""

@@ -431,6 +431,42 @@ def prefill_pack(lens, seqs=None):
     return groups[:ng].copy(), rows
 
 
+def prefill_pack_from(starts, counts, seqs=None):
+    """sli_prefill_pack_from (host only, no GPU): the chunks that continue sequences ``seqs`` (default 0 ..
+    len(counts)-1) from positions ``starts`` with ``counts`` tokens each. Returns (groups, chunk_rows) as prefill_pack
+    does; a sequence's first group starts at its start and ends at the next 16-boundary of its positions."""
+    import numpy as np
+    starts = np.ascontiguousarray(starts, np.int32)
+    counts = np.ascontiguousarray(counts, np.int32)
+    seqs = np.arange(counts.size, dtype=np.int32) if seqs is None else np.ascontiguousarray(seqs, np.int32)
+    if seqs.shape != counts.shape or starts.shape != counts.shape or counts.ndim != 1:
+        raise ValueError("prefill_pack_from: one start and one count per sequence")
+    cap_g = int(np.maximum(counts, 1).sum() // 16 + 2 * counts.size + 16)
+    cap_c = cap_g // 16 + 1
+    groups = np.zeros((cap_g, 3), np.int32)
+    rows = np.zeros(cap_c, np.int32)
+    n = ctypes.c_int32()
+    call("sli_prefill_pack_from", seqs.ctypes.data_as(ctypes.c_void_p), starts.ctypes.data_as(ctypes.c_void_p),
+         counts.ctypes.data_as(ctypes.c_void_p), counts.size, groups.ctypes.data_as(ctypes.c_void_p), cap_g,
+         rows.ctypes.data_as(ctypes.c_void_p), cap_c, ctypes.byref(n))
+    rows = rows[:n.value].copy()
+    ng = 0 if n.value == 0 else 16 * (n.value - 1) + int(rows[-1]) // 16
+    return groups[:ng].copy(), rows
+
+
+def kv_copy_prefix(kc, vc, src: int, dst: int, n: int):
+    """sli_kv_copy_prefix: K and V rows [0, n) of every layer and kv head from sequence ``src`` to sequence ``dst`` of
+    the caches kc / vc [L, B, hkv, T, hd] (contiguous device tensors of one dtype of 1, 2 or 4 bytes per element), in
+    place, one launch. Every other byte of both caches is untouched."""
+    if kc.shape != vc.shape or kc.dim() != 5 or kc.dtype != vc.dtype:
+        raise ValueError("kv_copy_prefix: kc and vc are [L, B, hkv, T, hd] tensors of one dtype")
+    if not (kc.is_cuda and vc.is_cuda and kc.is_contiguous() and vc.is_contiguous()):
+        raise ValueError("kv_copy_prefix: contiguous device tensors")
+    _dev(kc, vc)
+    L, B, hkv, T, hd = kc.shape
+    call("sli_kv_copy_prefix", _p(kc), _p(vc), kc.element_size(), L, B, hkv, T, hd, src, dst, n, _s())
+
+
 def _pf_groups(groups, M):
     """(seq, p0, nv) triples -> a host array of M / 16 sli_pf_group (short lists end in padding groups)."""
     gs = [tuple(int(v) for v in g) for g in groups]
