@@ -341,7 +341,9 @@ int sli_model_get_state_seq(sli_model* m, int32_t seq, int32_t* pos, int32_t* to
  * multi-process tensor parallelism every rank calls it, the chunk's residual rows all-reduced over RCCL
  * twice per layer), filling the K/V cache; the state is left at
  * (token ids[n-1], position n-1, advancing, prompt = ids), so the next sli_model_step yields the first
- * greedy token exactly as the reference's token-by-token predict (model.cpp:157-165) would. */
+ * greedy token exactly as the reference's token-by-token predict (model.cpp:157-165) would. A prompt is a
+ * continuation whose start is 0: behind its own argument checks this is sli_model_extend(m, ids, 0, n), on a
+ * fresh model and on one that holds another prompt and has stepped alike. */
 int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n);
 /* Which path sli_model_prefill takes for this model: 1 = chunked MFMA GEMMs (prefill.h), 0 = the decode step,
  * teacher-forced (fp32 weights, batch > 1, unsupported shapes, a TP rank without an RCCL communicator, or an FP8 K/V
@@ -397,7 +399,8 @@ int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, s
  * by sli_model_set_prefill, whose modes it ignores. SLI_ERR_STATE with the reason for fp32 weights, an fp32 cache,
  * tp_size > 1, ranks of an in-process group and unsupported shapes (no fallback). Argument errors are decided before
  * any state or device memory is touched: a duplicate or out-of-range sequence is SLI_ERR_ARG, a length outside
- * [1, min(ld, max_len)] or a token outside the vocabulary SLI_ERR_RANGE. */
+ * [1, min(ld, max_len)] or a token outside the vocabulary SLI_ERR_RANGE. Behind these checks the call is
+ * sli_model_extend_seqs with every start 0, counts = lens and advance 1: one host driver serves both. */
 int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
                            const int32_t* lens, int32_t ld);
 int sli_model_prefill_seqs_ok(const sli_model* m); /* 1: the model takes sli_model_prefill_seqs */
@@ -452,8 +455,9 @@ int sli_prefill_pack_from(const int32_t* seqs, const int32_t* starts, const int3
  * unlisted sequence's rows, state, prompt and history are untouched. advance == 1 leaves the sequences advancing, as
  * sli_model_prefill_seqs does; advance == 0 leaves them waiting (idempotent steps) while the rest of the batch steps: a
  * partly admitted prompt. A start below the position is a rollback: rows from the start on are overwritten as they are
- * recomputed, rows past the new end stay stale and are never read. On a fresh model a call with every start 0 is
- * sli_model_prefill_seqs bit for bit.
+ * recomputed, rows past the new end stay stale and are never read. sli_model_prefill_seqs is the case of every start 0
+ * (and sli_model_score_seqs that of sli_model_score_extend_seqs): the prompt calls run this call's driver behind their
+ * own checks, so a call with every start 0 leaves what they leave bit for bit.
  * The arguments are judged before any state or device memory is touched, each condition over every listed sequence
  * before the next: n_seqs outside [1, batch], a sequence out of range or listed twice: SLI_ERR_ARG; then SLI_ERR_RANGE
  * for counts[i] outside [1, ld]; starts[i] + counts[i] > max_len; a token outside the vocabulary; starts[i] outside

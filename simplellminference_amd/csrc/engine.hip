@@ -2104,6 +2104,30 @@ static int pf_enqueue(const PfPlan& pl, std::vector<PfSegs>& tabs, hipStream_t s
     }
     return SLI_OK;
 }
+// The two places a plan runs, each to the end of its chunks. A model: the plain chunk graphs, or with `score` the
+// scoring ones (record_score_segs), which have slots of their own.
+static int pf_run_model(sli_model* m, const PfPlan& pl, bool score) {
+    SLI_TRY(pf_alloc(m));
+    std::vector<PfSegs> tabs;
+    SLI_TRY(pf_enqueue(pl, tabs, m->stream, score ? m->pf.scgraph : m->pf.graph, score ? m->pf.scexec : m->pf.exec,
+                       {m->pf.segs}, [&](int M) {
+                           return score ? SLI_DISPATCH(m, record_score_segs, m, M) : SLI_DISPATCH(m, record_prefill, m, M);
+                       }));
+    return wait_stream(m);
+}
+// An in-process group: every rank's table, the group's graphs of the ranks' chunks in lockstep.
+static int pf_run_group(sli_tp_group* g, const PfPlan& pl) {
+    std::vector<PfSegs*> dev;
+    for (sli_model* m : g->ranks) {
+        SLI_TRY(pf_alloc(m));
+        dev.push_back(m->pf.segs);
+    }
+    std::vector<PfSegs> tabs;
+    SLI_TRY(pf_enqueue(pl, tabs, g->stream, g->pf_graph, g->pf_exec, dev,
+                       [&](int M) { return SLI_DISPATCH(g->ranks[0], record_group_prefill, g, M); }));
+    SLI_HIP(hipStreamSynchronize(g->stream));
+    return SLI_OK;
+}
 
 extern "C" int sli_model_prefill_path(const sli_model* m) { return m && m->B == 1 && pf_use_gemm(m) ? 1 : 0; }
 
@@ -2130,62 +2154,6 @@ extern "C" int sli_model_fused_qkv_attn(sli_model* m) {
     return done;
 }
 
-extern "C" int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n) {
-    SLI_CHECK(m && ids, SLI_ERR_ARG, "null argument");
-    SLI_CHECK(m->B == 1, SLI_ERR_STATE, "prefill: batch-1 models (a batch prefills through predict_batch)");
-    SLI_CHECK(!m->group, SLI_ERR_STATE, "prefill: ranks of an in-process group prefill through sli_tp_group_prefill");
-    SLI_CHECK(n >= 1 && n <= m->T, SLI_ERR_RANGE, "prompt length out of range");
-    for (int i = 0; i < n; ++i)
-        SLI_CHECK(ids[i] >= 0 && ids[i] < m->V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
-    SLI_HIP(hipSetDevice(m->c.device));
-    SLI_TRY(set_prompt(m, 0, ids, n));
-    SLI_HIP(hipMemcpyAsync(m->hist, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, m->stream));
-    if (n > 1 && pf_use_gemm(m)) {
-        SLI_TRY(pf_alloc(m));
-        const int32_t seq0 = 0;
-        std::vector<PfSegs> tabs;
-        SLI_TRY(pf_enqueue(pf_pack(&seq0, &n, 1), tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
-                           [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
-        SLI_TRY(wait_stream(m));
-    } else {
-        for (int p = 0; p < n - 1; ++p) {  // the decode step, teacher-forced (model.cpp:159-165)
-            SLI_TRY(set_state(m, 0, ids[p], p, 0));
-            SLI_TRY(sli_model_step(m));
-        }
-    }
-    // the last prompt position is an ordinary decode step: it yields the first greedy token
-    return set_state(m, 0, ids[n - 1], n - 1, 1);
-}
-
-extern "C" int sli_tp_group_prefill(sli_tp_group* g, const int32_t* ids, int32_t n) {
-    SLI_CHECK(g && ids, SLI_ERR_ARG, "null argument");
-    sli_model* m0 = g->ranks[0];
-    SLI_CHECK(m0->B == 1, SLI_ERR_STATE, "prefill: batch-1 groups (a batch prefills through predict_batch)");
-    SLI_CHECK(n >= 1 && n <= m0->T, SLI_ERR_RANGE, "prompt length out of range");
-    SLI_HIP(hipSetDevice(g->device));
-    for (sli_model* m : g->ranks) {
-        SLI_TRY(set_prompt(m, 0, ids, n));
-        SLI_HIP(hipMemcpyAsync(m->hist, ids, sizeof(int32_t) * n, hipMemcpyHostToDevice, m->stream));
-    }
-    if (n > 1 && pf_use_gemm(m0)) {
-        for (sli_model* m : g->ranks) SLI_TRY(pf_alloc(m));
-        const int32_t seq0 = 0;
-        std::vector<PfSegs> tabs;
-        std::vector<PfSegs*> dev;
-        for (sli_model* m : g->ranks) dev.push_back(m->pf.segs);
-        SLI_TRY(pf_enqueue(pf_pack(&seq0, &n, 1), tabs, g->stream, g->pf_graph, g->pf_exec, dev,
-                           [&](int M) { return SLI_DISPATCH(m0, record_group_prefill, g, M); }));
-        SLI_HIP(hipStreamSynchronize(g->stream));
-    } else {
-        for (int p = 0; p < n - 1; ++p) {
-            for (sli_model* m : g->ranks) SLI_TRY(set_state(m, 0, ids[p], p, 0));
-            SLI_TRY(sli_tp_group_step(g));
-        }
-    }
-    for (sli_model* m : g->ranks) SLI_TRY(set_state(m, 0, ids[n - 1], n - 1, 1));
-    return SLI_OK;
-}
-
 extern "C" int sli_model_predict_prefill(sli_model* m, const int32_t* prompt, int32_t n_prompt, int32_t max_length,
                                          int32_t* tokens_out, float* logits_out) {
     SLI_CHECK(m && prompt && tokens_out, SLI_ERR_ARG, "null argument");
@@ -2204,19 +2172,25 @@ extern "C" int sli_model_predict_prefill(sli_model* m, const int32_t* prompt, in
 }
 
 // ---------------------------------------------------------------- packed prefill of a batched model's sequences
+// a plan into the caller's buffers (the two planner entries, `name` the one that reports)
+static int pf_pack_out(const PfPlan& pl, const char* name, sli_pf_group* groups, int32_t cap_groups, int32_t* chunk_rows,
+                       int32_t cap_chunks, int32_t* n_chunks) {
+    SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
+              std::string(name) + ": the group or chunk buffer is too small");
+    std::copy(pl.groups.begin(), pl.groups.end(), groups);
+    std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
+    *n_chunks = (int32_t)pl.rows.size();
+    return SLI_OK;
+}
+
 extern "C" int sli_prefill_pack(const int32_t* seqs, const int32_t* lens, int32_t n_seqs, sli_pf_group* groups,
                                 int32_t cap_groups, int32_t* chunk_rows, int32_t cap_chunks, int32_t* n_chunks) {
     SLI_CHECK(seqs && lens && n_chunks && (groups || cap_groups == 0) && (chunk_rows || cap_chunks == 0), SLI_ERR_ARG,
               "sli_prefill_pack: null argument");
     SLI_CHECK(n_seqs >= 0 && cap_groups >= 0 && cap_chunks >= 0, SLI_ERR_ARG, "sli_prefill_pack: negative count");
     for (int i = 0; i < n_seqs; ++i) SLI_CHECK(lens[i] >= 1, SLI_ERR_RANGE, "sli_prefill_pack: a length below 1");
-    const PfPlan pl = pf_pack(seqs, lens, n_seqs);
-    SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
-              "sli_prefill_pack: the group or chunk buffer is too small");
-    std::copy(pl.groups.begin(), pl.groups.end(), groups);
-    std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
-    *n_chunks = (int32_t)pl.rows.size();
-    return SLI_OK;
+    return pf_pack_out(pf_pack(seqs, lens, n_seqs), "sli_prefill_pack", groups, cap_groups, chunk_rows, cap_chunks,
+                       n_chunks);
 }
 
 extern "C" int sli_prefill_pack_from(const int32_t* seqs, const int32_t* starts, const int32_t* counts, int32_t n_seqs,
@@ -2230,13 +2204,8 @@ extern "C" int sli_prefill_pack_from(const int32_t* seqs, const int32_t* starts,
         SLI_CHECK(starts[i] >= 0 && starts[i] <= (1 << 30) && counts[i] <= (1 << 30), SLI_ERR_RANGE,
                   "sli_prefill_pack_from: a start below 0, or a start or count above 2^30");
     }
-    const PfPlan pl = pf_pack_from(seqs, starts, counts, n_seqs);
-    SLI_CHECK((int64_t)pl.groups.size() <= cap_groups && (int64_t)pl.rows.size() <= cap_chunks, SLI_ERR_RANGE,
-              "sli_prefill_pack_from: the group or chunk buffer is too small");
-    std::copy(pl.groups.begin(), pl.groups.end(), groups);
-    std::copy(pl.rows.begin(), pl.rows.end(), chunk_rows);
-    *n_chunks = (int32_t)pl.rows.size();
-    return SLI_OK;
+    return pf_pack_out(pf_pack_from(seqs, starts, counts, n_seqs), "sli_prefill_pack_from", groups, cap_groups,
+                       chunk_rows, cap_chunks, n_chunks);
 }
 
 // Why this model cannot take sli_model_prefill_seqs (null: it can). Not bound by sli_model_set_prefill's modes: an FP8
@@ -2301,83 +2270,12 @@ static int score_alloc(sli_model* m) {
     return SLI_OK;
 }
 
-// sli_model_prefill_seqs, and with `score` sli_model_score_seqs: the same packing and launches, the scoring chunks
-// through graphs of their own (record_score_segs)
-struct PfScoreOut {
-    float* logprob;
-    int32_t* top;
-    float* top_logprob;
-};
-static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts, const int32_t* lens,
-                       int32_t ld, const PfScoreOut* score);
-
-extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
-                                      const int32_t* lens, int32_t ld) {
-    SLI_CHECK(m && seqs && prompts && lens, SLI_ERR_ARG, "null argument");
-    if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
-    return pf_seqs_run(m, seqs, n_seqs, prompts, lens, ld, nullptr);
-}
-
 extern "C" int sli_model_score_seqs_ok(const sli_model* m) { return m && !score_seqs_why(m) ? 1 : 0; }
 
-extern "C" int sli_model_score_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
-                                    const int32_t* lens, int32_t ld, float* logprob, int32_t* top, float* top_logprob) {
-    SLI_CHECK(m && seqs && prompts && lens && logprob, SLI_ERR_ARG, "null argument");
-    if (const char* why = score_seqs_why(m)) return fail(SLI_ERR_STATE, why);
-    const PfScoreOut out{logprob, top, top_logprob};
-    return pf_seqs_run(m, seqs, n_seqs, prompts, lens, ld, &out);
-}
-
-static int pf_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts, const int32_t* lens,
-                       int32_t ld, const PfScoreOut* score) {
-    // every argument is judged before any state or device memory is touched
-    SLI_TRY(pf_seqs_args(m->B, m->T, m->V, seqs, n_seqs, prompts, lens, ld));
-    SLI_HIP(hipSetDevice(m->c.device));
-    if (score) SLI_TRY(score_alloc(m));  // a failed allocation leaves the sequences as they were
-    for (int i = 0; i < n_seqs; ++i) {
-        const int32_t* ids = prompts + (size_t)i * ld;
-        SLI_TRY(set_prompt(m, seqs[i], ids, lens[i]));
-        SLI_HIP(hipMemcpyAsync(m->hist + (size_t)seqs[i] * (m->T + 1), ids, sizeof(int32_t) * lens[i],
-                               hipMemcpyHostToDevice, m->stream));
-    }
-    const PfPlan pl = pf_pack(seqs, lens, n_seqs);
-    if (!pl.rows.empty()) {
-        SLI_TRY(pf_alloc(m));
-        std::vector<PfSegs> tabs;
-        if (score)
-            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.scgraph, m->pf.scexec, {m->pf.segs},
-                               [&](int M) { return SLI_DISPATCH(m, record_score_segs, m, M); }));
-        else
-            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
-                               [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
-        SLI_TRY(wait_stream(m));
-    }
-    if (score) {  // entry (i, t), 1 <= t < lens[i]: slot (seqs[i], t) of the device buffers; everything else is empty
-        const size_t n = (size_t)n_seqs * ld;
-        std::fill_n(score->logprob, n, NAN);
-        if (score->top) std::fill_n(score->top, n, -1);
-        if (score->top_logprob) std::fill_n(score->top_logprob, n, NAN);
-        for (int i = 0; i < n_seqs; ++i) {
-            if (lens[i] < 2) continue;
-            const size_t src = (size_t)seqs[i] * (m->T + 1) + 1, dst = (size_t)i * ld + 1, cnt = (size_t)lens[i] - 1;
-            SLI_HIP(hipMemcpyAsync(score->logprob + dst, m->pf.sc_lp + src, sizeof(float) * cnt, hipMemcpyDeviceToHost,
-                                   m->stream));
-            if (score->top)
-                SLI_HIP(hipMemcpyAsync(score->top + dst, m->pf.sc_top + src, sizeof(int32_t) * cnt,
-                                       hipMemcpyDeviceToHost, m->stream));
-            if (score->top_logprob)
-                SLI_HIP(hipMemcpyAsync(score->top_logprob + dst, m->pf.sc_tlp + src, sizeof(float) * cnt,
-                                       hipMemcpyDeviceToHost, m->stream));
-        }
-        SLI_TRY(wait_stream(m));
-    }
-    // each sequence's last prompt position is an ordinary decode step
-    for (int i = 0; i < n_seqs; ++i)
-        SLI_TRY(set_state(m, seqs[i], prompts[(size_t)i * ld + lens[i] - 1], lens[i] - 1, 1));
-    return SLI_OK;
-}
-
 // ---------------------------------------------------------------- continuing sequences from a start position
+// A prompt is a continuation whose start is 0: the prompt entries (sli_model_prefill_seqs, sli_model_score_seqs,
+// sli_model_prefill, sli_tp_group_prefill) keep their own argument checks and run the drivers below from start 0.
+//
 // The argument checks of the extend calls for a model of batch B, max_len T and vocabulary V whose sequences stand at
 // pos[0 .. B), in their one order (sli.h at sli_model_extend_seqs): each condition over every listed sequence before the
 // next condition. starts == nullptr: each sequence's own position. Host only.
@@ -2420,53 +2318,48 @@ static int ext_put_tokens(sli_model* m, int seq, const int32_t* ids, int start, 
     return SLI_OK;
 }
 
-// what an extend leaves of the listed sequences' states (h: the states as downloaded before the call)
+// a sequence left at `token` and position pos, its first n_forced positions forced, with no sampling key and no error
+static void put_state(DevState& d, int32_t token, int32_t pos, int32_t n_forced, int advance) {
+    d.token = token;
+    d.pos = pos;
+    d.n_forced = n_forced;
+    d.advance = advance ? 1 : 0;
+    d.key = 0;
+    d.error = 0;
+}
+
+// what a continuation leaves of the listed sequences' states (h: the states as downloaded before the call)
 static int ext_put_states(sli_model* m, std::vector<DevState>& h, const int32_t* seqs, int n_seqs, const int32_t* tokens,
                           const int32_t* starts, const int32_t* counts, int ld, int advance) {
-    for (int i = 0; i < n_seqs; ++i) {
-        DevState& d = h[seqs[i]];
-        d.token = tokens[(size_t)i * ld + counts[i] - 1];
-        d.pos = starts[i] + counts[i] - 1;
-        d.n_forced = starts[i] + counts[i];
-        d.advance = advance ? 1 : 0;
-        d.key = 0;
-        d.error = 0;
-    }
+    for (int i = 0; i < n_seqs; ++i)
+        put_state(h[seqs[i]], tokens[(size_t)i * ld + counts[i] - 1], starts[i] + counts[i] - 1, starts[i] + counts[i],
+                  advance);
     return upload_states(m, h);
 }
 
-static int ext_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens, const int32_t* starts,
-                        const int32_t* counts, int32_t ld, int32_t advance, const PfScoreOut* score) {
-    SLI_HIP(hipSetDevice(m->c.device));
-    std::vector<DevState> h;
-    SLI_TRY(download_states(m, h));  // a read: every argument is judged before any state or device memory is touched
-    std::vector<int32_t> pos(m->B);
-    for (int b = 0; b < m->B; ++b) pos[b] = h[b].pos;
-    SLI_TRY(ext_args(m->B, m->T, m->V, pos.data(), seqs, n_seqs, tokens, starts, counts, ld));
-    std::vector<int32_t> st(n_seqs);
-    for (int i = 0; i < n_seqs; ++i) st[i] = starts ? starts[i] : pos[seqs[i]];
+// The packed driver (batched models), behind the entries' checks: nothing above this line has written to a state, the
+// prompt, the history or the cache. Sequence seqs[i] takes tokens[i * ld + j] at position starts[i] + j; h holds the
+// states as read before the call. With `score` the chunks are the scoring ones and entry (i, j), 1 <= j < counts[i],
+// is read back from slot (seqs[i], starts[i] + j) of the device buffers; everything else is empty.
+struct PfScoreOut {
+    float* logprob;
+    int32_t* top;
+    float* top_logprob;
+};
+static int ext_seqs(sli_model* m, std::vector<DevState>& h, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
+                    const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance, const PfScoreOut* score) {
     if (score) SLI_TRY(score_alloc(m));  // a failed allocation leaves the sequences as they were
-    for (int i = 0; i < n_seqs; ++i) SLI_TRY(ext_put_tokens(m, seqs[i], tokens + (size_t)i * ld, st[i], counts[i]));
-    const PfPlan pl = pf_pack_from(seqs, st.data(), counts, n_seqs);
-    if (!pl.rows.empty()) {
-        SLI_TRY(pf_alloc(m));
-        std::vector<PfSegs> tabs;
-        if (score)
-            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.scgraph, m->pf.scexec, {m->pf.segs},
-                               [&](int M) { return SLI_DISPATCH(m, record_score_segs, m, M); }));
-        else
-            SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
-                               [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
-        SLI_TRY(wait_stream(m));
-    }
-    if (score) {  // entry (i, j), 1 <= j < counts[i]: slot (seqs[i], start + j) of the device buffers
+    for (int i = 0; i < n_seqs; ++i) SLI_TRY(ext_put_tokens(m, seqs[i], tokens + (size_t)i * ld, starts[i], counts[i]));
+    const PfPlan pl = pf_pack_from(seqs, starts, counts, n_seqs);
+    if (!pl.rows.empty()) SLI_TRY(pf_run_model(m, pl, score != nullptr));
+    if (score) {
         const size_t n = (size_t)n_seqs * ld;
         std::fill_n(score->logprob, n, NAN);
         if (score->top) std::fill_n(score->top, n, -1);
         if (score->top_logprob) std::fill_n(score->top_logprob, n, NAN);
         for (int i = 0; i < n_seqs; ++i) {
             if (counts[i] < 2) continue;
-            const size_t src = (size_t)seqs[i] * (m->T + 1) + st[i] + 1, dst = (size_t)i * ld + 1;
+            const size_t src = (size_t)seqs[i] * (m->T + 1) + starts[i] + 1, dst = (size_t)i * ld + 1;
             const size_t cnt = (size_t)counts[i] - 1;
             SLI_HIP(hipMemcpyAsync(score->logprob + dst, m->pf.sc_lp + src, sizeof(float) * cnt, hipMemcpyDeviceToHost,
                                    m->stream));
@@ -2480,14 +2373,57 @@ static int ext_seqs_run(sli_model* m, const int32_t* seqs, int32_t n_seqs, const
         SLI_TRY(wait_stream(m));
     }
     // each sequence's last token is an ordinary decode step (or waits: advance == 0)
-    return ext_put_states(m, h, seqs, n_seqs, tokens, st.data(), counts, ld, advance);
+    return ext_put_states(m, h, seqs, n_seqs, tokens, starts, counts, ld, advance);
+}
+
+// sli_model_prefill_seqs, and with `score` sli_model_score_seqs, behind their null checks: pf_seqs_args, then the
+// driver with every start 0, the lengths as counts, advancing
+static int prompt_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts, const int32_t* lens,
+                       int32_t ld, const PfScoreOut* score) {
+    SLI_TRY(pf_seqs_args(m->B, m->T, m->V, seqs, n_seqs, prompts, lens, ld));
+    SLI_HIP(hipSetDevice(m->c.device));
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m, h));
+    const std::vector<int32_t> starts(n_seqs, 0);
+    return ext_seqs(m, h, seqs, n_seqs, prompts, starts.data(), lens, ld, 1, score);
+}
+
+extern "C" int sli_model_prefill_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                                      const int32_t* lens, int32_t ld) {
+    SLI_CHECK(m && seqs && prompts && lens, SLI_ERR_ARG, "null argument");
+    if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    return prompt_seqs(m, seqs, n_seqs, prompts, lens, ld, nullptr);
+}
+
+extern "C" int sli_model_score_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* prompts,
+                                    const int32_t* lens, int32_t ld, float* logprob, int32_t* top, float* top_logprob) {
+    SLI_CHECK(m && seqs && prompts && lens && logprob, SLI_ERR_ARG, "null argument");
+    if (const char* why = score_seqs_why(m)) return fail(SLI_ERR_STATE, why);
+    const PfScoreOut out{logprob, top, top_logprob};
+    return prompt_seqs(m, seqs, n_seqs, prompts, lens, ld, &out);
+}
+
+// sli_model_extend_seqs, and with `score` sli_model_score_extend_seqs, behind their null checks: ext_args over the
+// positions read from the device (a read: every argument is judged before anything is written), then the driver from
+// the starts given or, starts == nullptr, each sequence's own position
+static int continue_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens, const int32_t* starts,
+                         const int32_t* counts, int32_t ld, int32_t advance, const PfScoreOut* score) {
+    SLI_HIP(hipSetDevice(m->c.device));
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m, h));
+    std::vector<int32_t> pos(m->B);
+    for (int b = 0; b < m->B; ++b) pos[b] = h[b].pos;
+    SLI_TRY(ext_args(m->B, m->T, m->V, pos.data(), seqs, n_seqs, tokens, starts, counts, ld));
+    std::vector<int32_t> st(n_seqs);
+    for (int i = 0; i < n_seqs; ++i) st[i] = starts ? starts[i] : pos[seqs[i]];
+    return ext_seqs(m, h, seqs, n_seqs, tokens, st.data(), counts, ld, advance, score);
 }
 
 extern "C" int sli_model_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
                                      const int32_t* starts, const int32_t* counts, int32_t ld, int32_t advance) {
     SLI_CHECK(m && seqs && tokens && counts, SLI_ERR_ARG, "null argument");
     if (const char* why = pf_seqs_why(m)) return fail(SLI_ERR_STATE, why);
-    return ext_seqs_run(m, seqs, n_seqs, tokens, starts, counts, ld, advance, nullptr);
+    return continue_seqs(m, seqs, n_seqs, tokens, starts, counts, ld, advance, nullptr);
 }
 
 extern "C" int sli_model_score_extend_seqs(sli_model* m, const int32_t* seqs, int32_t n_seqs, const int32_t* tokens,
@@ -2496,40 +2432,80 @@ extern "C" int sli_model_score_extend_seqs(sli_model* m, const int32_t* seqs, in
     SLI_CHECK(m && seqs && tokens && counts && logprob, SLI_ERR_ARG, "null argument");
     if (const char* why = score_seqs_why(m)) return fail(SLI_ERR_STATE, why);
     const PfScoreOut out{logprob, top, top_logprob};
-    return ext_seqs_run(m, seqs, n_seqs, tokens, starts, counts, ld, advance, &out);
+    return continue_seqs(m, seqs, n_seqs, tokens, starts, counts, ld, advance, &out);
 }
 
-// The one-sequence routes (batch-1 models and groups): ranks = the model, or every rank of the group; step() one decode
-// step of them; enqueue(plan, tabs) the GEMM chunks of a plan and the wait for them. start == -1: the current position.
-template <class Step, class Enqueue>
+// The one-sequence driver (batch-1 models and groups), behind the entries' checks: ranks = the model, or every rank of
+// the group; step() one decode step of them; run(plan) the GEMM chunks of a plan to their end (pf_run_model,
+// pf_run_group). tokens[j] goes to position start + j: through the GEMM chunks where pf_use_gemm says so, otherwise
+// teacher-forced through the decode step (model.cpp:159-165), which gives the same tokens. The last token is left as an
+// ordinary decode step: after a prompt it yields the first greedy token.
+template <class Step, class Run>
 static int ext_one(const std::vector<sli_model*>& ranks, const int32_t* tokens, int32_t start, int32_t count, Step step,
-                   Enqueue enqueue) {
+                   Run run) {
     sli_model* m0 = ranks[0];
-    std::vector<DevState> h0;
-    SLI_TRY(download_states(m0, h0));
-    const int32_t seq0 = 0, pos0 = h0[0].pos;
-    const int32_t s = start == -1 ? pos0 : start;
-    SLI_TRY(ext_args(1, m0->T, m0->V, &pos0, &seq0, 1, tokens, &s, &count, std::max(count, 1)));
-    for (sli_model* m : ranks) SLI_TRY(ext_put_tokens(m, 0, tokens, s, count));
+    const int32_t seq0 = 0;
+    for (sli_model* m : ranks) SLI_TRY(ext_put_tokens(m, 0, tokens, start, count));
     // an fp32 cache continues through the decode step: pf_attn_kernel's 64-row blocks are consecutive positions from
     // their first group's p0, which a partial first group is not
-    const bool gemm = count > 1 && pf_use_gemm(m0) && (s == 0 || m0->c.kv_dtype != SLI_DT_F32);
-    if (gemm) {
-        for (sli_model* m : ranks) SLI_TRY(pf_alloc(m));
-        std::vector<PfSegs> tabs;
-        SLI_TRY(enqueue(pf_pack_from(&seq0, &s, &count, 1), tabs));
+    if (count > 1 && pf_use_gemm(m0) && (start == 0 || m0->c.kv_dtype != SLI_DT_F32)) {
+        SLI_TRY(run(pf_pack_from(&seq0, &start, &count, 1)));
     } else {
-        for (int j = 0; j < count - 1; ++j) {  // the decode step, teacher-forced
-            for (sli_model* m : ranks) SLI_TRY(set_state(m, 0, tokens[j], s + j, 0));
+        for (int j = 0; j < count - 1; ++j) {
+            for (sli_model* m : ranks) SLI_TRY(set_state(m, 0, tokens[j], start + j, 0));
             SLI_TRY(step());
         }
     }
     for (sli_model* m : ranks) {
         std::vector<DevState> h;
         SLI_TRY(download_states(m, h));
-        SLI_TRY(ext_put_states(m, h, &seq0, 1, tokens, &s, &count, count, 1));
+        SLI_TRY(ext_put_states(m, h, &seq0, 1, tokens, &start, &count, count, 1));
     }
     return SLI_OK;
+}
+
+// the prompt entries' checks of n and the tokens, for a model of max_len T and vocabulary V
+static int prompt_args(int T, int V, const int32_t* ids, int32_t n) {
+    SLI_CHECK(n >= 1 && n <= T, SLI_ERR_RANGE, "prompt length out of range");
+    for (int i = 0; i < n; ++i)
+        SLI_CHECK(ids[i] >= 0 && ids[i] < V, SLI_ERR_RANGE, "Token index is greater than vocab size.");
+    return SLI_OK;
+}
+// the extend entries': ext_args for the one sequence 0, and the start they resolve (-1: the current position)
+static int ext_one_args(sli_model* m0, const int32_t* tokens, int32_t* start, int32_t count) {
+    std::vector<DevState> h;
+    SLI_TRY(download_states(m0, h));
+    const int32_t seq0 = 0, pos0 = h[0].pos;
+    if (*start == -1) *start = pos0;
+    return ext_args(1, m0->T, m0->V, &pos0, &seq0, 1, tokens, start, &count, std::max(count, 1));
+}
+
+static int one_model(sli_model* m, const int32_t* tokens, int32_t start, int32_t count) {
+    return ext_one({m}, tokens, start, count, [&] { return sli_model_step(m); },
+                   [&](const PfPlan& pl) { return pf_run_model(m, pl, false); });
+}
+static int one_group(sli_tp_group* g, const int32_t* tokens, int32_t start, int32_t count) {
+    return ext_one(g->ranks, tokens, start, count, [&] { return sli_tp_group_step(g); },
+                   [&](const PfPlan& pl) { return pf_run_group(g, pl); });
+}
+
+extern "C" int sli_model_prefill(sli_model* m, const int32_t* ids, int32_t n) {
+    SLI_CHECK(m && ids, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(m->B == 1, SLI_ERR_STATE, "prefill: batch-1 models (a batch prefills through predict_batch)");
+    SLI_CHECK(!m->group, SLI_ERR_STATE, "prefill: ranks of an in-process group prefill through sli_tp_group_prefill");
+    SLI_TRY(prompt_args(m->T, m->V, ids, n));
+    SLI_CHECK(!m->comm_dead, SLI_ERR_COMM, "the RCCL communicator was aborted by an earlier bounded wait");
+    SLI_HIP(hipSetDevice(m->c.device));
+    return one_model(m, ids, 0, n);
+}
+
+extern "C" int sli_tp_group_prefill(sli_tp_group* g, const int32_t* ids, int32_t n) {
+    SLI_CHECK(g && ids, SLI_ERR_ARG, "null argument");
+    sli_model* m0 = g->ranks[0];
+    SLI_CHECK(m0->B == 1, SLI_ERR_STATE, "prefill: batch-1 groups (a batch prefills through predict_batch)");
+    SLI_TRY(prompt_args(m0->T, m0->V, ids, n));
+    SLI_HIP(hipSetDevice(g->device));
+    return one_group(g, ids, 0, n);
 }
 
 extern "C" int sli_model_extend(sli_model* m, const int32_t* tokens, int32_t start, int32_t count) {
@@ -2538,12 +2514,8 @@ extern "C" int sli_model_extend(sli_model* m, const int32_t* tokens, int32_t sta
     SLI_CHECK(!m->group, SLI_ERR_STATE, "extend: ranks of an in-process group extend through sli_tp_group_extend");
     SLI_CHECK(!m->comm_dead, SLI_ERR_COMM, "the RCCL communicator was aborted by an earlier bounded wait");
     SLI_HIP(hipSetDevice(m->c.device));
-    return ext_one({m}, tokens, start, count, [&] { return sli_model_step(m); },
-                   [&](const PfPlan& pl, std::vector<PfSegs>& tabs) -> int {
-                       SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph, m->pf.exec, {m->pf.segs},
-                                          [&](int M) { return SLI_DISPATCH(m, record_prefill, m, M); }));
-                       return wait_stream(m);
-                   });
+    SLI_TRY(ext_one_args(m, tokens, &start, count));
+    return one_model(m, tokens, start, count);
 }
 
 extern "C" int sli_tp_group_extend(sli_tp_group* g, const int32_t* tokens, int32_t start, int32_t count) {
@@ -2551,15 +2523,8 @@ extern "C" int sli_tp_group_extend(sli_tp_group* g, const int32_t* tokens, int32
     sli_model* m0 = g->ranks[0];
     SLI_CHECK(m0->B == 1, SLI_ERR_STATE, "extend: batch-1 groups");
     SLI_HIP(hipSetDevice(g->device));
-    return ext_one(g->ranks, tokens, start, count, [&] { return sli_tp_group_step(g); },
-                   [&](const PfPlan& pl, std::vector<PfSegs>& tabs) -> int {
-                       std::vector<PfSegs*> dev;
-                       for (sli_model* m : g->ranks) dev.push_back(m->pf.segs);
-                       SLI_TRY(pf_enqueue(pl, tabs, g->stream, g->pf_graph, g->pf_exec, dev,
-                                          [&](int M) { return SLI_DISPATCH(m0, record_group_prefill, g, M); }));
-                       SLI_HIP(hipStreamSynchronize(g->stream));
-                       return SLI_OK;
-                   });
+    SLI_TRY(ext_one_args(m0, tokens, &start, count));
+    return one_group(g, tokens, start, count);
 }
 
 // ---------------------------------------------------------------- prefix copy between sequences (kv_copy.h)
@@ -2571,13 +2536,7 @@ static int copy_prefix_rank(sli_model* m, int src, int dst, int n, int32_t tok) 
                            m->stream));
     std::vector<DevState> h;
     SLI_TRY(download_states(m, h));
-    DevState& d = h[dst];
-    d.token = tok;
-    d.pos = n;
-    d.n_forced = n + 1;
-    d.advance = 0;
-    d.key = 0;
-    d.error = 0;
+    put_state(h[dst], tok, n, n + 1, 0);
     return upload_states(m, h);
 }
 

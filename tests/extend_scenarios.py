@@ -17,9 +17,10 @@ import numpy as np
 LENS = (1, 2, 17, 40)
 # scenario -> weight seed, from the scan above. Its minimum top-2 gap over the compared positions (and seed 0's):
 #   turn 3.0e-3 (1.9e-4); turn-i8 2.9e-3 (3.9e-4); rollback 1.2e-2 (3.1e-3); admit 7.3e-3 (6.4e-3); one 5.9e-3 (5.6e-4);
-#   one-f32kv 5.9e-3 (4.8e-4); one-tp 1.9e-2 (3.1e-3); edge 2.2e-2 (seed 0 itself); fork 1.1e-2 (2.6e-5)
+#   one-f32kv 5.9e-3 (4.8e-4); one-tp 1.9e-2 (3.1e-3); edge 2.2e-2 (seed 0 itself); fork 1.1e-2 (2.6e-5);
+#   again 3.5e-2 (1.0e-2); again-f32kv 3.5e-2 (1.0e-2); again-tp 5.3e-2 (3.2e-2)
 SEEDS = {"turn": 21, "turn-i8": 17, "rollback": 15, "admit": 15, "one": 17, "one-f32kv": 17, "one-tp": 17, "edge": 0,
-         "fork": 20}
+         "fork": 20, "again": 10, "again-f32kv": 10, "again-tp": 21}
 
 
 def ocfg(oracle, cfg):
@@ -89,6 +90,15 @@ def fork(oracle, cfg, seed, **kw):
     return [p, p[:21] + prompt(7, cfg.vocab_size, seed=99)], [29, 20]
 
 
+AGAIN = ((40, 46), (9, 15))  # (prompt length, predict length) of the two calls
+
+
+def again(oracle, cfg, seed, **kw):
+    """A 40-token prompt predicted to 46, then on the same model a 9-token prompt predicted to 15: two independent
+    oracle runs, each compared from its last prompt position on."""
+    return [prompt(n, cfg.vocab_size) for n, _ in AGAIN], [n - 1 for n, _ in AGAIN]
+
+
 def min_gap(oracle, cfg, lists, first, steps, seed, **kw):
     from tests.score_ref import top2_gap
     g = np.inf
@@ -115,6 +125,9 @@ def scenarios(oracle):
         "one-tp": (h8, one, 64, {}),
         "edge": (g40, edge, 40, {}),
         "fork": (g, fork, 64, {}),
+        "again": (g, again, dict(AGAIN), {}),
+        "again-f32kv": (g, again, dict(AGAIN), dict(kv_f16=False)),
+        "again-tp": (h8, again, dict(AGAIN), {}),
     }
 
 

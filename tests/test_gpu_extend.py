@@ -1,5 +1,6 @@
 """Continuing sequences from a start position (sli_model_extend_seqs, sli_model_score_extend_seqs, sli_model_extend,
-sli_tp_group_extend; LlamaModel.extend / append / score_extend / admit, TPGroup.extend).
+sli_tp_group_extend; LlamaModel.extend / append / score_extend / admit, TPGroup.extend), and the prompt calls as the
+start-0 case of them.
 
 Bars: the project's own, from tests/test_gpu_batch_prefill.py and tests/test_gpu_score.py: against the oracle's predict
 over each sequence's full forced list greedy tokens bit-equal, logits of every compared position within 1e-3, the K/V
@@ -12,7 +13,8 @@ The scenarios and their weight seeds come from tests/extend_scenarios.py (the or
 tests.extend_scenarios` prints the scan). Minimum top-2 gap over the compared positions at the recorded seeds: turn 21:
 3.0e-3 (seed 0: 1.9e-4); turn, int8: 17: 2.9e-3; rollback 15: 1.2e-2 (sequence 2 from its first decoded position
 on); admit 15: 7.3e-3; one-sequence routes 17: 5.9e-3 (fp32 cache 5.9e-3, tiny-h8 1.9e-2); the position edge 0:
-2.2e-2. So the oracle alone leaves nothing out.
+2.2e-2; a shorter prompt after a longer one 10: 3.5e-2 (fp32 cache 3.5e-2; tiny-h8 21: 5.3e-2). So the oracle alone
+leaves nothing out.
 """
 import ctypes
 
@@ -480,3 +482,76 @@ def test_refusals_leave_every_state_as_it_was(gpu):
             fn([[1, 2, 3]], seqs=[0], starts=[0])
         assert e.value.code == 7 and "group" in str(e.value), e.value
     g.close()
+
+
+# ---------------------------------------------------------------- 11. a prompt is a continuation from 0
+def _one_sequence_engine(route, seed):
+    """A fresh batch-1 engine on `route`: (engine, its rank models, its one-sequence extend, the oracle's keywords)."""
+    from simplellminference_amd.model import LlamaModel, TPGroup, preset
+    if route == "tp2":
+        g = TPGroup(preset("tiny-h8"), 2, w_dtype="f16", kv_dtype="f16", seed=seed).init()
+        assert g.prefill_path() == "mfma"
+        return g, g.ranks, g.extend, {}
+    kv = "f32" if route == "f32kv" else "f16"
+    gm = LlamaModel(config=preset("tiny-gqa"), w_dtype="f16", kv_dtype=kv, seed=seed).init()
+    if route != "f32kv":
+        gm.set_prefill(route)
+    assert gm.prefill_path() == ("decode" if route == "decode" else "mfma")
+    return gm, [gm], gm.extend_one, dict(kv_f16=False) if route == "f32kv" else {}
+
+
+@pytest.mark.parametrize("route", ["gemm", "decode", "f32kv", "tp2"])
+def test_prefill_is_extend_from_zero_on_the_one_sequence_routes(gpu, route):
+    """37 tokens: positions 0 .. 35 are prefilled, two full groups and a partial one in the 64-row bucket. prefill()
+    against the one-sequence extend from start 0 on two fresh engines, then one step of each: per rank the state behind
+    the call and, behind the step, K/V rows [0, 37), the state, history [0, 38) and the logits are array_equal."""
+    out = []
+    for call in ("prefill", "extend"):
+        gm, ranks, extend, _ = _one_sequence_engine(route, 16)
+        p = S.prompt(37, gm.config.vocab_size)
+        if call == "prefill":
+            gm.prefill(p)
+        else:
+            extend(p, start=0)
+        left = [m.state() for m in ranks]
+        assert all((st["pos"], st["token"], st["error"]) == (36, p[36], 0) for st in left)
+        gm.step()
+        gm.sync()
+        layers = range(gm.config.num_hidden_layers)
+        out.append([(left[r], [m.kv(layer, which, 37) for layer in layers for which in (0, 1)], m.state(),
+                     m.history(0, 38), m.logits()[0].copy()) for r, m in enumerate(ranks)])
+        gm.close()
+    for r, (a, b) in enumerate(zip(*out)):
+        assert a[0] == b[0] and a[2] == b[2], (route, r, a[0], b[0], a[2], b[2])
+        assert all(np.array_equal(x, y) for x, y in zip(a[1], b[1])), (route, r)
+        assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]), (route, r)
+        assert a[2]["pos"] == 37
+
+
+@pytest.mark.parametrize("route", ["decode", "f32kv", "tp2"])
+def test_shorter_prompt_after_a_longer_one_without_reset(gpu, oracle, route):
+    """predict_prefill of a 40-token prompt to 46, then on the same engine of a 9-token prompt to 15 (nothing reset in
+    between: the first call's longer forced prefix, its advancing state and its rows 8 .. 45 are still there): each
+    call's tokens equal the oracle's predict, its logits from the last prompt position on are within the bar, and the
+    engine stands where a fresh one stands after the second call alone. (The GEMM route of a single model:
+    tests/test_gpu_prefill.py::test_prefill_twice_reuses_graphs.)"""
+    seed = S.SEEDS[{"decode": "again", "f32kv": "again-f32kv", "tp2": "again-tp"}[route]]
+    gm, ranks, _, okw = _one_sequence_engine(route, seed)
+    cfg = gm.config
+    for n, upto in S.AGAIN:
+        p = S.prompt(n, cfg.vocab_size)
+        toks, logits = gm.predict_prefill(p, upto, want_logits=True)
+        otok, olog, _ = S.run(oracle, cfg, p, upto, seed, **okw)
+        assert np.array_equal(toks, otok), (route, n, toks, otok)
+        assert np.isnan(logits[:n - 1]).all()
+        err = float(np.abs(logits[n - 1:] - olog[n - 1:]).max())
+        print(f"{route}, prompt of {n} to {upto}: max|dlogit| {err:.3e}")
+        assert err <= LOGIT, (route, n, err)
+    fresh, franks, _, _ = _one_sequence_engine(route, seed)
+    n, upto = S.AGAIN[1]
+    ftoks = fresh.predict_prefill(S.prompt(n, cfg.vocab_size), upto)
+    assert np.array_equal(toks, ftoks)
+    for m, f in zip(ranks, franks):
+        assert m.state()["error"] == 0 and m.state()["pos"] == f.state()["pos"] == upto, (m.state(), f.state())
+    gm.close()
+    fresh.close()
