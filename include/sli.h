@@ -227,6 +227,48 @@ enum { SLI_SAMPLE_STREAM = 12 }; /* the draw's stream kind, after sli_synth.h's 
 int sli_sample(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_sampling* p,
                int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, int32_t* out_dev, sli_stream_t stream);
 
+/* Per-row generation parameters (no reference counterpart): sli_sample's rule with a block of its own per row, token
+ * penalties before it and min-p after it. The rule, for one row of fp32 logits l[0..V), a block P, a history h (the
+ * sequence's tokens by position) and a position pos:
+ *  - Penalties. Active iff repetition_penalty != 1 or presence_penalty != 0 or frequency_penalty != 0. n_i = #{j :
+ *    penalty_from <= j <= pos, h[j] == i}; a history entry outside [0, V) is not counted, and no address is ever formed
+ *    from it; penalty_from > pos counts nothing. For n_i > 0: a = l_i > 0 ? l_i / repetition_penalty : l_i *
+ *    repetition_penalty; b = a - presence_penalty; l'_i = b - frequency_penalty * (float)n_i, each operation one IEEE
+ *    fp32 operation rounded to nearest, with no contraction. For n_i == 0, l'_i is l_i bit for bit. Inactive: l' = l
+ *    and the history is not read. A NaN stays NaN; +-inf follow IEEE.
+ *  - Greedy row. temperature == 0: the token is sli_argmax's answer for l' (first maximum, its NaN and +-0 semantics),
+ *    and nothing below applies.
+ *  - Sampled row. sli_sample's rule, word for word, on l' with (temperature, top_k, top_p, seed), the sequence id and
+ *    pos gives the candidate set C; a row with no finite maximum gives sli_argmax(l'). Then min-p: min_p == 0 is off;
+ *    otherwise c = (float)log((double)min_p), computed on the host, m' is the maximum of l' and C_m = {i : (l'_i - m')
+ *    / T >= c} with an IEEE fp32 subtract and divide. The Gumbel-max draw runs over the intersection of C and C_m,
+ *    which is never empty: the maximum is in both. With every new field neutral the token is bit-identical to
+ *    sli_sample's.
+ * Ranges (anything else, a NaN included, is SLI_ERR_ARG before the device is touched): temperature 0 or in [1e-2,
+ * 1e2]; top_k >= 0; top_p in (0, 1]; min_p in [0, 1); repetition_penalty in [0.1, 10]; presence_penalty and
+ * frequency_penalty in [-100, 100]; penalty_from >= 0; n_stop in [0, 8]; max_pos >= 0. */
+enum { SLI_MAX_STOP = 8 };
+typedef struct {
+    float temperature; int32_t top_k; float top_p; uint32_t seed;         /* sli_sampling's four; temperature 0: greedy */
+    float min_p, repetition_penalty, presence_penalty, frequency_penalty; /* 0, 1, 0, 0: off */
+    int32_t penalty_from;                                                 /* first history position counted */
+    int32_t max_pos;                                                      /* 0: none (model level only) */
+    int32_t n_stop; int32_t stop[SLI_MAX_STOP];                           /* model level only */
+} sli_gen_params;
+
+/* sli_sample with a host array of `rows` blocks, one per row, and the rows' histories: row r reads hist_dev + r *
+ * hist_stride (int32 tokens by position, hist_stride elements: a position at or past hist_stride is not read).
+ * hist_dev may be NULL iff no row has an active penalty, otherwise SLI_ERR_ARG; hist_stride >= 1 then. stop and
+ * max_pos are ignored here. out_dev[r] is -1 for a row with temperature 0 and no active penalty: such a row needs
+ * nothing from the sampler (its token is sli_argmax's), and its workgroup leaves at once. One workgroup per row, so a
+ * row's token does not depend on the other rows of the call, and it is bitwise reproducible: every sum is an integer
+ * (csrc/gen_sample.h). Rows without an active penalty never touch the history. Graph-capturable like sli_sample;
+ * the blocks are read during the call. Capacity (SLI_ERR_SHAPE beyond it, with the numbers; only where a row is
+ * penalised): vocab <= 262144 and hist_stride <= 4097, the workgroup's LDS bitmap and count table. */
+int sli_sample_gen(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_gen_params* p,
+                   int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, const int32_t* hist_dev,
+                   int64_t hist_stride, int32_t* out_dev, sli_stream_t stream);
+
 /* Scoring (no reference counterpart). The rule, for one row of V fp32 logits l and a target t:
  *   lse = M + log(sum_j exp(l_j - M)) with M = max_j l_j;  logprob = l_t - lse;
  *   top = the first index of the maximum in sli_argmax's order (-0 equals +0; a NaN never displaces the best so far,
@@ -523,6 +565,33 @@ int sli_model_set_sampling(sli_model* m, const sli_sampling* p);
 int sli_model_get_sampling(sli_model* m, sli_sampling* out);
 int sli_model_get_sampled(sli_model* m, int32_t seq, int32_t* token);
 int sli_model_graph_captures(sli_model* m, int32_t* n);
+/* Per-sequence generation inside the step (the rule at sli_sample_gen). sli_model_set_gen_seq gives sequence `seq` a
+ * block of its own; p == NULL returns it to the default: greedy, no penalties, no stop. The first call puts the model
+ * into per-sequence mode, which drops the step graph as turning sampling on does; from then on a change of any block
+ * re-captures nothing (the table lives in device memory). The per-sequence step is: LM head, the per-row sampler over
+ * the model's own history (csrc/gen_sample.h), key reduce, the sampled state update, then the stop launch.
+ * last_argmax stays the greedy argmax of the raw logits, sli_model_get_logits stays raw, sli_model_get_sampled
+ * reports the row's token. Any call of sli_model_set_sampling (NULL included) leaves the mode: it clears every block
+ * and restores that call's behaviour and graphs, node for node.
+ * The stop rule runs after the state update, one thread per sequence, and looks only at a sequence that is advancing
+ * and has just moved to a position p >= n_forced (its token at p was chosen, not forced): that token in stop[0 ..
+ * n_stop) gives SLI_FIN_STOP; else (max_pos > 0 and p >= max_pos) or p == max_len - 1 gives SLI_FIN_LENGTH. A finished
+ * sequence gets advance = 0: it is parked at (token, p), the token stays in the history, and its later steps are
+ * idempotent. A waiting sequence is never examined. A host call that writes a sequence's state clears its flag:
+ * sli_model_set_state(_seq), the prefill / extend / score routes, sli_model_copy_prefix's destination,
+ * sli_model_reset, and sli_model_set_gen_seq for that sequence.
+ * Beyond sli_sample_gen's ranges (SLI_ERR_ARG), SLI_ERR_RANGE before anything is written for seq outside [0, batch),
+ * a stop[i] outside [0, vocab) or max_pos > max_len - 1; SLI_ERR_SHAPE for a block with an active penalty on a model
+ * beyond the penalised sampler's capacity (vocab > 262144 or max_len > 4096: such a model takes every other block,
+ * stop conditions included); SLI_ERR_STATE with the reason as sli_model_set_sampling refuses: tp_size > 1,
+ * the ranks of an in-process group, SLI_EXEC_PERSIST (in either order of the setters). Every weight and cache type,
+ * batch 1 .. 8, after every prefill route.
+ * sli_model_get_gen_seq: the block in force (the default block outside the mode). sli_model_get_finished: out[b] = 0,
+ * SLI_FIN_STOP or SLI_FIN_LENGTH for every sequence of the batch (all 0 outside the mode). */
+enum { SLI_FIN_STOP = 1, SLI_FIN_LENGTH = 2 };
+int sli_model_set_gen_seq(sli_model* m, int32_t seq, const sli_gen_params* p);
+int sli_model_get_gen_seq(sli_model* m, int32_t seq, sli_gen_params* out);
+int sli_model_get_finished(sli_model* m, int32_t* out /* [batch] */);
 /* One decode step (hipGraph replay; captured on first use). Asynchronous on the model's stream. */
 int sli_model_step(sli_model* m);
 /* Host waits (sync, logits / state / history reads, predict, prefill, the timing probes) of a rank whose step

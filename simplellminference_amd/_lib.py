@@ -73,6 +73,16 @@ class Sampling(ctypes.Structure):  # sli_sampling
     _fields_ = [("temperature", c_f), ("top_k", c_i32), ("top_p", c_f), ("seed", c_u32)]
 
 
+MAX_STOP = 8  # SLI_MAX_STOP
+FIN_STOP, FIN_LENGTH = 1, 2  # SLI_FIN_STOP, SLI_FIN_LENGTH
+
+
+class GenParams(ctypes.Structure):  # sli_gen_params
+    _fields_ = [("temperature", c_f), ("top_k", c_i32), ("top_p", c_f), ("seed", c_u32),
+                ("min_p", c_f), ("repetition_penalty", c_f), ("presence_penalty", c_f), ("frequency_penalty", c_f),
+                ("penalty_from", c_i32), ("max_pos", c_i32), ("n_stop", c_i32), ("stop", c_i32 * MAX_STOP)]
+
+
 class BgemmPlan(ctypes.Structure):  # sli_bgemm_plan
     _fields_ = [(n, c_i32) for n in ("tpw", "splits", "groups", "step_width", "lds_bytes")] + [("counter_off", c_i64)]
 
@@ -135,6 +145,8 @@ _SIGS = {
     "sli_embedding": (c_int, [c_i32, c_vp, c_vp, c_int, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "sli_argmax": (c_int, [c_vp, c_i32, c_vp, c_vp]),
     "sli_sample": (c_int, [c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(Sampling), c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "sli_sample_gen": (c_int, [c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(GenParams), c_i32, c_vp, c_i32, c_vp, c_i64,
+                               c_vp, c_vp]),
     "sli_tp_plan": (c_int, [ctypes.POINTER(ModelConfig), c_i32, ctypes.POINTER(ShardWindow)]),
     "sli_tp_vocab": (c_int, [ctypes.POINTER(ModelConfig), P_i32, P_i32]),
     "sli_comm_id_bytes": (c_int, []),
@@ -164,6 +176,9 @@ _SIGS = {
     "sli_model_get_sampling": (c_int, [c_vp, ctypes.POINTER(Sampling)]),
     "sli_model_get_sampled": (c_int, [c_vp, c_i32, P_i32]),
     "sli_model_graph_captures": (c_int, [c_vp, P_i32]),
+    "sli_model_set_gen_seq": (c_int, [c_vp, c_i32, ctypes.POINTER(GenParams)]),
+    "sli_model_get_gen_seq": (c_int, [c_vp, c_i32, ctypes.POINTER(GenParams)]),
+    "sli_model_get_finished": (c_int, [c_vp, P_i32]),
     "sli_model_step": (c_int, [c_vp]),
     "sli_model_sync": (c_int, [c_vp]),
     "sli_model_get_logits": (c_int, [c_vp, c_vp, c_i32, P_i32]),

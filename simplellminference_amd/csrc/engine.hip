@@ -151,6 +151,14 @@ struct sli_model {
     sli_sampling* samp_dev = nullptr;   // their device copy, read by the sampler launch (no re-capture on a change)
     int32_t* sampled = nullptr;         // [B] the token each sequence drew in the last step (-1: none)
     int captures = 0;                   // step-graph captures so far (sli_model_graph_captures)
+    // per-sequence generation (sli_model_set_gen_seq; gen_sample.h): the blocks on the host, what the sampler and the
+    // stop launch read of them on the device (a change re-captures nothing), and the finished flags
+    bool gen = false;
+    std::vector<sli_gen_params> gen_prm;  // [B]
+    sli::GenRow* gen_rows = nullptr;      // [B]
+    sli::GenStop* gen_stop = nullptr;     // [B]
+    int32_t* gen_from = nullptr;          // [B] the position each sequence stood at before the step's state update
+    int32_t* fin = nullptr;               // [B] 0, SLI_FIN_STOP or SLI_FIN_LENGTH
     // SLI_EXEC_PERSIST: the layer stack as one persistent launch (tp_layers.h); its granule arrays, weight table,
     // launch counter and the device table of every rank's exchange granules (in the one-shot comm buffers)
     struct Tl {
@@ -395,6 +403,39 @@ __global__ void finalize_sampled_kernel(DevState* st, const unsigned long long* 
     st[b].last_argmax = (int)argmax_key_index(st[b].key);
     st[b].key = 0;
     advance_state(st + b, prompt + (size_t)b * (T + 1), hist + (size_t)b * (T + 1), T, sampled[b]);
+}
+
+// The state update of a per-sequence step (sli_model_set_gen_seq): finalize_sampled_kernel, except that a row the
+// sampler left at once (-1: temperature 0, no penalty) takes the argmax key's token, and that the position before
+// the update is kept for the stop launch.
+__global__ void finalize_gen_kernel(DevState* st, const unsigned long long* __restrict__ keys, int32_t* sampled,
+                                    const int32_t* __restrict__ prompt, int32_t* hist, int32_t* from, int T, int B) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    if (keys) st[b].key = keys[b];
+    st[b].last_argmax = (int)argmax_key_index(st[b].key);
+    st[b].key = 0;
+    if (sampled[b] < 0) sampled[b] = st[b].last_argmax;
+    from[b] = st[b].pos;
+    advance_state(st + b, prompt + (size_t)b * (T + 1), hist + (size_t)b * (T + 1), T, sampled[b]);
+}
+
+// The stop rule (sli.h at sli_model_set_gen_seq), one thread per sequence: only a sequence that is advancing and has
+// just moved to a position whose token was chosen is looked at; a finished one is parked where it stands.
+__global__ void gen_stop_kernel(DevState* st, const GenStop* __restrict__ gs, const int32_t* __restrict__ from,
+                                int32_t* fin, int T, int B) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    DevState& d = st[b];
+    if (!d.advance || d.pos == from[b] || d.pos < d.n_forced) return;
+    const GenStop g = gs[b];
+    int f = 0;
+    for (int i = 0; i < g.n_stop && i < SLI_MAX_STOP; ++i) f = g.stop[i] == d.token ? SLI_FIN_STOP : f;
+    if (!f && ((g.max_pos > 0 && d.pos >= g.max_pos) || d.pos == T - 1)) f = SLI_FIN_LENGTH;
+    if (f) {
+        fin[b] = f;
+        d.advance = 0;
+    }
 }
 
 // ---- batch > 1: one sequence per block / thread
@@ -1059,7 +1100,7 @@ struct StepRecorder {
         }
         SLI_TRY(gemv_lm(m));
         SLI_TRY(record_sample(m));
-        if (exchange || m->sampling)  // a sampling step updates the state in record_finalize
+        if (exchange || m->sampling || m->gen)  // a sampling step updates the state in record_finalize
             hipLaunchKernelGGL(keyreduce_kernel<false>, dim3(1), dim3(kKeyThreads), 0, s, m->keys, lm_head_blocks(m),
                                m->st, m->prompt, m->hist, m->T);
         else
@@ -1070,6 +1111,13 @@ struct StepRecorder {
     }
     // the draw of a sampling step (sample.h): row b of the logits as sequence b at the position just fed
     static int record_sample(sli_model* m) {
+        if (m->gen) {  // each row with its own block, over the model's own history (gen_sample.h); a model beyond the
+                       // table's capacity launches without it, and set_gen_seq takes no penalised block there
+            const bool table = gen_capacity_error(m->v_n, m->T + 1) == nullptr;
+            SLI_HIP(launch_sample_gen(m->logits, m->v_n, m->B, m->v_n, nullptr, m->gen_rows, 0, &m->st->pos, kPosStride,
+                                      m->hist, m->T + 1, table, m->sampled, m->stream));
+            return SLI_OK;
+        }
         if (!m->sampling) return SLI_OK;
         SLI_HIP(launch_sample(m->logits, m->v_n, m->B, m->v_n, m->samp, m->samp_dev, 0, &m->st->pos, kPosStride,
                               m->sampled, m->stream));
@@ -1078,7 +1126,13 @@ struct StepRecorder {
     // state update after the (exchanged) argmax keys: position, next token, history (model.cpp:157-183)
     static int record_finalize(sli_model* m) {
         hipStream_t s = m->stream;
-        if (m->sampling)
+        if (m->gen) {
+            hipLaunchKernelGGL(finalize_gen_kernel, dim3(1), dim3(64), 0, s, m->st, m->B > 1 ? m->bkeys : nullptr,
+                               m->sampled, m->prompt, m->hist, m->gen_from, m->T, m->B);
+            SLI_HIP(hipGetLastError());
+            hipLaunchKernelGGL(gen_stop_kernel, dim3(1), dim3(64), 0, s, m->st, m->gen_stop, m->gen_from, m->fin, m->T,
+                               m->B);
+        } else if (m->sampling)
             hipLaunchKernelGGL(finalize_sampled_kernel, dim3(1), dim3(64), 0, s, m->st, m->B > 1 ? m->bkeys : nullptr,
                                m->sampled, m->prompt, m->hist, m->T, m->B);
         else if (m->B > 1)
@@ -1111,7 +1165,7 @@ struct StepRecorder {
         }
         if (!m->collectives) {
             SLI_TRY(record_head(m, m->B > 1));
-            return m->B > 1 || m->sampling ? record_finalize(m) : SLI_OK;
+            return m->B > 1 || m->sampling || m->gen ? record_finalize(m) : SLI_OK;
         }
         SLI_TRY(record_head(m, true));
         if (m->B > 1)
@@ -1484,6 +1538,15 @@ static int download_states(sli_model* m, std::vector<DevState>& h) {
     return SLI_OK;
 }
 
+// A host call that writes sequence seq's state (seq < 0: every sequence's) clears its finished flag; outside the
+// per-sequence mode every flag is 0 already.
+static int clear_finished(sli_model* m, int seq) {
+    if (!m->gen) return SLI_OK;
+    int32_t* at = m->fin + (seq < 0 ? 0 : seq);
+    SLI_HIP(hipMemsetAsync(at, 0, sizeof(int32_t) * (seq < 0 ? m->B : 1), m->stream));
+    return SLI_OK;
+}
+
 // Device-side error bits (DevState::error: a bounded spin of the one-shot all-reduce or of the fused q/k/v +
 // attention hand-off gave up, leaving stale outputs) surfaced as a status: every predict path calls this after its
 // final stream sync, so a step that returned early never yields SLI_OK with garbage tokens.
@@ -1778,6 +1841,10 @@ static int create_model(const sli_model_config* cfg, const void* comm_id, sli_tp
     A((void**)&m->st, sizeof(DevState) * B);
     A((void**)&m->samp_dev, sizeof(sli_sampling));
     A((void**)&m->sampled, sizeof(int32_t) * B);
+    A((void**)&m->gen_rows, sizeof(GenRow) * B);
+    A((void**)&m->gen_stop, sizeof(GenStop) * B);
+    A((void**)&m->gen_from, sizeof(int32_t) * B);
+    A((void**)&m->fin, sizeof(int32_t) * B);
     A((void**)&m->prompt, sizeof(int32_t) * B * (m->T + 1));
     A((void**)&m->hist, sizeof(int32_t) * B * (m->T + 1));
     if (rc != SLI_OK) return bail(rc);
@@ -1909,6 +1976,7 @@ int sli_model_reset(sli_model* m) {
     SLI_HIP(hipMemsetAsync(m->vc, 0, kv, m->stream));
     std::vector<DevState> h(m->B);
     for (auto& d : h) d.advance = 1;
+    SLI_TRY(clear_finished(m, -1));
     return upload_states(m, h);
 }
 
@@ -1937,6 +2005,7 @@ static int set_state(sli_model* m, int seq, int32_t token, int32_t pos, int32_t 
         h[b].advance = advance ? 1 : 0;
         h[b].key = 0;
         h[b].error = 0;
+        SLI_TRY(clear_finished(m, b));
         SLI_HIP(hipMemcpyAsync(m->hist + (size_t)b * (m->T + 1) + pos, &token, sizeof(int32_t), hipMemcpyHostToDevice,
                                m->stream));
     }
@@ -2331,9 +2400,11 @@ static void put_state(DevState& d, int32_t token, int32_t pos, int32_t n_forced,
 // what a continuation leaves of the listed sequences' states (h: the states as downloaded before the call)
 static int ext_put_states(sli_model* m, std::vector<DevState>& h, const int32_t* seqs, int n_seqs, const int32_t* tokens,
                           const int32_t* starts, const int32_t* counts, int ld, int advance) {
-    for (int i = 0; i < n_seqs; ++i)
+    for (int i = 0; i < n_seqs; ++i) {
         put_state(h[seqs[i]], tokens[(size_t)i * ld + counts[i] - 1], starts[i] + counts[i] - 1, starts[i] + counts[i],
                   advance);
+        SLI_TRY(clear_finished(m, seqs[i]));
+    }
     return upload_states(m, h);
 }
 
@@ -2537,6 +2608,7 @@ static int copy_prefix_rank(sli_model* m, int src, int dst, int n, int32_t tok) 
     std::vector<DevState> h;
     SLI_TRY(download_states(m, h));
     put_state(h[dst], tok, n, n + 1, 0);
+    SLI_TRY(clear_finished(m, dst));
     return upload_states(m, h);
 }
 
@@ -2635,6 +2707,23 @@ extern "C" int sli_model_predict_batch_prefill(sli_model* m, const int32_t* prom
     return check_device_errors(m);
 }
 
+// the default block of a sequence: greedy, no penalties, no stop
+static sli_gen_params gen_default() {
+    sli_gen_params p{};
+    p.top_p = 1.0f;
+    p.repetition_penalty = 1.0f;
+    return p;
+}
+// every sequence back to the default block, on the host and on the device, and no sequence finished
+static int gen_clear(sli_model* m) {
+    m->gen_prm.assign(m->B, gen_default());
+    const std::vector<GenRow> rows(m->B, gen_row(gen_default()));
+    SLI_HIP(hipMemcpyAsync(m->gen_rows, rows.data(), sizeof(GenRow) * m->B, hipMemcpyHostToDevice, m->stream));
+    SLI_HIP(hipMemsetAsync(m->gen_stop, 0, sizeof(GenStop) * m->B, m->stream));
+    SLI_HIP(hipMemsetAsync(m->fin, 0, sizeof(int32_t) * m->B, m->stream));
+    return wait_stream(m);
+}
+
 extern "C" {
 
 int sli_model_set_state(sli_model* m, int32_t token, int32_t pos, int32_t advance) {
@@ -2678,7 +2767,7 @@ int sli_model_set_exec(sli_model* m, int32_t mode) {
     if (mode == SLI_EXEC_PERSIST) {
         std::string why;
         SLI_CHECK(tpl_check(m, &why), SLI_ERR_STATE, "persistent layers: " + why);
-        SLI_CHECK(!m->sampling, SLI_ERR_STATE,
+        SLI_CHECK(!m->sampling && !m->gen, SLI_ERR_STATE,
                   "persistent layers: not while sampling is on (sli_model_set_sampling(NULL) first)");
     }
     SLI_HIP(hipSetDevice(m->c.device));
@@ -2702,6 +2791,12 @@ int sli_model_set_sampling(sli_model* m, const sli_sampling* p) {
                   "set_sampling: tp_size > 1 shards the logits over the ranks (no distributed threshold yet)");
         SLI_CHECK(m->exec != SLI_EXEC_PERSIST, SLI_ERR_STATE,
                   "set_sampling: not under the persistent layers (sli_model_set_exec(SLI_EXEC_LAUNCHES) first)");
+    }
+    if (m->gen) {  // any call leaves the per-sequence mode: every block cleared, this call's own graph recorded next
+        SLI_HIP(hipSetDevice(m->c.device));
+        SLI_TRY(drop_step_graph(m));
+        SLI_TRY(gen_clear(m));
+        m->gen = false;
     }
     if (!on && !m->sampling) return SLI_OK;
     SLI_HIP(hipSetDevice(m->c.device));
@@ -2728,10 +2823,67 @@ int sli_model_get_sampled(sli_model* m, int32_t seq, int32_t* token) {
     SLI_CHECK(m && token, SLI_ERR_ARG, "null argument");
     SLI_CHECK(seq >= 0 && seq < m->B, SLI_ERR_RANGE, "sequence index out of range");
     *token = -1;
-    if (!m->sampling) return SLI_OK;
+    if (!m->sampling && !m->gen) return SLI_OK;
     SLI_HIP(hipMemcpyAsync(token, m->sampled + seq, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
     SLI_TRY(wait_stream(m));
     return SLI_OK;
+}
+
+int sli_model_set_gen_seq(sli_model* m, int32_t seq, const sli_gen_params* p) {
+    SLI_CHECK(m, SLI_ERR_ARG, "null model");
+    const sli_gen_params prm = p ? *p : gen_default();
+    const char* why = gen_params_error(prm);
+    SLI_CHECK(!why, SLI_ERR_ARG, std::string("set_gen_seq: ") + (why ? why : ""));
+    SLI_CHECK(seq >= 0 && seq < m->B, SLI_ERR_RANGE, "set_gen_seq: sequence index out of range");
+    for (int i = 0; i < prm.n_stop; ++i)
+        SLI_CHECK(prm.stop[i] >= 0 && prm.stop[i] < m->V, SLI_ERR_RANGE, "set_gen_seq: a stop token outside [0, vocab)");
+    SLI_CHECK(prm.max_pos <= m->T - 1, SLI_ERR_RANGE, "set_gen_seq: max_pos beyond max_len - 1");
+    SLI_CHECK(!m->group, SLI_ERR_STATE,
+              "set_gen_seq: the ranks of an in-process tp group hold vocab shards of the logits (no distributed "
+              "threshold yet)");
+    SLI_CHECK(m->c.tp_size <= 1, SLI_ERR_STATE,
+              "set_gen_seq: tp_size > 1 shards the logits over the ranks (no distributed threshold yet)");
+    SLI_CHECK(m->exec != SLI_EXEC_PERSIST, SLI_ERR_STATE,
+              "set_gen_seq: not under the persistent layers (sli_model_set_exec(SLI_EXEC_LAUNCHES) first)");
+    // beyond the table's capacity the mode runs without it (record_sample): only a penalised block is refused
+    const char* cap = gen_penalised(prm) ? gen_capacity_error(m->v_n, m->T + 1) : nullptr;
+    SLI_CHECK(!cap, SLI_ERR_SHAPE,
+              std::string("set_gen_seq: ") + (cap ? cap : "") + ": vocab " + std::to_string(m->v_n) + ", max_len " +
+                  std::to_string(m->T));
+    SLI_HIP(hipSetDevice(m->c.device));
+    if (!m->gen) {  // the per-row sampler and the stop launch join the step graph (and the model-level sampler leaves)
+        SLI_TRY(drop_step_graph(m));
+        SLI_HIP(hipMemsetAsync(m->sampled, 0xFF, sizeof(int32_t) * m->B, m->stream));
+        m->sampling = false;
+        m->samp = sli_sampling{};
+        SLI_TRY(gen_clear(m));
+        m->gen = true;
+    }
+    m->gen_prm[seq] = prm;
+    const GenRow row = gen_row(prm);
+    GenStop st{};
+    st.max_pos = prm.max_pos;
+    st.n_stop = prm.n_stop;
+    std::copy_n(prm.stop, SLI_MAX_STOP, st.stop);
+    SLI_HIP(hipMemcpyAsync(m->gen_rows + seq, &row, sizeof(row), hipMemcpyHostToDevice, m->stream));
+    SLI_HIP(hipMemcpyAsync(m->gen_stop + seq, &st, sizeof(st), hipMemcpyHostToDevice, m->stream));
+    SLI_TRY(clear_finished(m, seq));
+    return wait_stream(m);  // (row and st are read by the copies)
+}
+
+int sli_model_get_gen_seq(sli_model* m, int32_t seq, sli_gen_params* out) {
+    SLI_CHECK(m && out, SLI_ERR_ARG, "null argument");
+    SLI_CHECK(seq >= 0 && seq < m->B, SLI_ERR_RANGE, "sequence index out of range");
+    *out = m->gen ? m->gen_prm[seq] : gen_default();
+    return SLI_OK;
+}
+
+int sli_model_get_finished(sli_model* m, int32_t* out) {
+    SLI_CHECK(m && out, SLI_ERR_ARG, "null argument");
+    std::fill_n(out, m->B, 0);
+    if (!m->gen) return SLI_OK;
+    SLI_HIP(hipMemcpyAsync(out, m->fin, sizeof(int32_t) * m->B, hipMemcpyDeviceToHost, m->stream));
+    return wait_stream(m);
 }
 
 int sli_model_graph_captures(sli_model* m, int32_t* n) {

@@ -13,6 +13,7 @@
 #include "ops_internal.h"
 #include "rope_table.h"
 #include "sample.h"
+#include "gen_sample.h"
 
 namespace sli {
 
@@ -697,6 +698,34 @@ int sli_sample(const float* logits, int64_t row_stride, int32_t rows, int32_t vo
     SLI_CHECK(!why, SLI_ERR_ARG, std::string("sli_sample: ") + (why ? why : ""));
     SLI_HIP(launch_sample(logits, row_stride, rows, vocab, *p, nullptr, seq0, pos_dev, pos_stride, out_dev,
                           as_stream(stream)));
+    return SLI_OK;
+}
+
+int sli_sample_gen(const float* logits, int64_t row_stride, int32_t rows, int32_t vocab, const sli_gen_params* p,
+                   int32_t seq0, const int32_t* pos_dev, int32_t pos_stride, const int32_t* hist_dev,
+                   int64_t hist_stride, int32_t* out_dev, sli_stream_t stream) {
+    SLI_CHECK(logits && p && pos_dev && out_dev, SLI_ERR_ARG, "sli_sample_gen: null pointer");
+    SLI_CHECK(rows > 0 && vocab > 0, SLI_ERR_ARG, "sli_sample_gen: rows and vocab must be positive");
+    SLI_CHECK(row_stride == 0 || row_stride >= vocab, SLI_ERR_ARG, "sli_sample_gen: row_stride is 0 or at least vocab");
+    SLI_CHECK(pos_stride >= 0, SLI_ERR_ARG, "sli_sample_gen: pos_stride < 0");
+    bool table = false;
+    std::vector<GenRow> g(rows);
+    for (int r = 0; r < rows; ++r) {
+        const char* why = gen_params_error(p[r]);
+        SLI_CHECK(!why, SLI_ERR_ARG, "sli_sample_gen: row " + std::to_string(r) + ": " + (why ? why : ""));
+        table = table || gen_penalised(p[r]);
+        g[r] = gen_row(p[r]);
+    }
+    if (table) {
+        SLI_CHECK(hist_dev, SLI_ERR_ARG, "sli_sample_gen: null hist_dev with an active penalty");
+        SLI_CHECK(hist_stride >= 1, SLI_ERR_ARG, "sli_sample_gen: hist_stride < 1 with an active penalty");
+        const char* cap = gen_capacity_error(vocab, hist_stride);
+        SLI_CHECK(!cap, SLI_ERR_SHAPE,
+                  std::string("sli_sample_gen: ") + (cap ? cap : "") + ": vocab " + std::to_string(vocab) +
+                      ", hist_stride " + std::to_string(hist_stride));
+    }
+    SLI_HIP(launch_sample_gen(logits, row_stride, rows, vocab, g.data(), nullptr, seq0, pos_dev, pos_stride, hist_dev,
+                              hist_stride, table, out_dev, as_stream(stream)));
     return SLI_OK;
 }
 

@@ -25,4 +25,25 @@ hipError_t launch_sample(const float* logits, long long row_stride, int rows, in
                          const sli_sampling* pd, int seq0, const int32_t* pos, int pos_stride, int32_t* out,
                          hipStream_t s);
 
+// gen_sample.h: the per-row sampler. GenRow is what the kernel reads of one sli_gen_params (gen_row: log_min_p is
+// computed here, on the host). gen_params_error: the ranges of sli.h (null, or what is wrong); gen_capacity_error: null,
+// or why a penalised row cannot take vocabulary V and history rows of hist_len elements. pd != null: `rows` blocks in
+// device memory, read when the kernel runs; else pv: `rows` host blocks. table: some row may be penalised.
+struct GenRow {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    uint32_t seed;
+    float min_p, log_min_p;
+    float repetition_penalty, presence_penalty, frequency_penalty;
+    int32_t penalty_from;
+};
+const char* gen_params_error(const sli_gen_params& p);
+const char* gen_capacity_error(int V, long long hist_len);
+bool gen_penalised(const sli_gen_params& p);
+GenRow gen_row(const sli_gen_params& p);
+hipError_t launch_sample_gen(const float* logits, long long row_stride, int rows, int V, const GenRow* pv,
+                             const GenRow* pd, int seq0, const int32_t* pos, int pos_stride, const int32_t* hist,
+                             long long hist_len, bool table, int32_t* out, hipStream_t s);
+
 }  // namespace sli

@@ -130,46 +130,45 @@ __device__ __forceinline__ unsigned sample_prefix_mask(int level) {
 }
 __device__ __forceinline__ int sample_digit_shift(int level) { return level == 0 ? 21 : level == 1 ? 10 : 0; }
 
-// Row r of the launch: sequence seq0 + r at position pos[r * pos_stride]. pd != null: the parameters are read from
-// device memory (the engine's graph), else pv holds them.
-__global__ void __launch_bounds__(kSampleThreads)
-    sample_kernel(const float* __restrict__ logits, long long row_stride, int V, sli_sampling pv,
-                  const sli_sampling* __restrict__ pd, int seq0, const int32_t* __restrict__ pos, int pos_stride,
-                  int32_t* __restrict__ out) {
-    __shared__ SampleShared sh;
-    const int r = blockIdx.x;
-    const float* row = logits + (long long)r * row_stride;
-    const sli_sampling prm = pd ? *pd : pv;
-    const float T = prm.temperature;
-
+// The rule for one row, shared by sample_kernel and gen_sample.h's per-row kernel: each(f) calls f(value, index) for
+// every element of the row exactly once, in any pass (the row itself, or its penalised values). Returns the token in
+// every thread. GEN adds what sli_sample_gen's rule adds: temperature 0 (the argmax of the row is the answer) and
+// min-p in the draw pass (min_p_on, c = log(min_p)); without GEN both are compiled out and the arguments unused.
+template <bool GEN, class Each>
+__device__ __forceinline__ int32_t sample_row(Each each, int V, float T, int top_k, float top_p, uint32_t seed,
+                                              bool min_p_on, float c, int seq, const int32_t* __restrict__ posp,
+                                              SampleShared& sh) {
     // ---- pass 1: the maximum
     unsigned mo = 0;
-    sample_row_each(row, V, [&](float v, int) {
-        const unsigned o = sample_ord(v);
-        mo = o > mo ? o : mo;
-    });
-    mo = (unsigned)sample_block_max(mo, sh);
-    if (mo < kSampleOrdFiniteMin || mo >= kSampleOrdPosInf) {  // no finite maximum: sli_argmax's answer
+    bool greedy = false;
+    if constexpr (GEN) greedy = T == 0.0f;
+    if (!greedy) {
+        each([&](float v, int) {
+            const unsigned o = sample_ord(v);
+            mo = o > mo ? o : mo;
+        });
+        mo = (unsigned)sample_block_max(mo, sh);
+    }
+    if (greedy || mo < kSampleOrdFiniteMin || mo >= kSampleOrdPosInf) {  // no finite maximum: sli_argmax's answer
         unsigned long long best = 0;
-        sample_row_each(row, V, [&](float v, int i) {
+        each([&](float v, int i) {
             const unsigned long long k = argmax_key(v, (unsigned)i);
             best = k > best ? k : best;
         });
         best = sample_block_max(best, sh);
-        if (threadIdx.x == 0) out[r] = (int32_t)argmax_key_index(best);
-        return;
+        return (int32_t)argmax_key_index(best);
     }
     const float m = sample_ord_value(mo);
     unsigned lo = kSampleOrdFiniteMin;  // candidates: image >= lo
 
     // ---- top-k: the image of the k-th largest element
-    if (prm.top_k > 0 && prm.top_k < V) {
+    if (top_k > 0 && top_k < V) {
         unsigned thr = 0;
-        unsigned long long need = (unsigned long long)prm.top_k;
+        unsigned long long need = (unsigned long long)top_k;
         for (int level = 0; level < 3; ++level) {
             sample_clear_hist(sh);
             const unsigned mask = sample_prefix_mask(level);
-            sample_row_each(row, V, [&](float v, int) {
+            each([&](float v, int) {
                 const unsigned o = sample_ord(v);
                 if ((o & mask) == thr) atomicAdd(&sh.hist[sample_digit(o, level)], 1ull);
             });
@@ -182,13 +181,13 @@ __global__ void __launch_bounds__(kSampleThreads)
     }
 
     // ---- top-p over the top-k set: the largest image whose upper mass reaches top_p of the whole
-    if (prm.top_p < 1.0f) {
+    if (top_p < 1.0f) {
         unsigned thr = 0;
         unsigned long long need = 0;
         for (int level = 0; level < 3; ++level) {
             sample_clear_hist(sh);
             const unsigned mask = sample_prefix_mask(level);
-            sample_row_each(row, V, [&](float v, int) {
+            each([&](float v, int) {
                 const unsigned o = sample_ord(v);
                 if (o >= lo && (o & mask) == thr) {
                     const float w = expf(__fdiv_rn(__fsub_rn(v, m), T));  // in (0, 1]; the maximum gives 1
@@ -200,7 +199,7 @@ __global__ void __launch_bounds__(kSampleThreads)
                 // the whole mass Z is only known after this scan: find the bin against Z itself first (its `total`),
                 // then against the target ceil(top_p * Z), at least 1 and at most Z (Z >= 2^40: the maximum's mass)
                 (void)sample_find_bin(sh, 1ull, above, total);
-                const double want = ceil((double)prm.top_p * (double)total);
+                const double want = ceil((double)top_p * (double)total);
                 need = (unsigned long long)want;
                 need = need < 1ull ? 1ull : need > total ? total : need;
             }
@@ -211,21 +210,39 @@ __global__ void __launch_bounds__(kSampleThreads)
         lo = thr > lo ? thr : lo;
     }
 
-    // ---- the draw: Gumbel-max over the candidates
-    const int32_t p = pos[(long long)r * pos_stride];
-    const uint32_t stream = ((uint32_t)SLI_SAMPLE_STREAM << 16) | ((uint32_t)(seq0 + r) & 0xFFFFu);
+    // ---- the draw: Gumbel-max over the candidates (GEN: those that pass min-p; the maximum always does)
+    const int32_t p = *posp;
+    const uint32_t stream = ((uint32_t)SLI_SAMPLE_STREAM << 16) | ((uint32_t)seq & 0xFFFFu);
     const uint64_t hi = (uint64_t)(uint32_t)p << 32;
     unsigned long long best = 0;
-    sample_row_each(row, V, [&](float v, int i) {
+    each([&](float v, int i) {
         if (sample_ord(v) < lo) return;
-        const uint32_t h = sli_rng_u32(prm.seed, stream, hi | (uint32_t)i);
+        if constexpr (GEN) {
+            if (min_p_on && !(__fdiv_rn(__fsub_rn(v, m), T) >= c)) return;
+        }
+        const uint32_t h = sli_rng_u32(seed, stream, hi | (uint32_t)i);
         const float u = (float)(2u * (h >> 9) + 1u) * 5.9604644775390625e-08f;  // exact: an odd 24-bit integer * 2^-24
         const float key = __fsub_rn(__fdiv_rn(v, T), logf(-logf(u)));
         const unsigned long long k = argmax_key(key, (unsigned)i);
         best = k > best ? k : best;
     });
     best = sample_block_max(best, sh);
-    if (threadIdx.x == 0) out[r] = (int32_t)argmax_key_index(best);
+    return (int32_t)argmax_key_index(best);
+}
+
+// Row r of the launch: sequence seq0 + r at position pos[r * pos_stride]. pd != null: the parameters are read from
+// device memory (the engine's graph), else pv holds them.
+__global__ void __launch_bounds__(kSampleThreads)
+    sample_kernel(const float* __restrict__ logits, long long row_stride, int V, sli_sampling pv,
+                  const sli_sampling* __restrict__ pd, int seq0, const int32_t* __restrict__ pos, int pos_stride,
+                  int32_t* __restrict__ out) {
+    __shared__ SampleShared sh;
+    const int r = blockIdx.x;
+    const float* row = logits + (long long)r * row_stride;
+    const sli_sampling prm = pd ? *pd : pv;
+    const int32_t tok = sample_row<false>([&](auto f) { sample_row_each(row, V, f); }, V, prm.temperature, prm.top_k,
+                                          prm.top_p, prm.seed, false, 0.0f, seq0 + r, pos + (long long)r * pos_stride, sh);
+    if (threadIdx.x == 0) out[r] = tok;
 }
 
 // the argument ranges of sli.h, host only: null, or what is wrong (a NaN fails every comparison)

@@ -16,6 +16,12 @@ struct DevState {
     unsigned long long key;  // argmax key of the last step (0 between steps)
 };
 
+// what the stop launch of a per-sequence step reads of a sequence's sli_gen_params (sli_model_set_gen_seq)
+struct GenStop {
+    int32_t max_pos, n_stop;
+    int32_t stop[SLI_MAX_STOP];
+};
+
 // model.cpp:157-183: next position; teacher-forced prompt token while inside the prompt, else `next` (the greedy
 // argmax, or the token a sampling step drew).
 __device__ __forceinline__ void advance_state(DevState* st, const int32_t* prompt, int32_t* hist, int T, int next) {

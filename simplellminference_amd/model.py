@@ -224,6 +224,105 @@ class LlamaModel:
         call("sli_model_graph_captures", self._h, ctypes.byref(v))
         return v.value
 
+    # ------------------------------------------------------------------ per-sequence generation (sli_model_set_gen_seq)
+    def set_generation(self, seq: int, temperature: float | None = 0.0, top_k: int = 0, top_p: float = 1.0,
+                       seed: int = 0, min_p: float = 0.0, repetition_penalty: float = 1.0,
+                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_from: int = 0,
+                       max_pos: int = 0, stop=()) -> "LlamaModel":
+        """Sequence ``seq``'s own generation block (the rule: sli.h at sli_sample_gen and sli_model_set_gen_seq):
+        sampling, min-p, the three penalties over its history from ``penalty_from`` on, and its stop conditions (up to
+        8 ``stop`` tokens; ``max_pos``: the last position it may reach, 0 for none). ``set_generation(seq, None)``
+        returns it to the default (greedy, no penalties, no stop). The first call puts the model into per-sequence
+        mode; later changes re-capture nothing; any ``set_sampling`` call leaves the mode."""
+        if temperature is None:
+            call("sli_model_set_gen_seq", self._h, seq, None)
+        else:
+            from .ops import gen_params
+            prm = gen_params(temperature, top_k, top_p, seed, min_p, repetition_penalty, presence_penalty,
+                             frequency_penalty, penalty_from, max_pos, stop)
+            call("sli_model_set_gen_seq", self._h, seq, ctypes.byref(prm))
+        return self
+
+    def generation(self, seq: int) -> dict:
+        """Sequence ``seq``'s block in force, as set_generation's keywords."""
+        prm = _lib.GenParams()
+        call("sli_model_get_gen_seq", self._h, seq, ctypes.byref(prm))
+        d = {n: getattr(prm, n) for n, _ in _lib.GenParams._fields_[:10]}
+        d["stop"] = tuple(prm.stop[:prm.n_stop])
+        return d
+
+    def finished(self) -> np.ndarray:
+        """Per sequence: 0 (running or waiting), 1 (it drew one of its stop tokens) or 2 (it reached max_pos or the last
+        position): sli_model_get_finished."""
+        out = np.zeros(self.batch, np.int32)
+        call("sli_model_get_finished", self._h, out.ctypes.data_as(_lib.P_i32))
+        return out
+
+    _GEN_KEYS = {"temperature", "top_k", "top_p", "seed", "min_p", "repetition_penalty", "presence_penalty",
+                 "frequency_penalty", "penalty_from", "stop"}
+
+    def generate(self, requests) -> list[dict]:
+        """Run a queue of requests through the batch. A request is a dict with ``prompt`` (token ids),
+        ``max_new_tokens`` and any set_generation keyword (``seed`` defaults to the request's index). Free slots are
+        filled from the queue in order (the newly admitted prompts in one prefill_batch call, a one-token prompt
+        through set_state_seq), every step is followed by one finished() read, and a finished slot's tokens from
+        len(prompt) on are its result, the stop token included. Returns, in request order, ``{"tokens": int32 array,
+        "finish": "stop" | "length"}``. The model is left in per-sequence mode with every block cleared. Every request
+        is validated (lengths, keywords, the number of stop tokens) before anything runs. A draw is seeded by (seed,
+        slot, position), so a sampled request's tokens depend on the slot of the batch it lands in, hence on the
+        queue before it; the same call repeats bit for bit, and greedy requests do not depend on their slot."""
+        if not self.prefill_batch_ok():
+            raise RuntimeError("generate needs a model that takes prefill_batch (prefill_batch_ok())")
+        reqs = []
+        for i, r in enumerate(requests):
+            r = dict(r)
+            prompt = [int(t) for t in r.pop("prompt")]
+            new = int(r.pop("max_new_tokens"))
+            if not prompt or new < 1 or len(prompt) + new > self.config.max_length:
+                raise ValueError(f"request {i}: needs a prompt, max_new_tokens >= 1 and len(prompt) + max_new_tokens "
+                                 "<= max_len")
+            r.setdefault("seed", i)
+            unknown = set(r) - self._GEN_KEYS
+            if unknown:
+                raise ValueError(f"request {i}: unknown keys {sorted(unknown)} (max_pos follows from max_new_tokens)")
+            if len(tuple(r.get("stop", ()))) > _lib.MAX_STOP:
+                raise ValueError(f"request {i}: at most {_lib.MAX_STOP} stop tokens")
+            reqs.append((prompt, new, r))
+        results: list = [None] * len(reqs)
+        slots: list = [None] * self.batch  # the request each sequence runs
+        queue = list(range(len(reqs)))
+        for b in range(self.batch):  # nothing runs but what is admitted
+            self.set_generation(b, None)
+            st = self.state(b)
+            self.set_state_seq(b, st["token"], st["pos"], advance=False)
+        while queue or any(s is not None for s in slots):
+            new_slots = []
+            for b in range(self.batch):
+                if slots[b] is None and queue:
+                    slots[b] = queue.pop(0)
+                    new_slots.append(b)
+            packed = [b for b in new_slots if len(reqs[slots[b]][0]) > 1]
+            if packed:
+                self.prefill_batch([reqs[slots[b]][0] for b in packed], packed)
+            for b in new_slots:
+                prompt, new, kw = reqs[slots[b]]
+                if len(prompt) == 1:
+                    self.set_prompt_seq(b, prompt)
+                    self.set_state_seq(b, prompt[0], 0, advance=True)
+                self.set_generation(b, max_pos=len(prompt) - 1 + new, **kw)
+            self.step()
+            fin = self.finished()
+            for b in range(self.batch):
+                if slots[b] is None or not fin[b]:
+                    continue
+                prompt = reqs[slots[b]][0]
+                pos = self.state(b)["pos"]
+                results[slots[b]] = {"tokens": self.history(b, pos + 1)[len(prompt):].copy(),
+                                     "finish": "stop" if fin[b] == _lib.FIN_STOP else "length"}
+                slots[b] = None
+                self.set_generation(b, None)
+        return results
+
     # ------------------------------------------------------------------ tensor-parallel all-reduce
     def comm_handle(self) -> bytes:
         """This rank's one-shot all-reduce buffer as an IPC handle (exchange it with the other ranks)."""

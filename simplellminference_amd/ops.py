@@ -842,3 +842,45 @@ def sample(logits, temperature: float, top_k: int, top_p: float, seed: int, pos,
     call("sli_sample", _p(logits), logits.stride(0) if rows > 1 else vocab, rows, vocab, ctypes.byref(prm), seq0,
          _p(pos), pos.stride(0) if rows > 1 else 1, _p(out), _s())
     return out
+
+
+def gen_params(temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, min_p: float = 0.0,
+               repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+               penalty_from: int = 0, max_pos: int = 0, stop=()) -> "_lib.GenParams":
+    """One sli_gen_params block (the defaults: greedy, no penalties, no stop)."""
+    stop = [int(t) for t in stop]
+    if len(stop) > _lib.MAX_STOP:
+        raise ValueError(f"at most {_lib.MAX_STOP} stop tokens")
+    return _lib.GenParams(temperature, top_k, top_p, seed & 0xFFFFFFFF, min_p, repetition_penalty, presence_penalty,
+                          frequency_penalty, penalty_from, max_pos, len(stop),
+                          (ctypes.c_int32 * _lib.MAX_STOP)(*stop))
+
+
+def sample_gen(logits, params, pos, hist=None, seq0: int = 0, out=None):
+    """sli_sample_gen: ops.sample with one parameter block per row (``params``: a list of gen_params() blocks or of
+    dicts of its keywords) and the rows' token histories (``hist``: int32 device tensor [rows, n], tokens by position;
+    needed iff a row has an active penalty). Returns the int32 tokens [rows]; -1 for a row with temperature 0 and no
+    penalty, whose token is the argmax."""
+    if logits.dim() == 1:
+        logits = logits.unsqueeze(0)
+    rows, vocab = logits.shape
+    if not logits.is_cuda or logits.dtype != torch.float32 or (vocab > 1 and logits.stride(1) != 1):
+        raise ValueError("logits: fp32 device rows of contiguous elements")
+    if not pos.is_cuda or pos.dtype != torch.int32 or pos.dim() != 1 or pos.shape[0] < rows:
+        raise ValueError("pos: an int32 device tensor of one position per row")
+    if len(params) != rows:
+        raise ValueError("one parameter block per row")
+    blocks = (_lib.GenParams * rows)(*[p if isinstance(p, _lib.GenParams) else gen_params(**p) for p in params])
+    hp, hs = None, 0
+    if hist is not None:
+        if hist.dim() == 1:
+            hist = hist.unsqueeze(0)
+        if not hist.is_cuda or hist.dtype != torch.int32 or hist.shape[0] < rows or \
+                (hist.shape[1] > 1 and hist.stride(1) != 1) or (rows > 1 and hist.stride(0) != hist.shape[1]):
+            raise ValueError("hist: an int32 device tensor [rows, n] of contiguous rows")
+        hp, hs = _p(hist), hist.shape[1]
+    out = torch.empty(rows, device=logits.device, dtype=torch.int32) if out is None else out
+    _dev(out)
+    call("sli_sample_gen", _p(logits), logits.stride(0) if rows > 1 else vocab, rows, vocab, blocks, seq0,
+         _p(pos), pos.stride(0) if rows > 1 else 1, hp, hs, _p(out), _s())
+    return out
