@@ -107,6 +107,22 @@ int sli_matmul_mxfp4(const float* x, const void* data, const void* scales, float
 int sli_quant_f8(const float* src, void* codes, size_t n, sli_stream_t stream);
 int sli_dequant_f8(const void* codes, float* dst, size_t n, sli_stream_t stream);
 
+/* MXFP8 activations: OCP microscaling FP8, the narrow activation format of the block-scaled MFMA prefill
+ * (sli_prefill_gemm_mx8). An [M][K] image needs K % 32 == 0 and is two arrays:
+ *   codes  uint8 [M][K]: E4M3 codes as above;
+ *   scales uint8 [M][K / 32], e8m0: the block's elements are multiplied by 2^(byte - 127).
+ * Quantisation of a block of 32 finite values v (deterministic, integer arithmetic like the two rules above):
+ * amax = max|v|; amax == 0 gives scale byte 127 and codes 0; otherwise e = clamp(floor(log2(amax)) - 8, -127, 127),
+ * scale byte e + 127 (255 is never produced; 8 is the exponent of 448, so the largest element lands in [256, 512)), and
+ * each code is the E4M3 rule above applied to v * 2^-e (exact): nearest, ties to even, saturating at 448; the sign bit
+ * is v's. NaN and Inf inputs are out of contract.
+ *
+ * sli_quant_mxfp8: device fp32 [rows][cols] -> codes, scales (src 16-byte, codes 4-byte aligned).
+ * sli_dequant_mxfp8: the inverse, fp32 [rows][cols] (exact). cols % 32 != 0: SLI_ERR_SHAPE. */
+int sli_quant_mxfp8(const float* src, void* codes, void* scales, int32_t rows, int32_t cols, sli_stream_t stream);
+int sli_dequant_mxfp8(const void* codes, const void* scales, float* dst, int32_t rows, int32_t cols,
+                      sli_stream_t stream);
+
 /* Batched projection for B sequences decoding in lockstep (the reference is batch 1; this serves
  * SURVEY.md §8 config C4): y[b][r] = sum_c x[b][c] * W[r][c] for b < batch <= 8, on MFMA
  * (v_mfma_f32_16x16x32_f16; the fp32 input is carried as fp16 hi + lo columns). x [batch][cols] fp32, W
@@ -400,7 +416,14 @@ int sli_model_prefill_path(const sli_model* m);
  * chunk attention reads the codes; under the other three modes an FP8-cache model keeps the decode step, and
  * SLI_PREFILL_GEMM its refusal). May be changed between prefills; sli_model_prefill_path reports the outcome. The
  * ranks of an in-process group are set through sli_tp_group_set_prefill. */
-enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2, SLI_PREFILL_GEMM_KV8 = 3 };
+/* SLI_PREFILL_GEMM_MX8: the chunked prefill with every GEMM on the block-scaled MFMA (sli_prefill_gemm_mx8) and the
+ * activations quantised to MXFP8 ahead of each (norm-quant -> q/k/v -> attention -> quant -> wo -> norm-quant -> gate/up
+ * -> quant -> down): a numerical mode of its own, opt-in. Accepted by single-rank batch-1 MXFP4 models with an fp16 or
+ * FP8 K/V cache, head_dim 64 / 128 and projection depths on 128; SLI_ERR_STATE with the reason otherwise (fp16 / int8 /
+ * fp32 weights, tensor parallelism, batch > 1, an fp32 cache, a depth off 128). It steers the one-sequence driver
+ * (sli_model_prefill, sli_model_predict_prefill, sli_model_extend); the packed routes ignore it as they ignore every
+ * mode; sli_model_prefill_path reports 1. Its chunk graphs are cached apart from SLI_PREFILL_GEMM's. */
+enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2, SLI_PREFILL_GEMM_KV8 = 3, SLI_PREFILL_GEMM_MX8 = 4 };
 int sli_model_set_prefill(sli_model* m, int32_t mode);
 /* 1: the batch-1 decode step runs each layer's q/k/v projection and attention as ONE launch (qkv_attn.h: the
  * attention's K/V rows below the position stream while the projection runs; q and this step's K/V row are
@@ -755,6 +778,27 @@ int sli_prefill_gemm(const void* w, int w_dtype, const float* w_row_scale, const
 int sli_prefill_gemm_mxfp4(const void* data, const void* scales, const void* hi, const void* lo, int32_t N, int32_t K,
                            int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
                            sli_pgemm_tiling* tiling, sli_stream_t stream);
+
+/* The MXFP4 prefill GEMM on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4; csrc/pgemm_mx8.h), a numerical
+ * mode of its own: the activations are MXFP8 images (the rule at sli_quant_mxfp8), not hi / lo pairs.
+ * sli_prefill_norm_quant_mx8: x [M][D] fp32 -> codes [M][D], scales [M][D / 32] of h = RMSNorm(x row) * w (w NULL:
+ *   h = x); the norm is sli_prefill_norm_split's, sum for sum. D % 32 == 0, with w D <= 8192, M >= 1.
+ * sli_prefill_quant_mx8: the same image of h = hi + lo (one fp32 add) from an fp16 pair [M][D], as the chunk
+ *   attention and the SwiGLU epilogue write it. D % 32 == 0, any D.
+ * sli_prefill_gemm_mx8: one pgemm_mx8_kernel launch: sums[m][r] = sum over 32-k blocks of (sum_k w[r][k] a[m][k])
+ *   2^(scale byte of w - 127) 2^(scale byte of a - 127), block products and sum inside the MFMA, fp32 accumulation
+ *   across issues of 128 k, then the epilogue of sli_prefill_gemm_mxfp4 (no row scale). data / scales: MXFP4 weights in
+ *   the public layout; acodes / ascales: the MXFP8 image [M][K]. The checks of sli_prefill_gemm_mxfp4, and K % 128 == 0
+ *   (SLI_ERR_SHAPE otherwise); scales and ascales are 4-byte aligned (a row's four bytes of a stage travel as one
+ *   dword). *tiling: BM, WR, S, AT as there (a workgroup owns 16 * AT * WR weight rows x BM chunk rows, S stages in
+ *   the ring), PIPE 1, SA 0, KS 128. */
+int sli_prefill_norm_quant_mx8(const float* x, const float* w, void* codes, void* scales, int32_t M, int32_t D, float eps,
+                               sli_stream_t stream);
+int sli_prefill_quant_mx8(const void* hi, const void* lo, void* codes, void* scales, int32_t M, int32_t D,
+                          sli_stream_t stream);
+int sli_prefill_gemm_mx8(const void* data, const void* scales, const void* acodes, const void* ascales, int32_t N,
+                         int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                         sli_pgemm_tiling* tiling, sli_stream_t stream);
 
 /* Block-causal attention of M chunk rows (32, 64, 128 or 256): row m of head h attends the cache rows 0 .. p0 + m
  * of kv head h / (hq / hkv); q [rows][hq * hd] fp32, kc / vc one layer's cache [hkv][T][hd] in kv_dtype, the result

@@ -59,6 +59,19 @@ __device__ __forceinline__ void lm_dma_u8(const void* gsrc, unsigned lds) {
         : "v"(gsrc), "s"(lds)
         : "memory");
 }
+// LDS-DMA of 64 dwords: lane i's dword at gsrc (4-byte aligned) lands at LDS byte lds + 4 i
+__device__ __forceinline__ void lm_dma_u32(const void* gsrc, unsigned lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dword %1, off\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(gsrc), "s"(lds)
+        : "memory");
+}
 // at most N of this wave's vector-memory loads (DMA pieces) still in flight; vmcnt is 6 bits, N <= 63
 template <int N>
 __device__ __forceinline__ void lm_wait_vm() {

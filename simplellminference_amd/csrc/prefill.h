@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(256) pf_embed_kernel(const PfSegs* __restrict_
 
 // one workgroup per chunk row: h = (x * 1/rms) * w (rms_kernel.cpp:12-22) or plain x (w == nullptr), as hi/lo.
 // The row is held in registers (a float4 per thread and pass; D % 4 == 0, D <= 8192): one read of x, 8-byte
-// hi / lo stores.
-__global__ void __launch_bounds__(256) pf_norm_split_kernel(const float* __restrict__ x, const float* __restrict__ w,
+// hi / lo stores. (static: prefill.h is included by more than one translation unit.)
+static __global__ void __launch_bounds__(256) pf_norm_split_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            __half* __restrict__ hi, __half* __restrict__ lo, int D,
                                                            float eps) {
     constexpr int MAXV = 8;  // float4 per thread: D <= 8192

@@ -364,6 +364,117 @@ def prefill_gemm_logits(w, hi, lo, y, row_scale=None, scales=None):
     return _prefill_gemm(w, row_scale, hi, lo, 0, hi.shape[0], e, scales)
 
 
+# ---- the MXFP8 activation format and the block-scaled MFMA prefill GEMM (csrc/pgemm_mx8.h)
+def _mx8_image(M, D, device):
+    if D % 32:
+        raise ValueError("Tensor with Wrong Dim!")
+    return (torch.empty(M, D, device=device, dtype=torch.uint8),
+            torch.empty(M, D // 32, device=device, dtype=torch.uint8))
+
+
+def quant_mxfp8(x):
+    """fp32 [rows, cols] -> (codes uint8 [rows, cols] E4M3, scales uint8 [rows, cols/32] e8m0), the rule of sli.h."""
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError("quant_mxfp8 takes fp32 [rows, cols]")
+    codes, scales = _mx8_image(*x.shape, x.device)
+    _dev(x)
+    call("sli_quant_mxfp8", _p(x), _p(codes), _p(scales), x.shape[0], x.shape[1], _s())
+    return codes, scales
+
+
+def dequant_mxfp8(codes, scales, out=None):
+    """(codes, scales) -> fp32 [rows, cols], exact."""
+    rows, cols = codes.shape
+    if scales.shape != (rows, cols // 32) or cols % 32:
+        raise ValueError("Tensor with Wrong Dim!")
+    out = torch.empty(rows, cols, device=codes.device, dtype=torch.float32) if out is None else out
+    _dev(codes, scales, out)
+    call("sli_dequant_mxfp8", _p(codes), _p(scales), _p(out), rows, cols, _s())
+    return out
+
+
+def prefill_norm_quant_mx8(x, w, eps: float):
+    """pf_quant_mx8_kernel from fp32: x [M, D] -> the MXFP8 image of RMSNorm(x) * w (w None: of x itself)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or (w is not None and (w.dtype != torch.float32 or w.shape != x.shape[1:])):
+        raise ValueError("prefill_norm_quant_mx8 takes fp32 x [M, D] and w [D]")
+    codes, scales = _mx8_image(*x.shape, x.device)
+    _dev(x, w)
+    call("sli_prefill_norm_quant_mx8", _p(x), _p(w), _p(codes), _p(scales), x.shape[0], x.shape[1], eps, _s())
+    return codes, scales
+
+
+def prefill_quant_mx8(hi, lo):
+    """pf_quant_mx8_kernel from an fp16 hi / lo pair [M, D]: the MXFP8 image of hi + lo."""
+    if hi.shape != lo.shape or hi.dtype != torch.float16 or lo.dtype != torch.float16:
+        raise ValueError("Tensor with Wrong Dim!")
+    codes, scales = _mx8_image(*hi.shape, hi.device)
+    _dev(hi, lo)
+    call("sli_prefill_quant_mx8", _p(hi), _p(lo), _p(codes), _p(scales), hi.shape[0], hi.shape[1], _s())
+    return codes, scales
+
+
+def _prefill_gemm_mx8(w, scales, acodes, ascales, p0, nv, epi):
+    """sli_prefill_gemm_mx8: w uint8 [N, K/2] and scales uint8 [N, K/32] (MXFP4), acodes uint8 [M, K] and ascales
+    uint8 [M, K/32] (MXFP8). Returns the tiling that ran."""
+    N, K = w.shape[0], w.shape[1] * 2
+    M = acodes.shape[0]
+    if any(t.dtype != torch.uint8 for t in (w, scales, acodes, ascales)) or K % 32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if scales.shape != (N, K // 32) or acodes.shape != (M, K) or ascales.shape != (M, K // 32):
+        raise ValueError("Tensor with Wrong Dim!")
+    state = _pf_table(w.device)
+    _dev(w, scales, acodes, ascales)
+    tl = _lib.PgemmTiling()
+    call("sli_prefill_gemm_mx8", _p(w), _p(scales), _p(acodes), _p(ascales), N, K, M, p0, nv, ctypes.byref(epi),
+         _p(state), ctypes.byref(tl), _s())
+    return {n: getattr(tl, n) for n, _ in tl._fields_}
+
+
+def prefill_gemm_qkv_mx8(w, scales, acodes, ascales, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, p0: int,
+                         nv: int, kv_dtype=None):
+    """prefill_gemm_qkv on the block-scaled MFMA: MXFP4 W, MXFP8 activations; the same epilogue operands."""
+    if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[1]
+    if q.shape != (acodes.shape[0], hq * hd) or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, sin_t, cos_t)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_kv_dt(kc, kv_dtype), sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
+                           hd=hd, T=T)
+    return _prefill_gemm_mx8(w, scales, acodes, ascales, p0, nv, e)
+
+
+def prefill_gemm_gate_up_mx8(w, scales, acodes, ascales, ahi, alo, act_mode: int = 0):
+    """prefill_gemm_gate_up on the block-scaled MFMA: W [2 inter, K] = [gate; up]; ahi / alo [M, inter] fp16."""
+    inter = w.shape[0] // 2
+    if ahi.shape != (acodes.shape[0], inter) or alo.shape != ahi.shape:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(ahi, alo)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_GATE_UP, ahi=ahi.data_ptr(), alo=alo.data_ptr(), inter=inter,
+                           act_mode=act_mode)
+    return _prefill_gemm_mx8(w, scales, acodes, ascales, 0, acodes.shape[0], e)
+
+
+def prefill_gemm_resid_mx8(w, scales, acodes, ascales, y, resid=None):
+    """prefill_gemm_resid on the block-scaled MFMA: y [M, ld] = (resid or 0) + the sums."""
+    if y.shape[0] != acodes.shape[0] or (resid is not None and resid.shape != y.shape):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_RESID, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                           ld=y.shape[1])
+    return _prefill_gemm_mx8(w, scales, acodes, ascales, 0, acodes.shape[0], e)
+
+
+def prefill_gemm_logits_mx8(w, scales, acodes, ascales, y):
+    """prefill_gemm_logits on the block-scaled MFMA: y [M, ld][:, :N] for W's N >= 16 rows (any N)."""
+    if y.shape[0] != acodes.shape[0]:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_LOGITS, y=y.data_ptr(), ld=y.shape[1])
+    return _prefill_gemm_mx8(w, scales, acodes, ascales, 0, acodes.shape[0], e)
+
+
 def score_rows(logits, targets, want_top: bool = True):
     """sli_score_rows: per row of fp32 logits [M, V] (rows ``logits.stride(0)`` floats apart: a row-padded view is
     taken as it is) and int32 target, the target's log-probability, the first-max token and its log-probability (the

@@ -9,7 +9,8 @@ does not judge the formats' quality. The JSON carries that note ("synthetic": tr
 
     python tools/quant_quality.py [--layers 2] [--batch 4] [--tokens 256] [--flat PATH --preset llama2-7b] [--out ...]
 
-Writes profiles/quant_quality.json.
+Writes profiles/quant_quality.json. --mx8: MXFP4 against MXFP4 + MXFP8 activations (set_prefill("gemm-mx8")) instead,
+through the one-sequence driver (one_sequence below), to profiles/quant_quality_mx8.json; the same caveat.
 """
 import argparse
 import json
@@ -29,8 +30,36 @@ def _ids(n, b, vocab):
     return [(1 + 7919 * i + 104729 * b) % vocab for i in range(n)]
 
 
+def one_sequence(a, cfg, np, LlamaModel):
+    """MXFP4 against MXFP4 + MXFP8 activations (set_prefill("gemm-mx8")). The scoring route above is the packed one,
+    which ignores the prefill mode, so this leg goes through the one-sequence driver: per prompt prefix one
+    predict_prefill, whose first logits row after the prefix gives the next token's log-probability and the top-1."""
+    runs = (("fp16", "f16", "gemm"), ("mxfp4", "mxfp4", "gemm"), ("mxfp4+mxfp8", "mxfp4", "gemm-mx8"))
+    prompts = [_ids(a.tokens, b, cfg.vocab_size) for b in range(a.batch)]
+    cuts = range(16, a.tokens, max(1, a.tokens // 32))
+    res = {}
+    for name, w, mode in runs:
+        m = LlamaModel(config=cfg, model_path=a.flat, w_dtype=w, kv_dtype="f16", seed=None if a.flat else a.seed).init()
+        m.set_prefill(mode)
+        lp, top = [], []
+        for p in prompts:
+            for n in cuts:
+                m.reset()
+                row = m.predict_prefill(p[:n], n + 1, want_logits=True)[1][n - 1].astype(np.float64)
+                row -= row.max()
+                lp.append(row[p[n]] - math.log(np.exp(row).sum()))
+                top.append(int(row.argmax()))
+        m.close()
+        res[name] = (np.array(lp), np.array(top))
+    base_lp, base_top = res["fp16"]
+    return [{"format": name, "mean_nll": float(-lp.mean()), "mean_abs_dlogprob_vs_fp16": float(np.abs(lp - base_lp).mean()),
+             "top1_agreement_vs_fp16": float((top == base_top).mean()), "scored_positions": int(lp.size)}
+            for name, (lp, top) in res.items()]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mx8", action="store_true", help="only the one-sequence leg: fp16, mxfp4, mxfp4 + MXFP8 activations")
     ap.add_argument("--preset", default="llama2-7b")
     ap.add_argument("--layers", type=int, default=2, help="layers of the synthetic model (ignored with --flat)")
     ap.add_argument("--batch", type=int, default=4)
@@ -44,6 +73,18 @@ def main():
     from simplellminference_amd.model import LlamaModel, preset
     over = dict(max_length=a.ctx) if a.flat else dict(max_length=a.ctx, num_hidden_layers=a.layers)
     cfg = preset(a.preset, **over)
+    if a.mx8:
+        out = {"model": a.preset, "layers": cfg.num_hidden_layers, "weights": a.flat or f"synthetic seed {a.seed}",
+               "synthetic": not a.flat, "ln_vocab": math.log(cfg.vocab_size), "one_sequence": one_sequence(a, cfg, np, LlamaModel)}
+        if not a.flat:
+            out["note"] = NOTE
+            print("NOTE: " + NOTE)
+        for r in out["one_sequence"]:
+            print(f"{r['format']:<12} {r['mean_nll']:>10.5f} {r['mean_abs_dlogprob_vs_fp16']:>10.2e} {r['top1_agreement_vs_fp16']:>12.4f}")
+        with open(a.out.replace("quant_quality.json", "quant_quality_mx8.json"), "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        return
     prompts = [_ids(a.tokens, b, cfg.vocab_size) for b in range(a.batch)]
     res = {}
     for name, w, kv in FORMATS:
