@@ -571,6 +571,23 @@ int sli_model_get_history(sli_model* m, int32_t seq, int32_t n, int32_t* out);
 enum { SLI_EXEC_LAUNCHES = 0, SLI_EXEC_PERSIST = 2 };
 int sli_model_set_exec(sli_model* m, int32_t mode);
 int sli_model_get_exec(sli_model* m, int32_t* mode);
+/* The projections of the batched decode step. SLI_DECODE_AUTO (the default): bgemm_kernel, as before. SLI_DECODE_MX8:
+ * the five projection launches of the step (q/k/v, wo, gate/up, down, LM head) run sli_batch_gemm_mx8's kernel, FP4
+ * weights times MXFP8 activations on the block-scaled MFMA; it is the decode half of SLI_PREFILL_GEMM_MX8 and, like
+ * it, a numerical mode of its own, so it is opt-in. Everything else in the step (embedding, attention, samplers, key
+ * reduce, stop launch, state update) is untouched, and so are the prefill, score and extend routes, which ignore the
+ * mode. Taken by a single-rank SLI_DT_MXFP4 model created with SLI_CREATE_MX_BATCH at batch 2 .. 8 whose projection
+ * depths (dim, q width, ffn) are multiples of 128, with any cache type, under SLI_EXEC_LAUNCHES; SLI_ERR_STATE with
+ * the reason otherwise: other weight types, batch 1 (its step is the GEMV recorder), tp_size > 1, the ranks of an
+ * in-process group, SLI_EXEC_PERSIST, a depth off 128, and a projection for which no plan fits the 160 KiB of LDS (the LM
+ * head's plan is held to the model's argmax key slots, one per workgroup group). An unknown mode (checked first) or a
+ * null model is SLI_ERR_ARG. Changing the
+ * mode re-lays the model's fragment-layout weight images in place from the public-layout weights it keeps (no second
+ * copy; the two modes' images have the same byte sizes) and drops the captured step, which the next step re-captures;
+ * back under SLI_DECODE_AUTO the step is the earlier one bit for bit. sli_model_decode_path: the mode in force. */
+enum { SLI_DECODE_AUTO = 0, SLI_DECODE_MX8 = 1 };
+int sli_model_set_decode(sli_model* m, int32_t mode);
+int sli_model_decode_path(sli_model* m);
 /* Sampling inside the step (the rule at sli_sample). p == NULL or p->temperature == 0: greedy, the default and the
  * reference's behaviour. Otherwise every step draws one token per sequence from its logits, as sequence b (the row
  * of the batch) at the position of the token just fed, between the LM head and the key reduce; past the prompt the
@@ -930,6 +947,43 @@ size_t sli_batch_gemm_mxfp4_workspace_bytes(int32_t rows, int32_t K, int32_t B, 
 int sli_batch_gemm_mxfp4(const float* x, const float* norm_w, float eps, const void* data, const void* scales,
                          int32_t tiled, int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan,
                          void* workspace, size_t workspace_bytes, sli_stream_t stream);
+
+/* sli_batch_gemm_mxfp4 on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4; csrc/bgemm_mx8.h): the same
+ * MXFP4 matrix, the same epilogue descriptor, roles and norm pairing, but the activations enter the MFMA as OCP MXFP8
+ * (e4m3 codes, one e8m0 scale per 32 consecutive k), quantised by the launch while it stages them, so this is a
+ * numerical mode of its own (sli_model_set_decode(SLI_DECODE_MX8) runs it in a model). The staging rule: a block is 32
+ * consecutive k of one sequence; its scale and codes are sli_quant_mxfp8's, word for word, of h[b][k] = x[b][k]
+ * (store) or the fp32 product x[b][k] * norm_w[k] (the roles with a norm). The per-sequence 1 / sqrt(mean(x^2) + eps)
+ * multiplies the finished sum, exactly where sli_batch_gemm applies it, so the codes do not depend on the rms. (This
+ * differs on purpose from sli_prefill_norm_quant_mx8, which normalises first and quantises (x * inv) * w.) Each
+ * 128-k issue adds sum_k code(W) 2^(ws - 127) code(h) 2^(hs - 127) into an fp32 tile; the partial tiles of the k-slices
+ * and splits are added in fp32 in a fixed order.
+ *
+ * The plan, in / out: a workgroup owns tpw consecutive 16-row tiles and one of `splits` ranges of 128-k stages; its 16
+ * waves are wt tiles in flight x wk k-slices of the range. tpw == 0 asks the planner (bg_mx8_plan: what a model of this
+ * shape runs); tpw != 0 forces (tpw, splits, wt, wk), which must satisfy wt * wk == 16 (powers of two), splits == 1 with
+ * a norm, splits <= K / 128, and the LDS image 1 KiB + ceil(K / 128 / splits) * 1056 B + (wk > 1: 16 KiB) + tpw / 2 KiB
+ * within 160 KiB. On return every field holds what ran.
+ * Refused as SLI_ERR_SHAPE before the device is touched: K % 128 != 0, B outside [1, 8], (hq + 2 hkv) hd % 16 != 0,
+ * inter % 8 != 0; everything else sli_batch_gemm refuses is SLI_ERR_ARG here too. tiled != 0: the call first re-lays
+ * data and scales into the mode's images inside the workspace (per (tile, 128-k stage) one KiB of data, lane l's 16
+ * bytes at l * 16, and 64 scale bytes, lane l's at l; the byte sizes of sli_batch_gemm_mxfp4's images) and streams
+ * those, as a model in the mode does. The workspace function needs no device. */
+typedef struct {
+    int32_t tpw, splits, wt, wk, groups, lds_bytes;
+    int64_t counter_off;
+} sli_bgemm_mx8_plan;
+size_t sli_batch_gemm_mx8_workspace_bytes(int32_t rows, int32_t K, int32_t B, int32_t norm, int32_t tiled,
+                                          sli_bgemm_mx8_plan* plan);
+int sli_batch_gemm_mx8(const float* x, const float* norm_w, float eps, const void* data, const void* scales, int32_t tiled,
+                       int32_t K, int32_t B, const sli_bgemm_epilogue* epi, sli_bgemm_mx8_plan* plan, void* workspace,
+                       size_t workspace_bytes, sli_stream_t stream);
+/* The plain-rows form (sli_matmul_batch_mxfp4's arguments): y[b][r] = sum_k W[r][k] * mxfp8(x[b])[k], the store role with
+ * no residual, the planner's plan, the counters zeroed by the call. cols % 128 == 0, 1 <= batch <= 8, else SLI_ERR_SHAPE
+ * (the workspace function returns 0). */
+size_t sli_matmul_batch_mx8_workspace_bytes(int32_t rows, int32_t cols, int32_t batch, int32_t tiled);
+int sli_matmul_batch_mx8(const float* x, const void* data, const void* scales, float* y, int32_t rows, int32_t cols,
+                         int32_t batch, int32_t tiled, void* workspace, size_t workspace_bytes, sli_stream_t stream);
 
 /* ---------------------------------------------------------------- decode stages, for tests and labs
  * One GEMV launch of the batch-1 decode step (csrc/gemv.h), without a model or a workspace (the GEMVs keep no

@@ -87,6 +87,10 @@ class BgemmPlan(ctypes.Structure):  # sli_bgemm_plan
     _fields_ = [(n, c_i32) for n in ("tpw", "splits", "groups", "step_width", "lds_bytes")] + [("counter_off", c_i64)]
 
 
+class BgemmMx8Plan(ctypes.Structure):  # sli_bgemm_mx8_plan
+    _fields_ = [(n, c_i32) for n in ("tpw", "splits", "wt", "wk", "groups", "lds_bytes")] + [("counter_off", c_i64)]
+
+
 class GemvEpilogue(ctypes.Structure):  # sli_gemv_epilogue
     _fields_ = [("role", c_i32),
                 ("parts", c_vp), ("np", c_i32),
@@ -235,6 +239,13 @@ _SIGS = {
     "sli_batch_gemm_mxfp4_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmPlan)]),
     "sli_batch_gemm_mxfp4": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
                                      ctypes.POINTER(BgemmPlan), c_vp, c_sz, c_vp]),
+    "sli_batch_gemm_mx8_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmMx8Plan)]),
+    "sli_batch_gemm_mx8": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.POINTER(BgemmEpilogue),
+                                   ctypes.POINTER(BgemmMx8Plan), c_vp, c_sz, c_vp]),
+    "sli_matmul_batch_mx8_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "sli_matmul_batch_mx8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "sli_model_set_decode": (c_int, [c_vp, c_i32]),
+    "sli_model_decode_path": (c_int, [c_vp]),
     "sli_decode_gemv_plan": (c_int, [c_int, c_i32, c_i32, ctypes.POINTER(GemvEpilogue), ctypes.POINTER(GemvPlan)]),
     "sli_decode_gemv": (c_int, [c_vp, c_vp, c_f, c_vp, c_int, c_vp, c_i32, ctypes.POINTER(GemvEpilogue),
                                 ctypes.POINTER(GemvPlan), c_vp]),
@@ -297,6 +308,9 @@ def call(name: str, *args) -> int:
                                                  "sli_matmul_batch_i8_workspace_bytes",
                                                  "sli_batch_gemm_workspace_bytes",
                                                  "sli_matmul_batch_mxfp4_workspace_bytes",
-                                                 "sli_batch_gemm_mxfp4_workspace_bytes"):
+                                                 "sli_batch_gemm_mxfp4_workspace_bytes",
+                                                 "sli_batch_gemm_mx8_workspace_bytes",
+                                                 "sli_matmul_batch_mx8_workspace_bytes",
+                                                 "sli_model_decode_path"):
         check(rc, name)
     return rc

@@ -154,19 +154,10 @@ size_t sli_batch_gemm_workspace_bytes(int32_t rows, int32_t K, int32_t B, int32_
 
 }  // extern "C"
 
-// sli_batch_gemm and sli_batch_gemm_mxfp4 (fn: the entry's name in messages; mx_scales: the block scales of an
-// SLI_DT_MXFP4 matrix, null for the other weight types): one contract, one body
-static int bgo_entry(const std::string& fn, const float* x, const float* norm_w, float eps, const void* w, int w_dtype,
-                     const float* w_row_scale, const void* mx_scales, int32_t tiled, int32_t K, int32_t B,
-                     const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan, void* workspace, size_t workspace_bytes,
-                     sli_stream_t stream) {
-    const bool mx = w_dtype == SLI_DT_MXFP4;
-    SLI_CHECK(x && w && epi && plan && workspace && (!mx || mx_scales), SLI_ERR_ARG, fn + ": null pointer");
-    SLI_CHECK(bgo_al16(x) && bgo_al16(norm_w) && bgo_al16(w) && bgo_al16(w_row_scale) && bgo_al16(mx_scales) &&
-                  bgo_al16(workspace),
-              SLI_ERR_ARG, fn + ": 16-byte alignment");
-    const sli_bgemm_epilogue& e = *epi;
-    const bool norm = norm_w != nullptr;
+namespace sli {
+// what every entry checks of an epilogue descriptor and its norm pairing (declared in mx8_api.h: sli_batch_gemm_mx8
+// shares it)
+int bgo_check_epilogue(const std::string& fn, const sli_bgemm_epilogue& e, bool norm) {
     switch (e.role) {
         case SLI_BG_QKV:
             SLI_CHECK(norm, SLI_ERR_ARG, fn + ": the q/k/v launch has the fused RMSNorm (norm_w)");
@@ -207,6 +198,25 @@ static int bgo_entry(const std::string& fn, const float* x, const float* norm_w,
             break;
         default: return fail(SLI_ERR_ARG, fn + ": role must be 0 (q/k/v), 1 (gate/up), 2 (store) or 3 (logits)");
     }
+    return SLI_OK;
+}
+int64_t bgo_epilogue_rows(const sli_bgemm_epilogue& e) { return bgo_rows(e); }
+}  // namespace sli
+
+// sli_batch_gemm and sli_batch_gemm_mxfp4 (fn: the entry's name in messages; mx_scales: the block scales of an
+// SLI_DT_MXFP4 matrix, null for the other weight types): one contract, one body
+static int bgo_entry(const std::string& fn, const float* x, const float* norm_w, float eps, const void* w, int w_dtype,
+                     const float* w_row_scale, const void* mx_scales, int32_t tiled, int32_t K, int32_t B,
+                     const sli_bgemm_epilogue* epi, sli_bgemm_plan* plan, void* workspace, size_t workspace_bytes,
+                     sli_stream_t stream) {
+    const bool mx = w_dtype == SLI_DT_MXFP4;
+    SLI_CHECK(x && w && epi && plan && workspace && (!mx || mx_scales), SLI_ERR_ARG, fn + ": null pointer");
+    SLI_CHECK(bgo_al16(x) && bgo_al16(norm_w) && bgo_al16(w) && bgo_al16(w_row_scale) && bgo_al16(mx_scales) &&
+                  bgo_al16(workspace),
+              SLI_ERR_ARG, fn + ": 16-byte alignment");
+    const sli_bgemm_epilogue& e = *epi;
+    const bool norm = norm_w != nullptr;
+    if (int rc = bgo_check_epilogue(fn, e, norm)) return rc;
     const int64_t rows = bgo_rows(e);
     SLI_CHECK(rows >= 1 && rows <= 0x7FFFFFF0, SLI_ERR_ARG, fn + ": bad row count");
     BgPlan p;

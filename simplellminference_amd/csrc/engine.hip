@@ -110,6 +110,12 @@ struct sli_model {
     unsigned* bg_cnt = nullptr;           // their arrival counters (zero between launches)
     unsigned long long* bkeys = nullptr;  // [B] per-sequence argmax keys (all-reduced MAX under TP)
     int key_ld = 0;                       // per-sequence stride of the per-workgroup argmax keys
+    // sli_model_set_decode(SLI_DECODE_MX8): the projections on the block-scaled MFMA (bgemm_mx8.h), their plans and
+    // their own split workspace; the weight images are then in that kernel's layout (bg_build_tiles_mx8)
+    int decode = SLI_DECODE_AUTO;
+    sli::Bg8Plan b8_qkv, b8_wo, b8_gu, b8_down, b8_lm;
+    float* b8_ws = nullptr;
+    unsigned* b8_cnt = nullptr;
     // prompt prefill (sli_model_prefill, prefill.h): chunks of up to kPfMaxChunk prompt positions through
     // every layer per weight pass; one captured graph per chunk size (kPfSizes)
     struct Prefill {
@@ -953,7 +959,26 @@ struct StepRecorder {
     // layout, else the *_s scales in the public layout)
     static constexpr bool kBgWT = std::is_same<WT, __half>::value || std::is_same<WT, int8_t>::value || MX;
     template <class Epi>
-    static int bg(sli_model* m, const void* W, const void* ws, const BgIn& in_, const Epi& e, const BgPlan& p) {
+    // p: the launch's bgemm.h plan; q: its bgemm_mx8.h plan, which SLI_DECODE_MX8 runs instead
+    static int bg(sli_model* m, const void* W, const void* ws, const BgIn& in_, const Epi& e, const BgPlan& p, const Bg8Plan& q) {
+        if (m->decode == SLI_DECODE_MX8) {  // sli_model_set_decode: the same launch on the block-scaled MFMA
+            if constexpr (MX && !std::is_same<Epi, BgEpiPush>::value) {
+                Bg8In in{};
+                in.x = in_.x;
+                in.norm_w = in_.norm_w;
+                in.eps = in_.eps;
+                in.K = in_.K;
+                in.B = in_.B;
+                in.ws = m->b8_ws;
+                in.counters = m->b8_cnt;
+                in.tiled = in_.tiled;
+                in.w = (const uint8_t*)W;
+                in.wscale = (const uint8_t*)ws;
+                return mx8_bgemm(in, e, q, m->stream);
+            } else {
+                return fail(SLI_ERR_STATE, "SLI_DECODE_MX8 runs single-rank MXFP4 models");
+            }
+        }
         if constexpr (kBgWT) {
             BgIn in = in_;
             if (MX) in.wscale = (const uint8_t*)ws;
@@ -998,7 +1023,7 @@ struct StepRecorder {
         BgEpiQKV<KT> e{m->q, (KT*)m->kc + lay, (KT*)m->vc + lay, &m->st->pos, kPosStride, m->sin_t, m->cos_t,
                        m->hq, m->hkv, m->hd, m->T};
         e.rscale = rs(m->layers[l].qkv_s);
-        return bg(m, m->bg_tiled ? m->layers[l].qkv_t : m->layers[l].qkv, bsc(m, m->layers[l].qkv_ts, m->layers[l].qkv_s), bin(m, m->x, m->norms + (size_t)(2 * l) * m->D, m->D), e, m->bp_qkv);
+        return bg(m, m->bg_tiled ? m->layers[l].qkv_t : m->layers[l].qkv, bsc(m, m->layers[l].qkv_ts, m->layers[l].qkv_s), bin(m, m->x, m->norms + (size_t)(2 * l) * m->D, m->D), e, m->bp_qkv, m->b8_qkv);
     }
     // batched wo / down with the exchange per group (oneshot.h BgEpiPush; region 3: wo, 4: down)
     static BgEpiPush push_bg(sli_model* m, int region, const BgPlan& p, const float* rscale) {
@@ -1028,28 +1053,28 @@ struct StepRecorder {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].wo_t : m->layers[l].wo;
         const void* ws = bsc(m, m->layers[l].wo_ts, m->layers[l].wo_s);
-        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo, m->layers[l].wo_s), m->bp_wo);
+        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), push_bg(m, 3, m->bp_wo, m->layers[l].wo_s), m->bp_wo, m->b8_wo);
         BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].wo_s), 1.0f, m->D, m->D};
-        return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), e, m->bp_wo);
+        return bg(m, w, ws, bin(m, m->attn, nullptr, m->hq * m->hd), e, m->bp_wo, m->b8_wo);
     }
     static int b_gu(sli_model* m, int l) {
         BgEpiSwiGLU e{m->act, m->Il, m->c.act_mode, rs(m->layers[l].gu_s)};
-        return bg(m, m->bg_tiled ? m->layers[l].gu_t : m->layers[l].gu, bsc(m, m->layers[l].gu_ts, m->layers[l].gu_s), bin(m, m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->D), e, m->bp_gu);
+        return bg(m, m->bg_tiled ? m->layers[l].gu_t : m->layers[l].gu, bsc(m, m->layers[l].gu_ts, m->layers[l].gu_s), bin(m, m->x, m->norms + (size_t)(2 * l + 1) * m->D, m->D), e, m->bp_gu, m->b8_gu);
     }
     static int b_down(sli_model* m, int l) {
         const bool tp = m->partial;
         const void* w = m->bg_tiled ? m->layers[l].down_t : m->layers[l].down;
         const void* ws = bsc(m, m->layers[l].down_ts, m->layers[l].down_s);
-        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down, m->layers[l].down_s), m->bp_down);
+        if (fused_ar(m)) return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), push_bg(m, 4, m->bp_down, m->layers[l].down_s), m->bp_down, m->b8_down);
         BgEpiStore e{tp ? m->xpart : m->x, (!tp || m->c.tp_rank == 0) ? m->x : nullptr, rs(m->layers[l].down_s), 1.0f, m->D, m->D};
-        return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), e, m->bp_down);
+        return bg(m, w, ws, bin(m, m->act, nullptr, m->Il), e, m->bp_down, m->b8_down);
     }
     static int b_lm(sli_model* m) {
         BgEpiLogits e{m->logits, m->keys, m->v_n, m->v_n, m->v_lo, m->key_ld, m->emb_s && !MX ? m->emb_s + m->v_lo : nullptr};
         const void* w = m->bg_tiled ? m->lm_t : wptr(m->emb, m->wbytes, (size_t)m->v_lo * m->D);
         // (mxfp4 row-major: the block scales of table row v_lo on; sptr)
         const void* ws = bsc(m, m->lm_ts, sptr(m, m->emb_s, (size_t)m->v_lo, m->D));
-        return bg(m, w, ws, bin(m, m->x, m->norms + (size_t)(2 * m->L) * m->D, m->D), e, m->bp_lm);
+        return bg(m, w, ws, bin(m, m->x, m->norms + (size_t)(2 * m->L) * m->D, m->D), e, m->bp_lm, m->b8_lm);
     }
     // ---- one step = phases 0 .. 2L (model.cpp:48-139). Phase 2l: [embedding when l = 0,] qkv(l),
     // attention(l), wo(l); phase 2l+1: gate/up(l), down(l); phase 2L: LM head + first argmax stage.
@@ -1101,7 +1126,7 @@ struct StepRecorder {
             SLI_TRY(b_lm(m));
             SLI_TRY(record_sample(m));
             hipLaunchKernelGGL(keyreduce_batch_kernel, dim3(m->B), dim3(256), 0, s, m->keys, m->key_ld,
-                               m->bp_lm.groups, m->bkeys);
+                               m->decode == SLI_DECODE_MX8 ? m->b8_lm.groups : m->bp_lm.groups, m->bkeys);
             SLI_HIP(hipGetLastError());
             return SLI_OK;
         }
@@ -1485,8 +1510,36 @@ static int bg_build_tiles(sli_model* m) {
     m->tiles_dirty = false;
     return SLI_OK;
 }
+// SLI_DECODE_MX8: the same allocations in bgemm_mx8.h's layout (a KiB of data and 64 scale bytes per tile and 128-k
+// stage: the byte sizes of bg_tiled_mx_bytes / bg_tiled_mx_scale_bytes), from the public-layout weights, by the same
+// row maps
+static int bg_build_tiles_mx8(sli_model* m) {
+    const int D = m->D, hd = m->hd, QD = m->hq * hd;
+    hipStream_t s = m->stream;
+    BgEpiQKV<__half> eq{};
+    eq.hq = m->hq;
+    eq.hkv = m->hkv;
+    eq.hd = hd;
+    BgEpiStore eo{};
+    eo.nrows = D;
+    BgEpiSwiGLU eg{};
+    eg.inter = m->Il;
+    BgEpiLogits el{};
+    el.nrows = m->v_n;
+    for (const LayerW& w : m->layers) {
+        SLI_TRY(mx8_bg_tile(w.qkv, mx_scales(w.qkv_s), D, m->bp_qkv.ntiles, eq, w.qkv_t, w.qkv_ts, s));
+        SLI_TRY(mx8_bg_tile(w.wo, mx_scales(w.wo_s), QD, m->bp_wo.ntiles, eo, w.wo_t, w.wo_ts, s));
+        SLI_TRY(mx8_bg_tile(w.gu, mx_scales(w.gu_s), D, m->bp_gu.ntiles, eg, w.gu_t, w.gu_ts, s));
+        SLI_TRY(mx8_bg_tile(w.down, mx_scales(w.down_s), m->Il, m->bp_down.ntiles, eo, w.down_t, w.down_ts, s));
+    }
+    SLI_TRY(mx8_bg_tile(wptr(m->emb, m->wbytes, (size_t)m->v_lo * D), mx_scales(sptr(m, m->emb_s, (size_t)m->v_lo, D)), D,
+                        m->bp_lm.ntiles, el, m->lm_t, m->lm_ts, s));
+    m->tiles_dirty = false;
+    return SLI_OK;
+}
 static int bg_sync_tiles(sli_model* m) {
     if (!m->bg_tiled || !m->tiles_dirty) return SLI_OK;
+    if (m->decode == SLI_DECODE_MX8) return bg_build_tiles_mx8(m);
     if (m->c.w_dtype == SLI_DT_MXFP4) return bg_build_tiles<mxfp4>(m);
     return m->c.w_dtype == SLI_DT_I8 ? bg_build_tiles<int8_t>(m) : bg_build_tiles<__half>(m);
 }
@@ -2846,6 +2899,56 @@ int sli_model_set_exec(sli_model* m, int32_t mode) {
     }
     return SLI_OK;
 }
+
+int sli_model_set_decode(sli_model* m, int32_t mode) {
+    SLI_CHECK(mode == SLI_DECODE_AUTO || mode == SLI_DECODE_MX8, SLI_ERR_ARG, "set_decode: unknown decode mode");
+    SLI_CHECK(m, SLI_ERR_ARG, "null model");
+    if (mode == SLI_DECODE_MX8) {
+        SLI_CHECK(m->exec != SLI_EXEC_PERSIST, SLI_ERR_STATE,
+                  "set_decode: SLI_DECODE_MX8 runs the launch graph, not the persistent layers (sli_model_set_exec(SLI_EXEC_LAUNCHES) first)");
+        SLI_CHECK(m->c.w_dtype == SLI_DT_MXFP4, SLI_ERR_STATE,
+                  "set_decode: SLI_DECODE_MX8 needs MXFP4 weights (the block-scaled MFMA multiplies FP4 codes)");
+        SLI_CHECK(!m->group, SLI_ERR_STATE, "set_decode: SLI_DECODE_MX8 is single-rank (not for the ranks of an in-process group)");
+        SLI_CHECK(m->c.tp_size <= 1 && !m->partial, SLI_ERR_STATE,
+                  "set_decode: SLI_DECODE_MX8 is single-rank (no tensor parallelism: tp_size > 1)");
+        SLI_CHECK(m->B >= 2, SLI_ERR_STATE,
+                  "set_decode: SLI_DECODE_MX8 is the batched step (batch 2 .. 8); batch 1 runs the GEMV recorder");
+        SLI_CHECK(m->D % kBg8Stage == 0 && m->Il % kBg8Stage == 0 && (m->hq * m->hd) % kBg8Stage == 0, SLI_ERR_STATE,
+                  "set_decode: SLI_DECODE_MX8 needs projection depths (dim, q width, ffn) that are multiples of 128 (one MFMA issue)");
+    }
+    if (mode == m->decode) return SLI_OK;
+    SLI_HIP(hipSetDevice(m->c.device));
+    if (mode == SLI_DECODE_MX8 && !m->b8_cnt) {  // first use: the plans, the LDS opt-in, the split workspace
+        const int cus = gemv_max_blocks(), D = m->D, B = m->B;
+        m->b8_qkv = bg_mx8_plan(m->bp_qkv.ntiles, D, B, true, cus);
+        m->b8_wo = bg_mx8_plan(m->bp_wo.ntiles, m->hq * m->hd, B, false, cus);
+        m->b8_gu = bg_mx8_plan(m->bp_gu.ntiles, D, B, true, cus);
+        m->b8_down = bg_mx8_plan(m->bp_down.ntiles, m->Il, B, false, cus);
+        m->b8_lm = bg_mx8_plan(m->bp_lm.ntiles, D, B, true, cus, m->key_ld);  // one argmax key slot per group
+        size_t part = 0;
+        int groups = 1;
+        for (const Bg8Plan* p : {&m->b8_qkv, &m->b8_wo, &m->b8_gu, &m->b8_down, &m->b8_lm}) {
+            SLI_CHECK(p->groups > 0, SLI_ERR_STATE, "set_decode: SLI_DECODE_MX8: no plan fits a projection of this model");
+            part = std::max(part, bg8_part_bytes(*p));
+            groups = std::max(groups, p->groups);
+        }
+        SLI_TRY(mx8_bgemm_prepare());
+        void *ws = nullptr, *cnt = nullptr;
+        SLI_HIP(hipMalloc(&ws, part + 256));
+        m->allocs.push_back(ws);
+        SLI_HIP(hipMalloc(&cnt, sizeof(unsigned) * groups));
+        m->allocs.push_back(cnt);
+        SLI_HIP(hipMemset(cnt, 0, sizeof(unsigned) * groups));
+        m->b8_ws = (float*)ws;
+        m->b8_cnt = (unsigned*)cnt;
+    }
+    SLI_TRY(drop_step_graph(m));  // (waits for the stream: nothing reads the images while they are re-laid)
+    m->decode = mode;
+    m->tiles_dirty = m->bg_tiled;  // the next capture re-lays the images in the mode's layout (bg_sync_tiles)
+    return SLI_OK;
+}
+
+int sli_model_decode_path(sli_model* m) { return m ? m->decode : SLI_DECODE_AUTO; }
 
 int sli_model_set_sampling(sli_model* m, const sli_sampling* p) {
     SLI_CHECK(m, SLI_ERR_ARG, "null model");

@@ -420,6 +420,16 @@ class LlamaModel:
         outcome."""
         call("sli_model_set_prefill", self._h, _PREFILL_MODES[mode])
 
+    def set_decode(self, mode: str) -> "LlamaModel":
+        """The projections of the batched decode step (sli_model_set_decode): 'auto' (the default) or 'mx8' (batched
+        MXFP4 models: FP4 weights times MXFP8 activations on the block-scaled MFMA, the decode half of prefill mode
+        'gemm-mx8'; a numerical mode of its own). Any other name goes to the C layer as an unknown mode."""
+        call("sli_model_set_decode", self._h, {"auto": 0, "mx8": 1}.get(mode, -1))
+        return self
+
+    def decode_path(self) -> str:
+        return "mx8" if _lib.load().sli_model_decode_path(self._h) == 1 else "auto"
+
     def fused_qkv_attn(self) -> int:
         """1 when the decode step runs q/k/v + attention as one launch per layer, 0 otherwise:
         sli_model_fused_qkv_attn."""

@@ -174,6 +174,25 @@ def matmul_batch_mxfp4(x, data, scales, tiled: bool = False, y=None):
     return y
 
 
+def matmul_batch_mx8(x, data, scales, tiled: bool = False, y=None):
+    """matmul_batch_mxfp4 on the block-scaled MFMA: y[b][r] = sum_c W[r][c] * mxfp8(x[b])[c], the activations quantised
+    to MXFP8 by the launch (sli_quant_mxfp8's rule per 32 columns). cols % 128 == 0, batch <= 8."""
+    batch, cols = x.shape
+    rows = data.shape[0]
+    if (data.dtype != torch.uint8 or scales.dtype != torch.uint8 or cols % 32 or data.shape != (rows, cols // 2)
+            or scales.shape != (rows, cols // 32)):
+        raise ValueError("Tensor with Wrong Dim!")
+    y = torch.empty(batch, rows, device=x.device, dtype=torch.float32) if y is None else y
+    nbytes = _lib.load().sli_matmul_batch_mx8_workspace_bytes(rows, cols, batch, int(tiled))
+    if nbytes == 0:
+        raise ValueError("unsupported batched shape (cols % 128 != 0 or batch > 8)")
+    ws = torch.empty(nbytes // 4 + 1, device=x.device, dtype=torch.float32)
+    _dev(x, data, scales, y, ws)
+    call("sli_matmul_batch_mx8", _p(x), _p(data), _p(scales), _p(y), rows, cols, batch, int(tiled), _p(ws),
+         ws.numel() * 4, _s())
+    return y
+
+
 def rmsnorm(x, w, eps: float, y=None):
     """rmsnorm_kernel_cuda (rms_kernel.cuh:6-7)."""
     y = torch.empty_like(x) if y is None else y
@@ -771,6 +790,103 @@ def batch_gemm_logits(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int
     e = _lib.BgemmEpilogue(role=BG_ROLE_LOGITS, logits=logits.data_ptr(), keys_out=keys_out.data_ptr(),
                            nrows=w.shape[0], ld=logits.shape[1], vocab_off=vocab_off, key_ld=keys_out.shape[1])
     return _batch_gemm(x, norm_w, eps, w, row_scale, tiled, e, w.shape[0], plan, ws, scales)
+
+
+# ---- the same launches on the block-scaled MFMA with MXFP8 activations (sli_batch_gemm_mx8, csrc/bgemm_mx8.h).
+# plan: None (the planner, bg_mx8_plan) or (tpw, splits, wt, wk) forced; the returned dict has those fields.
+def _mx8_plan(plan):
+    return _lib.BgemmMx8Plan(tpw=plan[0], splits=plan[1], wt=plan[2], wk=plan[3]) if plan else _lib.BgemmMx8Plan()
+
+
+def batch_gemm_mx8_plan(rows: int, K: int, B: int, norm: bool, tiled: bool = False, plan=None):
+    """The plan sli_batch_gemm_mx8 would run for a [rows, K] MXFP4 matrix and the workspace bytes it needs, without a
+    device. Returns (plan dict, bytes); bytes 0: refused."""
+    p = _mx8_plan(plan)
+    nbytes = call("sli_batch_gemm_mx8_workspace_bytes", rows, K, B, int(norm), int(tiled), ctypes.byref(p))
+    return {n: getattr(p, n) for n, _ in p._fields_}, nbytes
+
+
+def _batch_gemm_mx8(x, norm_w, eps, data, scales, tiled, epi, rows, plan, ws):
+    B, K = x.shape
+    if (K % 32 or data.dtype != torch.uint8 or scales.dtype != torch.uint8 or data.shape != (rows, K // 2)
+            or scales.shape != (rows, K // 32) or x.dtype != torch.float32):
+        raise ValueError("Tensor with Wrong Dim!")
+    if norm_w is not None and norm_w.numel() != K:
+        raise ValueError("Tensor with Wrong Dim!")
+    p, q = _mx8_plan(plan), _mx8_plan(plan)
+    nbytes = call("sli_batch_gemm_mx8_workspace_bytes", rows, K, B, int(norm_w is not None), int(tiled), ctypes.byref(q))
+    if nbytes == 0:
+        raise _lib.SliError(2, "sli_batch_gemm_mx8_workspace_bytes",
+                            (_lib.load().sli_last_error() or b"").decode())
+    if ws is None:
+        ws = torch.zeros(nbytes, device=x.device, dtype=torch.uint8)
+    _dev(x, norm_w, data, scales, ws)
+    call("sli_batch_gemm_mx8", _p(x), _p(norm_w), eps, _p(data), _p(scales), int(tiled), K, B, ctypes.byref(epi),
+         ctypes.byref(p), _p(ws), ws.numel(), _s())
+    out = {n: getattr(p, n) for n, _ in p._fields_}
+    out["ws"] = ws
+    return out
+
+
+def batch_gemm_qkv_mx8(x, norm_w, eps: float, w, q, kc, vc, pos, sin_t, cos_t, hq: int, hkv: int, hd: int, row_scale=None,
+                       tiled: bool = False, plan=None, kv_dtype=None, ws=None, scales=None):
+    """batch_gemm_qkv on the block-scaled MFMA: w the uint8 MXFP4 data, scales the block scales (required)."""
+    if scales is None or row_scale is not None:
+        raise ValueError("the mx8 launches take MXFP4 weights: scales is required, row_scale is not taken")
+    B = x.shape[0]
+    if kc.shape != vc.shape or kc.dtype != vc.dtype or kc.dim() != 4 or tuple(kc.shape[:2]) != (B, hkv) or kc.shape[3] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[2]
+    if q.dim() != 2 or q.shape[0] < B or q.shape[1] != hq * hd or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    if pos.dtype != torch.int32 or pos.numel() != B:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, pos, sin_t, cos_t)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_kv_dt(kc, kv_dtype), pos=pos.data_ptr(), sin_t=sin_t.data_ptr(),
+                           cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv, hd=hd, T=T)
+    return _batch_gemm_mx8(x, norm_w, eps, w, scales, tiled, e, (hq + 2 * hkv) * hd, plan, ws)
+
+
+def batch_gemm_gate_up_mx8(x, norm_w, eps: float, w, act, act_mode: int = 0, row_scale=None, tiled: bool = False,
+                           plan=None, ws=None, scales=None):
+    """batch_gemm_gate_up on the block-scaled MFMA (scales required)."""
+    if scales is None or row_scale is not None:
+        raise ValueError("the mx8 launches take MXFP4 weights: scales is required, row_scale is not taken")
+    inter = w.shape[0] // 2
+    if act.dim() != 2 or act.shape[0] < x.shape[0] or act.shape[1] != inter or act.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(act)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_GATE_UP, act=act.data_ptr(), inter=inter, act_mode=act_mode)
+    return _batch_gemm_mx8(x, norm_w, eps, w, scales, tiled, e, 2 * inter, plan, ws)
+
+
+def batch_gemm_store_mx8(x, w, y, resid=None, scale: float = 1.0, row_scale=None, tiled: bool = False, plan=None, ws=None,
+                         scales=None):
+    """batch_gemm_store on the block-scaled MFMA (scales required)."""
+    if scales is None or row_scale is not None:
+        raise ValueError("the mx8 launches take MXFP4 weights: scales is required, row_scale is not taken")
+    if y.dim() != 2 or y.shape[0] < x.shape[0] or y.dtype != torch.float32 or (resid is not None and resid.shape != y.shape):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_STORE, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                           scale=scale, nrows=w.shape[0], ld=y.shape[1])
+    return _batch_gemm_mx8(x, None, 0.0, w, scales, tiled, e, w.shape[0], plan, ws)
+
+
+def batch_gemm_logits_mx8(x, norm_w, eps: float, w, logits, keys_out, vocab_off: int = 0, row_scale=None,
+                          tiled: bool = False, plan=None, ws=None, scales=None):
+    """batch_gemm_logits on the block-scaled MFMA (scales required)."""
+    if scales is None or row_scale is not None:
+        raise ValueError("the mx8 launches take MXFP4 weights: scales is required, row_scale is not taken")
+    if logits.dim() != 2 or logits.shape[0] < x.shape[0] or logits.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if keys_out.dim() != 2 or keys_out.shape[0] < x.shape[0] or keys_out.dtype != torch.int64:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(logits, keys_out)
+    e = _lib.BgemmEpilogue(role=BG_ROLE_LOGITS, logits=logits.data_ptr(), keys_out=keys_out.data_ptr(),
+                           nrows=w.shape[0], ld=logits.shape[1], vocab_off=vocab_off, key_ld=keys_out.shape[1])
+    return _batch_gemm_mx8(x, norm_w, eps, w, scales, tiled, e, w.shape[0], plan, ws)
 
 
 GV_ROLE_QKV, GV_ROLE_GATE_UP, GV_ROLE_WO, GV_ROLE_DOWN, GV_ROLE_LOGITS = 0, 1, 2, 3, 4

@@ -11,6 +11,8 @@ does not judge the formats' quality. The JSON carries that note ("synthetic": tr
 
 Writes profiles/quant_quality.json. --mx8: MXFP4 against MXFP4 + MXFP8 activations (set_prefill("gemm-mx8")) instead,
 through the one-sequence driver (one_sequence below), to profiles/quant_quality_mx8.json; the same caveat.
+--mx8-decode: MXFP4 against MXFP4 under set_decode("mx8") in the batched decode step (decode_steps below), to
+profiles/quant_quality_mx8_decode.json; the same caveat.
 """
 import argparse
 import json
@@ -57,8 +59,31 @@ def one_sequence(a, cfg, np, LlamaModel):
             for name, (lp, top) in res.items()]
 
 
+def decode_steps(a, cfg, np, LlamaModel):
+    """MXFP4 against MXFP4 + MXFP8 activations in the batched decode step (set_decode("mx8")): the prompts teacher-forced
+    through predict_batch, one decode step per position, every position's logits scored against the next prompt token."""
+    runs = (("fp16", "f16", "auto"), ("mxfp4", "mxfp4", "auto"), ("mxfp4+mxfp8 decode", "mxfp4", "mx8"))
+    prompts = [_ids(a.tokens, b, cfg.vocab_size) for b in range(a.batch)]
+    nxt = np.array(prompts)[:, 1:]
+    res = {}
+    for name, w, mode in runs:
+        m = LlamaModel(config=cfg, model_path=a.flat, w_dtype=w, kv_dtype="f16", seed=None if a.flat else a.seed,
+                       batch=a.batch, mx_batch=w == "mxfp4").init()
+        m.set_decode(mode)
+        rows = m.predict_batch(prompts, a.tokens, want_logits=True)[1][:, :-1].astype(np.float64)
+        m.close()
+        rows -= rows.max(axis=2, keepdims=True)
+        lp = np.take_along_axis(rows, nxt[:, :, None], axis=2)[:, :, 0] - np.log(np.exp(rows).sum(axis=2))
+        res[name] = (lp.ravel(), rows.argmax(axis=2).ravel())
+    base_lp, base_top = res["fp16"]
+    return [{"format": name, "mean_nll": float(-lp.mean()), "mean_abs_dlogprob_vs_fp16": float(np.abs(lp - base_lp).mean()),
+             "top1_agreement_vs_fp16": float((top == base_top).mean()), "scored_positions": int(lp.size)}
+            for name, (lp, top) in res.items()]
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mx8-decode", action="store_true", help="only the batched decode leg: fp16, mxfp4, mxfp4 under set_decode('mx8')")
     ap.add_argument("--mx8", action="store_true", help="only the one-sequence leg: fp16, mxfp4, mxfp4 + MXFP8 activations")
     ap.add_argument("--preset", default="llama2-7b")
     ap.add_argument("--layers", type=int, default=2, help="layers of the synthetic model (ignored with --flat)")
@@ -73,6 +98,19 @@ def main():
     from simplellminference_amd.model import LlamaModel, preset
     over = dict(max_length=a.ctx) if a.flat else dict(max_length=a.ctx, num_hidden_layers=a.layers)
     cfg = preset(a.preset, **over)
+    if a.mx8_decode:
+        out = {"model": a.preset, "layers": cfg.num_hidden_layers, "weights": a.flat or f"synthetic seed {a.seed}",
+               "synthetic": not a.flat, "batch": a.batch, "ln_vocab": math.log(cfg.vocab_size),
+               "decode_steps": decode_steps(a, cfg, np, LlamaModel)}
+        if not a.flat:
+            out["note"] = NOTE
+            print("NOTE: " + NOTE)
+        for r in out["decode_steps"]:
+            print(f"{r['format']:<20} {r['mean_nll']:>10.5f} {r['mean_abs_dlogprob_vs_fp16']:>10.2e} {r['top1_agreement_vs_fp16']:>12.4f}")
+        with open(a.out.replace("quant_quality.json", "quant_quality_mx8_decode.json"), "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        return
     if a.mx8:
         out = {"model": a.preset, "layers": cfg.num_hidden_layers, "weights": a.flat or f"synthetic seed {a.seed}",
                "synthetic": not a.flat, "ln_vocab": math.log(cfg.vocab_size), "one_sequence": one_sequence(a, cfg, np, LlamaModel)}
