@@ -123,6 +123,16 @@ int sli_quant_mxfp8(const float* src, void* codes, void* scales, int32_t rows, i
 int sli_dequant_mxfp8(const void* codes, const void* scales, float* dst, int32_t rows, int32_t cols,
                       sli_stream_t stream);
 
+/* Per-token int8 activations: the activation format of the integer-MFMA prefill GEMM (sli_prefill_gemm_i8a8), dynamic
+ * symmetric W8A8. An [M][K] image is two arrays:
+ *   codes  int8  [M][K];
+ *   scales float [M]: row m's elements are code * scales[m].
+ * Quantisation of a row h of finite fp32 values (the rule int8 weight rows are placed by):
+ *   scales[m] = max_k |h[m][k]| / 127 (one IEEE fp32 division),
+ *   code[m][k] = clamp(rint(h[m][k] / scales[m]), -127, 127) (an IEEE fp32 division, round to nearest even);
+ *   scales[m] == 0 (an all-zero row) gives all codes 0. -128 is never produced. NaN and Inf inputs are out of contract.
+ * The writers are sli_prefill_norm_quant_i8 and sli_prefill_quant_i8 (below, at sli_prefill_gemm_i8a8). */
+
 /* Batched projection for B sequences decoding in lockstep (the reference is batch 1; this serves
  * SURVEY.md §8 config C4): y[b][r] = sum_c x[b][c] * W[r][c] for b < batch <= 8, on MFMA
  * (v_mfma_f32_16x16x32_f16; the fp32 input is carried as fp16 hi + lo columns). x [batch][cols] fp32, W
@@ -423,7 +433,16 @@ int sli_model_prefill_path(const sli_model* m);
  * fp32 weights, tensor parallelism, batch > 1, an fp32 cache, a depth off 128). It steers the one-sequence driver
  * (sli_model_prefill, sli_model_predict_prefill, sli_model_extend); the packed routes ignore it as they ignore every
  * mode; sli_model_prefill_path reports 1. Its chunk graphs are cached apart from SLI_PREFILL_GEMM's. */
-enum { SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2, SLI_PREFILL_GEMM_KV8 = 3, SLI_PREFILL_GEMM_MX8 = 4 };
+/* SLI_PREFILL_GEMM_I8A8: the same chain for int8 weights, every GEMM on the integer MFMA (sli_prefill_gemm_i8a8) and the
+ * activations quantised to per-token int8 ahead of each (dynamic W8A8): a numerical mode of its own, opt-in. Accepted by
+ * single-rank batch-1 int8 models with an fp16 or FP8 K/V cache, head_dim 64 / 128, projection depths on 128 and a hidden
+ * size of at most 8192; SLI_ERR_STATE with the reason otherwise (fp16 / MXFP4 / fp32 weights, tensor parallelism, batch
+ * > 1, an fp32 cache, a depth off 128). It steers the same driver as SLI_PREFILL_GEMM_MX8, the packed routes ignore it,
+ * sli_tp_group_set_prefill refuses it, and its chunk graphs are cached apart from SLI_PREFILL_GEMM's. */
+enum {
+    SLI_PREFILL_AUTO = 0, SLI_PREFILL_GEMM = 1, SLI_PREFILL_DECODE = 2, SLI_PREFILL_GEMM_KV8 = 3, SLI_PREFILL_GEMM_MX8 = 4,
+    SLI_PREFILL_GEMM_I8A8 = 5
+};
 int sli_model_set_prefill(sli_model* m, int32_t mode);
 /* 1: the batch-1 decode step runs each layer's q/k/v projection and attention as ONE launch (qkv_attn.h: the
  * attention's K/V rows below the position stream while the projection runs; q and this step's K/V row are
@@ -816,6 +835,26 @@ int sli_prefill_quant_mx8(const void* hi, const void* lo, void* codes, void* sca
 int sli_prefill_gemm_mx8(const void* data, const void* scales, const void* acodes, const void* ascales, int32_t N,
                          int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
                          sli_pgemm_tiling* tiling, sli_stream_t stream);
+
+/* The int8 prefill GEMM on the integer MFMA (v_mfma_i32_16x16x64_i8; csrc/pgemm_i8a8.h), a numerical mode of its own:
+ * the activations are per-token int8 images (the rule above, at "Per-token int8 activations"), not hi / lo pairs.
+ * sli_prefill_norm_quant_i8: x [M][D] fp32 -> codes int8 [M][D], scales fp32 [M] of h = RMSNorm(x row) * w (w NULL:
+ *   h = x); the norm is sli_prefill_norm_split's, sum for sum. D % 4 == 0, with w D <= 8192, M >= 1.
+ * sli_prefill_quant_i8: the same image of h = hi + lo (one fp32 add) from an fp16 pair [M][D], as the chunk attention
+ *   and the SwiGLU epilogue write it. D % 4 == 0, any D.
+ * sli_prefill_gemm_i8a8: one pgemm_i8a8_kernel launch: acc[m][r] = sum_k acodes[m][k] * w[r][k] in i32, exact over the
+ *   whole depth; sums[m][r] = (float)acc * ascales[m], then the epilogue of sli_prefill_gemm, whose row scale is
+ *   w_row_scale [N] (or NULL). w: int8 [N][K]. The checks of sli_prefill_gemm, and K % 128 == 0 and K <= 131072 (127^2 K
+ *   stays below 2^31), SLI_ERR_SHAPE otherwise; w, acodes and w_row_scale are 16-byte, ascales 4-byte aligned.
+ *   *tiling: BM, WR, S, AT as there (a workgroup owns 16 * AT * WR weight rows x BM chunk rows, S stages in the ring),
+ *   PIPE 1, SA 0, KS 128. */
+int sli_prefill_norm_quant_i8(const float* x, const float* w, void* codes, float* scales, int32_t M, int32_t D, float eps,
+                              sli_stream_t stream);
+int sli_prefill_quant_i8(const void* hi, const void* lo, void* codes, float* scales, int32_t M, int32_t D,
+                         sli_stream_t stream);
+int sli_prefill_gemm_i8a8(const void* w, const float* w_row_scale, const void* acodes, const float* ascales, int32_t N,
+                          int32_t K, int32_t M, int32_t p0, int32_t nv, const sli_pgemm_epilogue* epi, void* state,
+                          sli_pgemm_tiling* tiling, sli_stream_t stream);
 
 /* Block-causal attention of M chunk rows (32, 64, 128 or 256): row m of head h attends the cache rows 0 .. p0 + m
  * of kv head h / (hq / hkv); q [rows][hq * hd] fp32, kc / vc one layer's cache [hkv][T][hd] in kv_dtype, the result

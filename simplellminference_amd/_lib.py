@@ -213,6 +213,10 @@ _SIGS = {
     "sli_prefill_quant_mx8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "sli_prefill_gemm_mx8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
                                      ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
+    "sli_prefill_norm_quant_i8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f, c_vp]),
+    "sli_prefill_quant_i8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "sli_prefill_gemm_i8a8": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                      ctypes.POINTER(PgemmEpilogue), c_vp, ctypes.POINTER(PgemmTiling), c_vp]),
     "sli_prefill_pack": (c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, P_i32]),
     "sli_model_prefill_seqs": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32]),
     "sli_model_prefill_seqs_ok": (c_int, [c_vp]),

@@ -30,6 +30,7 @@
 #include "common.h"
 #include "gemv.h"
 #include "kv_copy.h"
+#include "i8a8_api.h"
 #include "mx8_api.h"
 #include "oneshot.h"
 #include "ops_internal.h"
@@ -139,6 +140,8 @@ struct sli_model {
         int mode = SLI_PREFILL_AUTO;  // sli_model_set_prefill
         // SLI_PREFILL_GEMM_MX8: the chunk's MXFP8 activation image (codes [chunk][widest depth], scales / 32) and chunk
         // graphs of their own, so switching modes replays nothing recorded under the other
+        // SLI_PREFILL_GEMM_I8A8 (int8 weights, so never the same model): the same slots, c8 the int8 codes [chunk][widest
+        // depth] and s8 the chunk rows' fp32 scales
         uint8_t* c8 = nullptr;
         uint8_t* s8 = nullptr;
         hipGraph_t graph8[4] = {};
@@ -1341,6 +1344,41 @@ struct StepRecorder {
         }
         return SLI_OK;
     }
+    // The chunk under SLI_PREFILL_GEMM_I8A8 (single rank, int8 weights): record_prefill_mx8's chain with every GEMM on
+    // the integer MFMA (pgemm_i8a8.h) from a per-token int8 image of its activations; the weight row scales go to the
+    // epilogues as under SLI_PREFILL_GEMM.
+    static int record_prefill_i8a8(sli_model* m, int M) {
+        auto& f = m->pf;
+        hipStream_t s = m->stream;
+        const int D = m->D, hd = m->hd, QD = m->hq * hd;
+        float* sc = reinterpret_cast<float*>(f.s8);
+        hipLaunchKernelGGL((pf_embed_kernel<WT>), dim3(M), dim3(256), 0, s, f.segs, m->prompt, (const WT*)m->emb,
+                           (const void*)m->emb_s, f.x, D, m->T + 1);
+        SLI_HIP(hipGetLastError());
+        sli_pgemm_epilogue er{};
+        er.role = 2, er.y = f.x, er.resid = f.x, er.ld = D;
+        for (int l = 0; l < m->L; ++l) {
+            const LayerW& w = m->layers[l];
+            const size_t ls = (size_t)l * m->B * m->hkv * m->T * hd;
+            sli_pgemm_epilogue eq{};
+            eq.role = 0, eq.q = f.q, eq.kc = (KT*)m->kc + ls, eq.vc = (KT*)m->vc + ls, eq.kv_dtype = m->c.kv_dtype;
+            eq.sin_t = m->sin_t, eq.cos_t = m->cos_t, eq.hq = m->hq, eq.hkv = m->hkv, eq.hd = hd, eq.T = m->T;
+            sli_pgemm_epilogue eg{};
+            eg.role = 1, eg.ahi = f.ahi, eg.alo = f.alo, eg.inter = m->Il, eg.act_mode = m->c.act_mode;
+            PfAttnArgs<KT> aa{f.q, (const KT*)m->kc + ls, (const KT*)m->vc + ls, f.hhi, f.hlo, m->hq, m->hkv, m->T,
+                              1.0f / sqrtf((float)hd)};
+            SLI_TRY(i8a8_norm_quant(f.x, m->norms + (size_t)(2 * l) * D, f.c8, sc, M, D, m->c.eps, s));
+            SLI_TRY(i8a8_gemm(w.qkv, w.qkv_s, f.c8, sc, (m->hq + 2 * m->hkv) * hd, D, M, eq, f.segs, nullptr, s));
+            SLI_HIP(launch_pf_attn<KT>(aa, hd, M, f.segs, s));
+            SLI_TRY(i8a8_pair_quant(f.hhi, f.hlo, f.c8, sc, M, QD, s));
+            SLI_TRY(i8a8_gemm(w.wo, w.wo_s, f.c8, sc, D, QD, M, er, f.segs, nullptr, s));
+            SLI_TRY(i8a8_norm_quant(f.x, m->norms + (size_t)(2 * l + 1) * D, f.c8, sc, M, D, m->c.eps, s));
+            SLI_TRY(i8a8_gemm(w.gu, w.gu_s, f.c8, sc, 2 * m->Il, D, M, eg, f.segs, nullptr, s));
+            SLI_TRY(i8a8_pair_quant(f.ahi, f.alo, f.c8, sc, M, m->Il, s));
+            SLI_TRY(i8a8_gemm(w.down, w.down_s, f.c8, sc, D, m->Il, M, er, f.segs, nullptr, s));
+        }
+        return SLI_OK;
+    }
     // a chunk of any route but the in-process group's; a single-rank model has no exchange
     static int record_prefill(sli_model* m, int M) {
         for (int p = 0; p < 2 * m->L; ++p) {
@@ -2165,8 +2203,24 @@ static const char* pf_mx8_refusal(const sli_model* m) {
         return "set_prefill: SLI_PREFILL_GEMM_MX8 needs projection depths that are multiples of 128 (one MFMA issue), hidden size <= 8192";
     return nullptr;
 }
+// SLI_PREFILL_GEMM_I8A8 (pgemm_i8a8.h): why this model cannot take it, or null
+static const char* pf_i8a8_refusal(const sli_model* m) {
+    if (m->c.w_dtype != SLI_DT_I8) return "set_prefill: SLI_PREFILL_GEMM_I8A8 needs int8 weights (the integer MFMA multiplies int8 codes)";
+    if (m->c.tp_size > 1 || m->partial || m->group) return "set_prefill: SLI_PREFILL_GEMM_I8A8 is single-rank (no tensor parallelism)";
+    if (m->B != 1) return "set_prefill: SLI_PREFILL_GEMM_I8A8 is batch 1";
+    if (m->c.kv_dtype == SLI_DT_F32) return "set_prefill: SLI_PREFILL_GEMM_I8A8 needs an fp16 or FP8 K/V cache";
+    if (m->hd != 64 && m->hd != 128) return "set_prefill: SLI_PREFILL_GEMM_I8A8 needs head_dim 64 or 128";
+    if (m->D % 128 || m->Il % 128 || (m->hq * m->hd) % 128 || m->D > 8192 || m->Il > kI8A8MaxK)
+        return "set_prefill: SLI_PREFILL_GEMM_I8A8 needs projection depths that are multiples of 128 (one stage), hidden size <= 8192";
+    return nullptr;
+}
+// the modes that run the chunk chain from an 8-bit activation image, and their refusal for this model
+static bool pf_a8_mode(int mode) { return mode == SLI_PREFILL_GEMM_MX8 || mode == SLI_PREFILL_GEMM_I8A8; }
+static const char* pf_a8_refusal(const sli_model* m, int mode) {
+    return mode == SLI_PREFILL_GEMM_MX8 ? pf_mx8_refusal(m) : pf_i8a8_refusal(m);
+}
 static bool pf_supported(const sli_model* m, int mode) {
-    if (mode == SLI_PREFILL_GEMM_MX8) return pf_mx8_refusal(m) == nullptr;
+    if (pf_a8_mode(mode)) return pf_a8_refusal(m, mode) == nullptr;
     if (m->partial && !m->collectives && !m->group) return false;
     if (m->c.kv_dtype == SLI_DT_F8E4M3 && mode != SLI_PREFILL_GEMM_KV8) return false;  // opt-in (sli.h)
     return m->c.w_dtype != SLI_DT_F32 && m->B == 1 && pf_shape_ok(m);
@@ -2175,16 +2229,16 @@ static bool pf_supported(const sli_model* m, int mode) {
 // stepwise path replays the decode graph, so the mode only selects which of the two is launched; nothing captured
 // depends on it. auto keeps MXFP4 on the decode step (the default flips once the tests that pin it are revisited).
 static bool pf_forced(int mode) {
-    return mode == SLI_PREFILL_GEMM || mode == SLI_PREFILL_GEMM_KV8 || mode == SLI_PREFILL_GEMM_MX8;
+    return mode == SLI_PREFILL_GEMM || mode == SLI_PREFILL_GEMM_KV8 || pf_a8_mode(mode);
 }
-static bool pf_mode_ok(int mode) { return mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_GEMM_MX8; }
+static bool pf_mode_ok(int mode) { return mode >= SLI_PREFILL_AUTO && mode <= SLI_PREFILL_GEMM_I8A8; }
 static bool pf_use_gemm(const sli_model* m) {
     if (m->pf.mode == SLI_PREFILL_DECODE || !pf_supported(m, m->pf.mode)) return false;
     return pf_forced(m->pf.mode) || m->c.w_dtype != SLI_DT_MXFP4;
 }
 static int pf_set_mode(sli_model* m, int mode) {
-    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0, 1, 2, 3 or 4");
-    if (mode == SLI_PREFILL_GEMM_MX8 && pf_mx8_refusal(m)) return fail(SLI_ERR_STATE, pf_mx8_refusal(m));
+    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0 .. 5");
+    if (pf_a8_mode(mode) && pf_a8_refusal(m, mode)) return fail(SLI_ERR_STATE, pf_a8_refusal(m, mode));
     SLI_CHECK(!pf_forced(mode) || pf_supported(m, mode), SLI_ERR_STATE,
               "set_prefill: this model cannot take the GEMM prefill (fp32 weights, an FP8 K/V cache outside "
               "SLI_PREFILL_GEMM_KV8, batch > 1, a TP rank without a communicator, head_dim not 64 / 128, or a "
@@ -2286,18 +2340,20 @@ static int pf_enqueue(const PfPlan& pl, std::vector<PfSegs>& tabs, hipStream_t s
 }
 // The two places a plan runs, each to the end of its chunks. A model: the plain chunk graphs, or with `score` the
 // scoring ones (record_score_segs), which have slots of their own.
-static int pf_run_model(sli_model* m, const PfPlan& pl, bool score, bool mx8 = false) {
+static int pf_run_model(sli_model* m, const PfPlan& pl, bool score, bool a8 = false) {
     SLI_TRY(pf_alloc(m));
     std::vector<PfSegs> tabs;
-    if (mx8) {  // the one-sequence driver under SLI_PREFILL_GEMM_MX8: the image, the LDS opt-ins, graphs of their own
+    if (a8) {  // the one-sequence driver under SLI_PREFILL_GEMM_MX8 / _I8A8: the image, the LDS opt-ins, graphs of their own
+        const bool i8 = m->pf.mode == SLI_PREFILL_GEMM_I8A8;
         if (!m->pf.s8) {  // s8 is set last: a failure on the way leaves the block to be tried again
             const size_t W = std::max<size_t>({(size_t)m->D, (size_t)m->hq * m->hd, (size_t)m->Il});
-            SLI_TRY(mx8_prepare());
+            SLI_TRY(i8 ? i8a8_prepare() : mx8_prepare());
             if (!m->pf.c8) SLI_TRY(model_alloc(m, (void**)&m->pf.c8, kPfMaxChunk * W));
-            SLI_TRY(model_alloc(m, (void**)&m->pf.s8, kPfMaxChunk * W / 32));
+            SLI_TRY(model_alloc(m, (void**)&m->pf.s8, i8 ? kPfMaxChunk * sizeof(float) : kPfMaxChunk * W / 32));
         }
-        SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph8, m->pf.exec8, {m->pf.segs},
-                           [&](int M) { return SLI_DISPATCH(m, record_prefill_mx8, m, M); }));
+        SLI_TRY(pf_enqueue(pl, tabs, m->stream, m->pf.graph8, m->pf.exec8, {m->pf.segs}, [&](int M) {
+            return i8 ? SLI_DISPATCH(m, record_prefill_i8a8, m, M) : SLI_DISPATCH(m, record_prefill_mx8, m, M);
+        }));
         return wait_stream(m);
     }
     SLI_TRY(pf_enqueue(pl, tabs, m->stream, score ? m->pf.scgraph : m->pf.graph, score ? m->pf.scexec : m->pf.exec,
@@ -2323,6 +2379,7 @@ static int pf_run_group(sli_tp_group* g, const PfPlan& pl) {
 extern "C" int sli_model_prefill_path(const sli_model* m) { return m && m->B == 1 && pf_use_gemm(m) ? 1 : 0; }
 
 extern "C" int sli_model_set_prefill(sli_model* m, int32_t mode) {
+    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0 .. 5");  // first, as sli_model_set_decode's
     SLI_CHECK(m, SLI_ERR_ARG, "null argument");
     SLI_CHECK(!m->group, SLI_ERR_STATE, "set_prefill: ranks of an in-process group are set through sli_tp_group_set_prefill");
     return pf_set_mode(m, mode);
@@ -2330,7 +2387,7 @@ extern "C" int sli_model_set_prefill(sli_model* m, int32_t mode) {
 
 extern "C" int sli_tp_group_set_prefill(sli_tp_group* g, int32_t mode) {
     SLI_CHECK(g, SLI_ERR_ARG, "null argument");
-    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0, 1, 2, 3 or 4");
+    SLI_CHECK(pf_mode_ok(mode), SLI_ERR_ARG, "set_prefill: mode must be 0 .. 5");
     for (sli_model* m : g->ranks)
         SLI_CHECK(!pf_forced(mode) || pf_supported(m, mode), SLI_ERR_STATE,
                   "set_prefill: this group cannot take the GEMM prefill");
@@ -2675,7 +2732,7 @@ static int ext_one_args(sli_model* m0, const int32_t* tokens, int32_t* start, in
 
 static int one_model(sli_model* m, const int32_t* tokens, int32_t start, int32_t count) {
     return ext_one({m}, tokens, start, count, [&] { return sli_model_step(m); },
-                   [&](const PfPlan& pl) { return pf_run_model(m, pl, false, m->pf.mode == SLI_PREFILL_GEMM_MX8); });
+                   [&](const PfPlan& pl) { return pf_run_model(m, pl, false, pf_a8_mode(m->pf.mode)); });
 }
 static int one_group(sli_tp_group* g, const int32_t* tokens, int32_t start, int32_t count) {
     return ext_one(g->ranks, tokens, start, count, [&] { return sli_tp_group_step(g); },

@@ -494,6 +494,94 @@ def prefill_gemm_logits_mx8(w, scales, acodes, ascales, y):
     return _prefill_gemm_mx8(w, scales, acodes, ascales, 0, acodes.shape[0], e)
 
 
+# ---- per-token int8 activations and the integer-MFMA prefill GEMM (csrc/pgemm_i8a8.h)
+def _i8_image(M, D, device):
+    return (torch.empty(M, D, device=device, dtype=torch.int8), torch.empty(M, device=device, dtype=torch.float32))
+
+
+def prefill_norm_quant_i8(x, w, eps: float):
+    """pf_quant_i8_kernel from fp32: x [M, D] -> (codes int8 [M, D], scales fp32 [M]) of RMSNorm(x) * w (w None: of x)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or (w is not None and (w.dtype != torch.float32 or w.shape != x.shape[1:])):
+        raise ValueError("prefill_norm_quant_i8 takes fp32 x [M, D] and w [D]")
+    codes, scales = _i8_image(*x.shape, x.device)
+    _dev(x, w)
+    call("sli_prefill_norm_quant_i8", _p(x), _p(w), _p(codes), _p(scales), x.shape[0], x.shape[1], eps, _s())
+    return codes, scales
+
+
+def prefill_quant_i8(hi, lo):
+    """pf_quant_i8_kernel from an fp16 hi / lo pair [M, D]: the per-token int8 image of hi + lo."""
+    if hi.shape != lo.shape or hi.dim() != 2 or hi.dtype != torch.float16 or lo.dtype != torch.float16:
+        raise ValueError("Tensor with Wrong Dim!")
+    codes, scales = _i8_image(*hi.shape, hi.device)
+    _dev(hi, lo)
+    call("sli_prefill_quant_i8", _p(hi), _p(lo), _p(codes), _p(scales), hi.shape[0], hi.shape[1], _s())
+    return codes, scales
+
+
+def _prefill_gemm_i8a8(w, row_scale, acodes, ascales, p0, nv, epi):
+    """sli_prefill_gemm_i8a8: w int8 [N, K] and row_scale fp32 [N] (or None), acodes int8 [M, K] and ascales fp32 [M].
+    Returns the tiling that ran."""
+    N, K = w.shape
+    M = acodes.shape[0]
+    if w.dtype != torch.int8 or acodes.dtype != torch.int8 or ascales.dtype != torch.float32:
+        raise ValueError("Tensor with Wrong Dim!")
+    if acodes.shape != (M, K) or ascales.shape != (M,) or (row_scale is not None and (
+            row_scale.dtype != torch.float32 or row_scale.shape != (N,))):
+        raise ValueError("Tensor with Wrong Dim!")
+    state = _pf_table(w.device)
+    _dev(w, row_scale, acodes, ascales)
+    tl = _lib.PgemmTiling()
+    call("sli_prefill_gemm_i8a8", _p(w), _p(row_scale), _p(acodes), _p(ascales), N, K, M, p0, nv, ctypes.byref(epi),
+         _p(state), ctypes.byref(tl), _s())
+    return {n: getattr(tl, n) for n, _ in tl._fields_}
+
+
+def prefill_gemm_qkv_i8a8(w, row_scale, acodes, ascales, q, kc, vc, sin_t, cos_t, hq: int, hkv: int, hd: int, p0: int,
+                          nv: int, kv_dtype=None):
+    """prefill_gemm_qkv on the integer MFMA: int8 W, per-token int8 activations; the same epilogue operands."""
+    if kc.dtype != vc.dtype or kc.shape != vc.shape or kc.shape[0] != hkv or kc.shape[2] != hd:
+        raise ValueError("Tensor with Wrong Dim!")
+    T = kc.shape[1]
+    if q.shape != (acodes.shape[0], hq * hd) or sin_t.shape != (T, hd // 2) or cos_t.shape != (T, hd // 2):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, kc, vc, sin_t, cos_t)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_QKV, q=q.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(),
+                           kv_dtype=_kv_dt(kc, kv_dtype), sin_t=sin_t.data_ptr(), cos_t=cos_t.data_ptr(), hq=hq, hkv=hkv,
+                           hd=hd, T=T)
+    return _prefill_gemm_i8a8(w, row_scale, acodes, ascales, p0, nv, e)
+
+
+def prefill_gemm_gate_up_i8a8(w, row_scale, acodes, ascales, ahi, alo, act_mode: int = 0):
+    """prefill_gemm_gate_up on the integer MFMA: W [2 inter, K] = [gate; up]; ahi / alo [M, inter] fp16."""
+    inter = w.shape[0] // 2
+    if ahi.shape != (acodes.shape[0], inter) or alo.shape != ahi.shape:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(ahi, alo)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_GATE_UP, ahi=ahi.data_ptr(), alo=alo.data_ptr(), inter=inter,
+                           act_mode=act_mode)
+    return _prefill_gemm_i8a8(w, row_scale, acodes, ascales, 0, acodes.shape[0], e)
+
+
+def prefill_gemm_resid_i8a8(w, row_scale, acodes, ascales, y, resid=None):
+    """prefill_gemm_resid on the integer MFMA: y [M, ld] = (resid or 0) + the sums."""
+    if y.shape[0] != acodes.shape[0] or (resid is not None and resid.shape != y.shape):
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y, resid)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_RESID, y=y.data_ptr(), resid=resid.data_ptr() if resid is not None else None,
+                           ld=y.shape[1])
+    return _prefill_gemm_i8a8(w, row_scale, acodes, ascales, 0, acodes.shape[0], e)
+
+
+def prefill_gemm_logits_i8a8(w, row_scale, acodes, ascales, y):
+    """prefill_gemm_logits on the integer MFMA: y [M, ld][:, :N] for W's N >= 16 rows (any N)."""
+    if y.shape[0] != acodes.shape[0]:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(y)
+    e = _lib.PgemmEpilogue(role=PF_ROLE_LOGITS, y=y.data_ptr(), ld=y.shape[1])
+    return _prefill_gemm_i8a8(w, row_scale, acodes, ascales, 0, acodes.shape[0], e)
+
+
 def score_rows(logits, targets, want_top: bool = True):
     """sli_score_rows: per row of fp32 logits [M, V] (rows ``logits.stride(0)`` floats apart: a row-padded view is
     taken as it is) and int32 target, the target's log-probability, the first-max token and its log-probability (the
