@@ -1116,6 +1116,58 @@ int sli_decode_gemv(const float* x, const float* norm_w, float eps, const void* 
 int sli_decode_gemv_mxfp4(const float* x, const float* norm_w, float eps, const void* data, const void* scales,
                           int32_t cols, const sli_gemv_epilogue* epi, sli_gemv_plan* plan, sli_stream_t stream);
 
+/* One decode attention launch (csrc/attention.h, attn_mfma.h) as a model step records it, for 1 <= B <= 8 sequences:
+ * out[(b hq + h) hd ..] = softmax_t((q_bh . K[b hkv + h / (hq / hkv)][t]) / sqrt(hd)) V[..][t] over t <= pos[b].
+ * q [B hq hd] fp32; k / v ONE layer of the head-major cache [B hkv][T][hd] in kv_dtype (SLI_DT_F32 / F16 / F8E4M3);
+ * out [B hq hd] fp32; part: sli_mha_workspace_bytes(T, B hq, hd) minus the counters is enough, [B hq][splits][hd + 4]
+ * (o[hd], m, l, pad) over splits of ppwg positions; counters [2 B hkv] uint32, ZERO ON ENTRY and zero again on
+ * return of the launch (the caller's contract, as a model keeps it); pos int32 ON THE DEVICE, sequence b's at
+ * pos[b * pos_seq_stride]; 0 <= pos[b] < T is the caller's contract. Rows past pos[b] are never read: they may hold
+ * anything, NaN and the FP8 NaN codes included. For t <= pos[b] an FP8 NaN code is out of contract, as for sli_mha.
+ * merge, the engine's three values: 0 the head's last-arriving workgroup merges its live splits into out inside the
+ * launch; 1 the launch stores the live splits' partials only (plain stores; out, dead splits and pad words untouched)
+ * and the consumer merges (SLI_GV_WO with part); 2 the same, then attn_merge_kernel as its own launch writes out. The
+ * MFMA kernels (every FP8 cache; an fp16 cache unless merge == 1) turn 2 into 0: plan.merge says what took effect.
+ * The launch is mha_launch with the engine's own arguments (seq_heads and the position stride only when B > 1), so it
+ * runs the code objects a model step runs. */
+typedef struct {
+    const float* q;
+    const void* k;
+    const void* v;
+    int32_t kv_dtype;
+    float* out;
+    float* part;
+    uint32_t* counters;
+    const int32_t* pos;
+    int32_t pos_seq_stride; /* int32s between consecutive sequences' positions (B > 1) */
+    int32_t B, hq, hkv, hd, T;
+    int32_t merge;
+} sli_attn_launch;
+
+/* The geometry of a launch, in / out. In: cus, as in sli_gemv_plan (0: the device's; otherwise the split geometry is
+ * made as if the chip had `cus` compute units, 1 <= cus <= the device's). Out, what ran: kernel 0 the register-staged
+ * attn_partial_kernel, 1 the MFMA kernel; g query heads per kv head as launched and kv_group (2: a GQA-4 head group
+ * run as two GQA-2 groups); waves per workgroup; ppwg positions per split; max_splits splits per kv head; tpw tiles
+ * per wave and nbuf ring slots (MFMA; 0 otherwise); grid workgroups; merge_grid the merge launch's (0: none); merge as
+ * it took effect. */
+typedef struct {
+    int32_t cus;
+    int32_t kernel, g, kv_group, waves, ppwg, max_splits, tpw, nbuf, grid, merge_grid, merge;
+} sli_attn_plan;
+
+/* *plan resolved as sli_decode_attn would resolve it for operands that are 16-byte aligned; nothing is launched and
+ * no pointer of *launch is read. It needs no device when plan->cus != 0. */
+int sli_decode_attn_plan(const sli_attn_launch* launch, sli_attn_plan* plan);
+
+/* One launch (two with merge 2 on the register-staged kernel). Refused, each with its own message, before the device
+ * is touched: a null pointer, q / k / v / out / part not 16-byte aligned, merge outside 0 .. 2, FP8 with merge 1,
+ * counters or pos not 4-byte aligned, a kv_dtype other than the three, pos_seq_stride < 1 when B > 1, cus negative,
+ * above the device's or above 4096 (SLI_ERR_ARG; sli_decode_attn_plan, which asks no device, holds cus to 4096 only);
+ * hd other than 64 or 128, hq % hkv != 0 or hq / hkv not in {1, 2, 4, 8}, hq above 4096, B outside 1 .. 8, T < 1 or
+ * one layer's cache [B hkv][T][hd] of 2^31 elements or more, more splits than the merge or the partial buffer holds
+ * (SLI_ERR_SHAPE). */
+int sli_decode_attn(const sli_attn_launch* launch, sli_attn_plan* plan, sli_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,17 @@ class GemvPlan(ctypes.Structure):  # sli_gemv_plan
                                      "nb", "ns", "masked_tail", "lds_bytes")]
 
 
+class AttnLaunch(ctypes.Structure):  # sli_attn_launch
+    _fields_ = [("q", c_vp), ("k", c_vp), ("v", c_vp), ("kv_dtype", c_i32), ("out", c_vp), ("part", c_vp),
+                ("counters", c_vp), ("pos", c_vp), ("pos_seq_stride", c_i32)] + \
+               [(n, c_i32) for n in ("B", "hq", "hkv", "hd", "T", "merge")]
+
+
+class AttnPlan(ctypes.Structure):  # sli_attn_plan
+    _fields_ = [(n, c_i32) for n in ("cus", "kernel", "g", "kv_group", "waves", "ppwg", "max_splits", "tpw", "nbuf",
+                                     "grid", "merge_grid", "merge")]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "sli_version": (c_int, []),
@@ -255,6 +266,8 @@ _SIGS = {
                                 ctypes.POINTER(GemvPlan), c_vp]),
     "sli_decode_gemv_mxfp4": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_i32, ctypes.POINTER(GemvEpilogue),
                                       ctypes.POINTER(GemvPlan), c_vp]),
+    "sli_decode_attn_plan": (c_int, [ctypes.POINTER(AttnLaunch), ctypes.POINTER(AttnPlan)]),
+    "sli_decode_attn": (c_int, [ctypes.POINTER(AttnLaunch), ctypes.POINTER(AttnPlan), c_vp]),
     "sli_tp_group_destroy": (c_int, [c_vp]),
     "sli_tp_group_rank": (c_int, [c_vp, c_i32, ctypes.POINTER(c_vp)]),
     "sli_tp_group_step": (c_int, [c_vp]),

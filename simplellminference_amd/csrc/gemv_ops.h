@@ -13,7 +13,9 @@
 // before anything touches the device.
 //
 // Not covered: EpiPush (the residual exchange inside wo / down needs peers), the shared q/k/v + attention launch
-// (qkv_attn.h; tests/test_gpu_qkv_attn.py holds it bit for bit to the two-launch step) and tp_layers.h.
+// (qkv_attn.h; tests/test_gpu_qkv_attn.py holds it bit for bit to the two-launch step) and tp_layers.h. The decode
+// attention launch between q/k/v and wo, whose partials the merged wo consumes, has its own entry: sli_decode_attn
+// (ops.hip, tests/test_gpu_decode_attn.py).
 #pragma once
 #include "common.h"
 #include "gemv.h"

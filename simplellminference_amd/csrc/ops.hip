@@ -240,20 +240,31 @@ static void attn_mfma_go(const AttnArgs<KT>& a, int blocks, int nbuf, hipStream_
             hipLaunchKernelGGL((attn_mfma_f8_kernel<HD, G, 4>), grid, wg, 0, s, a);
     }
 }
+// what a launch ran, for sli_decode_attn (plan->cus is the caller's)
+static void plan_set(sli_attn_plan* p, int kernel, int g, int kv_group, int waves, int ppwg, int max_splits, int tpw,
+                     int nbuf, int grid, int merge_grid, int merge) {
+    p->kernel = kernel, p->g = g, p->kv_group = kv_group, p->waves = waves, p->ppwg = ppwg, p->max_splits = max_splits;
+    p->tpw = tpw, p->nbuf = nbuf, p->grid = grid, p->merge_grid = merge_grid, p->merge = merge;
+}
 // Split geometry: one workgroup per CU over the whole context (attn_mfma_tpw), its splits merged by the head's
 // last-arriving workgroup inside the launch (a.defer_merge 0). ring: the most tiles a wave keeps in flight.
 template <typename KT, int HD>
-static int attn_mfma_launch(AttnArgs<KT> a, int g, int T, int ring, hipStream_t s) {
+static int attn_mfma_launch(AttnArgs<KT> a, int g, int T, int ring, hipStream_t s, int cus = 0,
+                            sli_attn_plan* plan = nullptr, bool dry = false) {
     // the partial buffer (mha_part_bytes) holds ceil(T / pf) splits per head, pf = the fp32 kernel's positions per
     // workgroup; at head_dim 64 that is 256 keys, so one tile per wave (128 keys) over a longer context would store
     // past it (the round-5 fault record): the split is never shorter than pf
     const int pf = attn_wg_positions(SLI_DT_F32, HD);
-    const int tpw = std::max(attn_mfma_tpw(a.n_kv_heads, T, device_cus()), (pf + kAmWgKeys - 1) / kAmWgKeys);
+    const int tpw = std::max(attn_mfma_tpw(a.n_kv_heads, T, cus > 0 ? cus : device_cus()), (pf + kAmWgKeys - 1) / kAmWgKeys);
     a.ppwg = kAmWgKeys * tpw;
     a.max_splits = (T + a.ppwg - 1) / a.ppwg;
     if (a.max_splits > kAttnMaxWgSplits) return fail(SLI_ERR_SHAPE, "mha: context too long for the split merge");
     if (a.max_splits > (T + pf - 1) / pf) return fail(SLI_ERR_SHAPE, "mha: more splits than the partial buffer holds");
     const int blocks = a.n_kv_heads * a.max_splits, nbuf = std::min(tpw, ring);
+    if (plan)  // nbuf: the instantiated ring depth (attn_mfma_go's ladder)
+        plan_set(plan, 1, g, 1, kAmWaves, a.ppwg, a.max_splits, tpw, nbuf >= 4 ? 4 : nbuf >= 2 ? 2 : 1, blocks, 0,
+                 a.defer_merge);
+    if (dry) return SLI_OK;
     switch (g) {
         case 1: attn_mfma_go<KT, HD, 1>(a, blocks, nbuf, s); break;
         case 2: attn_mfma_go<KT, HD, 2>(a, blocks, nbuf, s); break;
@@ -268,7 +279,7 @@ template <typename KT, int HD>
 static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out, int layer, int pos, const int32_t* pos_dev,
                          int T, int H, int Hkv, long long pos_stride, long long head_stride, long long layer_stride,
                          float* part, unsigned* counters, hipStream_t s, int seq_heads, int pos_seq_stride,
-                         int cache_heads, int defer_merge) {
+                         int cache_heads, int defer_merge, int cus, sli_attn_plan* plan, bool dry) {
     if constexpr (std::is_same<KT, f8e4m3>::value) {  // never the register-staged kernels of attention.h
         AttnArgs<KT> a{q,    kc + (long long)layer * layer_stride, vc + (long long)layer * layer_stride, pos_stride,
                        head_stride, part, out, counters, pos_dev, pos, Hkv, 0, 1.0f / sqrtf((float)HD),
@@ -283,7 +294,7 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
         if (!attn_mfma_aligned(a))
             return fail(SLI_ERR_ARG, "mha: an FP8 cache needs 16-byte aligned bases, row stride and head stride");
         a.defer_merge = 0;  // the head's last-arriving workgroup merges (a requested merge launch becomes that)
-        return attn_mfma_launch<KT, HD>(a, g, T, SLI_ATTN_F8_RING, s);
+        return attn_mfma_launch<KT, HD>(a, g, T, SLI_ATTN_F8_RING, s, cus, plan, dry);
     } else {
     using Geo = AttnGeom<KT, HD>;
     constexpr int ppw_wg = Geo::PPWG;
@@ -298,7 +309,7 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
     if constexpr (std::is_same<KT, __half>::value) {
         if (attn_mfma_ok(a, g)) {
             if (a.defer_merge == 2) a.defer_merge = 0;  // a requested merge launch becomes the in-launch merge
-            return attn_mfma_launch<KT, HD>(a, g, T, 2, s);
+            return attn_mfma_launch<KT, HD>(a, g, T, 2, s, cus, plan, dry);
         }
     }
     // GQA-4 as two GQA-2 groups per kv head: the 59-VGPR GQA-2 kernel at 8 waves/SIMD instead of the 128-VGPR GQA-4
@@ -306,7 +317,7 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
     // only (partials are indexed by q head; the counters by kv head), where the unsplit grid fills at most half the
     // chip. Measured (profiles/r4_gqa_split_ab.txt): Llama-3-8B batch 1 (8 kv heads x 16 splits = 128 workgroups)
     // attention 10.7 -> 8.1 us; C4 (1024 workgroups) 34.5 -> 41 us, so off there.
-    if (g == 4 && defer_merge && cache_heads == 0 && 2 * Hkv * wg_splits <= device_cus()) {
+    if (g == 4 && defer_merge && cache_heads == 0 && 2 * Hkv * wg_splits <= (cus > 0 ? cus : device_cus())) {
         g = 2;
         a.kv_group = 2;
         a.n_kv_heads = 2 * Hkv;
@@ -314,6 +325,11 @@ static int mha_launch_hd(const float* q, const KT* kc, const KT* vc, float* out,
         Hkv *= 2;
     }
     const int blocks = Hkv * wg_splits;
+    if (!(g == 1 || g == 2 || g == 4 || g == 8)) return fail(SLI_ERR_SHAPE, "mha: heads per kv head must be 1, 2, 4 or 8");
+    if (plan)
+        plan_set(plan, 0, g, a.kv_group, attn_waves(g), ppw_wg, wg_splits, 0, 0, blocks,
+                 defer_merge == 2 ? Hkv * attn_merge_wgs(g * HD) : 0, defer_merge);
+    if (dry) return SLI_OK;
     switch (g) {
         case 1: hipLaunchKernelGGL((attn_partial_kernel<KT, HD, 1>), dim3(blocks), dim3(64 * attn_waves(1)), 0, s, a); break;
         case 2: hipLaunchKernelGGL((attn_partial_kernel<KT, HD, 2>), dim3(blocks), dim3(64 * attn_waves(2)), 0, s, a); break;
@@ -340,26 +356,28 @@ template <typename KT>
 int mha_launch(const float* q, const KT* kc, const KT* vc, float* out, int layer, int pos, const int32_t* pos_dev,
                int T, int hd, int H, int Hkv, long long pos_stride, long long head_stride, long long layer_stride,
                float* part, unsigned* counters, hipStream_t s, int seq_heads, int pos_seq_stride, int cache_heads,
-               int defer_merge) {
+               int defer_merge, int cus, sli_attn_plan* plan, bool dry) {
     if (hd == 128)
         return mha_launch_hd<KT, 128>(q, kc, vc, out, layer, pos, pos_dev, T, H, Hkv, pos_stride, head_stride,
-                                      layer_stride, part, counters, s, seq_heads, pos_seq_stride, cache_heads, defer_merge);
+                                      layer_stride, part, counters, s, seq_heads, pos_seq_stride, cache_heads, defer_merge,
+                                      cus, plan, dry);
     if (hd == 64)
         return mha_launch_hd<KT, 64>(q, kc, vc, out, layer, pos, pos_dev, T, H, Hkv, pos_stride, head_stride,
-                                     layer_stride, part, counters, s, seq_heads, pos_seq_stride, cache_heads, defer_merge);
+                                     layer_stride, part, counters, s, seq_heads, pos_seq_stride, cache_heads, defer_merge,
+                                      cus, plan, dry);
     return fail(SLI_ERR_SHAPE, "mha: head_dim must be 64 or 128");
 }
 
 template int mha_launch<float>(const float*, const float*, const float*, float*, int, int, const int32_t*, int, int,
                                int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int, int,
-                               int, int);
+                               int, int, int, sli_attn_plan*, bool);
 template int mha_launch<__half>(const float*, const __half*, const __half*, float*, int, int, const int32_t*, int,
                                 int, int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int,
-                                int, int, int);
+                                int, int, int, int, sli_attn_plan*, bool);
 
 template int mha_launch<f8e4m3>(const float*, const f8e4m3*, const f8e4m3*, float*, int, int, const int32_t*, int,
                                 int, int, int, long long, long long, long long, float*, unsigned*, hipStream_t, int,
-                                int, int, int);
+                                int, int, int, int, sli_attn_plan*, bool);
 
 size_t mha_part_bytes(int T, int H, int hd) {
     const int ppw_wg_min = attn_wg_positions(SLI_DT_F32, hd);
@@ -615,6 +633,71 @@ int sli_mha_strided(const float* q, const void* k, const void* v, int kv_dtype, 
         return mha_launch<f8e4m3>(q, (const f8e4m3*)k, (const f8e4m3*)v, out, 0, pos, nullptr, max_seq_len, head_dim,
                                   n_heads, n_kv_heads, pos_stride, head_stride, 0, (float*)workspace, counters, s);
     return fail(SLI_ERR_ARG, "sli_mha_strided: bad kv dtype");
+}
+
+}  // extern "C"
+
+// One decode attention launch as the engine records it (engine.hip StepRecorder::record_phase): sequence b owns kv heads
+// [b * hkv, (b + 1) * hkv) of one layer's head-major cache, seq_heads and the position stride only for a batch.
+// Everything that needs no pointer is decided by attn_shape_error; dry: the plan alone (sli_decode_attn_plan).
+static int attn_shape_error(const std::string& fn, const sli_attn_launch& a, const sli_attn_plan& p, bool with_device) {
+    SLI_CHECK(a.kv_dtype == SLI_DT_F32 || a.kv_dtype == SLI_DT_F16 || a.kv_dtype == SLI_DT_F8E4M3, SLI_ERR_ARG,
+              fn + ": bad kv dtype");
+    SLI_CHECK(a.hd == 64 || a.hd == 128, SLI_ERR_SHAPE, fn + ": head_dim must be 64 or 128");
+    SLI_CHECK(a.hq > 0 && a.hkv > 0 && a.hq % a.hkv == 0, SLI_ERR_SHAPE, fn + ": hq must be a multiple of hkv");
+    const int g = a.hq / a.hkv;
+    SLI_CHECK(g == 1 || g == 2 || g == 4 || g == 8, SLI_ERR_SHAPE, fn + ": heads per kv head must be 1, 2, 4 or 8");
+    SLI_CHECK(a.hq <= (1 << 12), SLI_ERR_SHAPE, fn + ": hq exceeds 4096");
+    SLI_CHECK(a.B >= 1 && a.B <= 8, SLI_ERR_SHAPE, fn + ": B must be 1 .. 8");
+    SLI_CHECK(a.T >= 1 && (int64_t)a.T * a.hd * a.hkv * a.B < ((int64_t)1 << 31), SLI_ERR_SHAPE,
+              fn + ": T must be positive (and one layer's cache below 2^31 elements)");
+    SLI_CHECK(a.B == 1 || a.pos_seq_stride >= 1, SLI_ERR_ARG, fn + ": pos_seq_stride must be >= 1 for a batch");
+    SLI_CHECK(a.merge >= 0 && a.merge <= 2, SLI_ERR_ARG, fn + ": merge must be 0 (in the launch), 1 (the consumer) or 2 (a merge launch)");
+    SLI_CHECK(a.kv_dtype != SLI_DT_F8E4M3 || a.merge != 1, SLI_ERR_ARG,
+              fn + ": an FP8 cache takes no merge in the consumer");
+    SLI_CHECK(p.cus >= 0, SLI_ERR_ARG, fn + ": cus must be >= 0");
+    SLI_CHECK(p.cus <= 4096 && !(p.cus > 0 && with_device && p.cus > device_cus()), SLI_ERR_ARG,
+              fn + ": cus exceeds the device's compute units");
+    return SLI_OK;
+}
+
+template <typename KT>
+static int attn_entry(const sli_attn_launch& a, sli_attn_plan* plan, hipStream_t s, bool dry) {
+    const bool batched = a.B > 1;
+    return mha_launch<KT>(a.q, (const KT*)a.k, (const KT*)a.v, a.out, 0, 0, a.pos, a.T, a.hd, a.B * a.hq, a.B * a.hkv,
+                          a.hd, (long long)a.T * a.hd, 0, a.part, a.counters, s, batched ? a.hkv : 0,
+                          batched ? a.pos_seq_stride : 0, 0, a.merge, plan->cus, plan, dry);
+}
+
+static int attn_dispatch(const sli_attn_launch& a, sli_attn_plan* plan, hipStream_t s, bool dry) {
+    if (a.kv_dtype == SLI_DT_F32) return attn_entry<float>(a, plan, s, dry);
+    if (a.kv_dtype == SLI_DT_F16) return attn_entry<__half>(a, plan, s, dry);
+    return attn_entry<f8e4m3>(a, plan, s, dry);
+}
+
+extern "C" {
+
+int sli_decode_attn_plan(const sli_attn_launch* launch, sli_attn_plan* plan) {
+    SLI_CHECK(launch && plan, SLI_ERR_ARG, "sli_decode_attn_plan: null pointer");
+    if (int rc = attn_shape_error("sli_decode_attn_plan", *launch, *plan, false)) return rc;
+    sli_attn_launch a = *launch;  // only the shape is read: the plan of aligned operands
+    a.q = nullptr, a.k = a.v = nullptr, a.out = a.part = nullptr, a.counters = nullptr, a.pos = nullptr;
+    return attn_dispatch(a, plan, nullptr, true);
+}
+
+int sli_decode_attn(const sli_attn_launch* launch, sli_attn_plan* plan, sli_stream_t stream) {
+    SLI_CHECK(launch && plan, SLI_ERR_ARG, "sli_decode_attn: null pointer");
+    const sli_attn_launch& a = *launch;
+    SLI_CHECK(a.q && a.k && a.v && a.out && a.part && a.counters && a.pos, SLI_ERR_ARG, "sli_decode_attn: null pointer");
+    SLI_CHECK((uintptr_t)a.q % 16 == 0 && (uintptr_t)a.k % 16 == 0 && (uintptr_t)a.v % 16 == 0 &&
+                  (uintptr_t)a.out % 16 == 0 && (uintptr_t)a.part % 16 == 0,
+              SLI_ERR_ARG, "sli_decode_attn: 16-byte alignment");
+    SLI_CHECK((uintptr_t)a.counters % 4 == 0 && (uintptr_t)a.pos % 4 == 0, SLI_ERR_ARG,
+              "sli_decode_attn: counters and pos are 4-byte aligned");
+    if (int rc = attn_shape_error("sli_decode_attn", a, *plan, true)) return rc;
+    sli_attn_plan dry = *plan;  // the launcher's own refusals (the split counts), before anything is launched
+    if (int rc = attn_dispatch(a, &dry, nullptr, true)) return rc;
+    return attn_dispatch(a, plan, as_stream(stream), false);
 }
 
 __global__ void quant_f8_kernel(const float* in, uint8_t* out, size_t n) {

@@ -1131,6 +1131,50 @@ def decode_gemv_logits(x, norm_w, eps: float, w, logits, keys, vocab_off: int = 
     return _decode_gemv(x, norm_w, eps, w, row_scale, scales, e, nrows, cus)
 
 
+def decode_attn_plan(kv_dtype: int, B: int, hq: int, hkv: int, hd: int, T: int, merge: int = 0, cus: int = 0,
+                     pos_seq_stride: int = 1):
+    """The geometry sli_decode_attn would run (sli_attn_plan as a dict), nothing launched; no device is needed when
+    cus != 0. kv_dtype: a DT_* code."""
+    a = _lib.AttnLaunch(kv_dtype=kv_dtype, B=B, hq=hq, hkv=hkv, hd=hd, T=T, merge=merge, pos_seq_stride=pos_seq_stride)
+    p = _lib.AttnPlan(cus=cus)
+    call("sli_decode_attn_plan", ctypes.byref(a), ctypes.byref(p))
+    return _gv_plan_dict(p)
+
+
+def _attn_part_floats(T: int, heads: int, hd: int) -> int:
+    """fp32 elements of the split partials of `heads` query heads over a T-row cache (the engine's own sizing)."""
+    return (_lib.load().sli_mha_workspace_bytes(T, heads, hd) - 4 * heads) // 4
+
+
+def decode_attn(q, k, v, out, part, counters, pos, hq: int, merge: int = 0, pos_seq_stride: int = 1, kv_dtype=None,
+                cus: int = 0):
+    """One decode attention launch as a model step records it (sli_decode_attn): q [B hq hd] fp32, k / v one layer of
+    the head-major cache [B hkv, T, hd], out [>= B hq hd] fp32, part [>= sli_mha_workspace_bytes(T, B hq, hd) / 4 - B hq] fp32,
+    counters [>= 2 B hkv] int32 (zero on entry), pos int32 on the device with sequence b's position at
+    pos[b * pos_seq_stride], 0 <= pos < T. merge: 0 in the launch, 1 left to the consumer, 2 a merge launch. Returns
+    the plan that ran as a dict."""
+    if k.dim() != 3 or k.shape != v.shape or k.dtype != v.dtype or q.dtype != torch.float32 or \
+            out.dtype != torch.float32 or part.dtype != torch.float32 or counters.dtype != torch.int32 or \
+            pos.dtype != torch.int32:
+        raise ValueError("Tensor with Wrong Dim!")
+    nkv, T, hd = k.shape
+    heads = q.numel() // hd
+    if heads * hd != q.numel() or heads % hq or nkv * hq % heads:
+        raise ValueError("Tensor with Wrong Dim!")
+    B = heads // hq
+    hkv = nkv // B
+    if B < 1 or hkv * B != nkv or out.numel() < q.numel() or part.numel() < _attn_part_floats(T, heads, hd) or \
+            counters.numel() < 2 * nkv or pos.numel() < (B - 1) * max(pos_seq_stride, 0) + 1:
+        raise ValueError("Tensor with Wrong Dim!")
+    _dev(q, k, v, out, part, counters, pos)
+    a = _lib.AttnLaunch(q=q.data_ptr(), k=k.data_ptr(), v=v.data_ptr(), kv_dtype=_kv_dt(k, kv_dtype),
+                        out=out.data_ptr(), part=part.data_ptr(), counters=counters.data_ptr(), pos=pos.data_ptr(),
+                        pos_seq_stride=pos_seq_stride, B=B, hq=hq, hkv=hkv, hd=hd, T=T, merge=merge)
+    p = _lib.AttnPlan(cus=cus)
+    call("sli_decode_attn", ctypes.byref(a), ctypes.byref(p), _s())
+    return _gv_plan_dict(p)
+
+
 def argmax(logits, out=None):
     """argmaxLayer::forward (argmax.cpp:7-17) on device: first index of the maximum."""
     out = torch.empty(1, device=logits.device, dtype=torch.int32) if out is None else out
